@@ -12,6 +12,13 @@ Metric: homomorphic AES-128 rounds/sec (enc) = 10 * states / wall time, summed o
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 under
 torch.distributed.run (one process per GPU; RANK/LOCAL_RANK/WORLD_SIZE from the env).
+
+A plain run sets up, warms up, times the K steps and prints the result line -- nothing else.
+--dump-outputs DIR also writes what the last timed step returned (dump_outputs).  --full adds
+everything else the bench measures or checks: the live kernel sampling behind the roofline
+figures, the precision pass, the check of every timed output against the plaintext AES, the
+secondary legs (batch / C5 round trip, multi-pair, folded, true-FHE, REF-call legs), the CPU
+baseline and the detail file.
 """
 from __future__ import annotations
 
@@ -47,6 +54,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the sampled kernel timing of the roofline figures, the precision "
+                         "pass, the plaintext-AES check of the timed outputs, the secondary legs, the CPU baseline, the detail "
+                         "file; the options below that select or size those take effect only with it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs); the key "
+                         "seed (--seed, default DUMP_SEED) and the encryption nonce are pinned, so runs with the same "
+                         "arguments have the same inputs")
     ap.add_argument("--kernel", default="ntt_rows_fwd", help="kernel id timed live for the roofline (the dominant kernel)")
     ap.add_argument("--kernel2", default="key_inner", help="secondary kernel id reported as roofline_secondary")
     ap.add_argument("--eager-steps", type=int, default=1,
@@ -117,10 +132,18 @@ def parse():
     ap.add_argument("--traffic-json", default=str(Path(__file__).resolve().parent / "profiles" / "r6_pmc_traffic_bench_final.json"),
                     help="per-kernel-class HBM / algorithmic byte ratios from rocprofv3 --pmc passes over this bench's own "
                          "C2 leg (tools/gpu_task.sh pmcbench; FETCH_SIZE and raw TCC write requests, separate runs)")
-    ap.add_argument("--detail-json", default="gpurun_out/bench_detail.json",
+    ap.add_argument("--detail-json", default=None,
                     help="the full per-leg / per-class record (prose included) is written here; stdout carries the compact "
-                         "line (<= 12 KB) that names this file; '' = do not write it")
-    return ap.parse_args()
+                         "line (<= 12 KB) that names this file; '' = do not write it (default: bench_detail.json beside this "
+                         "file with --full, not written without)")
+    args = ap.parse_args()
+    if not args.full and (args.whole_stats or args.profile_all):
+        ap.error("--whole-stats and --profile-all belong to the measurements behind --full")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU engine (not --dry-run)")
+    if args.detail_json is None:
+        args.detail_json = str(ROOT / "bench_detail.json") if args.full else ""
+    return args
 
 
 def dist_setup(want: int):
@@ -325,6 +348,37 @@ def measure_precision(pipe, ctx, rks, state, what: str) -> dict:
             "state_slots_per_stage": nslots,
             "note": f"slot error = angular distance of every state slot to the nearest 16th root of unity, over every "
                     f"logged stage of one encrypt of {what} (renorm / XOR4 / GF / SubBytes / bootstrap outputs)"}
+
+
+# --dump-outputs: the key seed when --seed is not given, the base of the per-rank encryption nonce, and
+# the size limit of everything written
+DUMP_SEED = 7
+DUMP_NONCE = 0x0D15EA5E
+DUMP_MAX_BYTES = 60_000_000
+
+
+def dump_outputs(path: Path, pipe, ctx, out) -> dict:
+    """--dump-outputs: the (ct_hi, ct_lo) pair the last timed encrypt returned, as float arrays in
+    path/<name>.npy: each ciphertext's RNS residues as the engine holds them ((polys, limbs, N) u32, exact in
+    float64), its decrypted slot values ((2, slots): real, imaginary) and the 16 decoded bytes (float32).
+    An array over its share of DUMP_MAX_BYTES is written as a fixed, seeded sample of its elements."""
+    E = ctx.engine
+    arrays = {}
+    for name, ct in zip(("hi", "lo"), out):
+        arrays[f"ct_{name}_residues"] = E.export(ct).astype(np.float64)
+        z = np.asarray(ctx.decrypt(ct))
+        arrays[f"ct_{name}_slots"] = np.stack([z.real, z.imag]).astype(np.float64)
+    arrays["bytes"] = np.asarray(pipe.encoder.decode(*out)).astype(np.float32)
+    path.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    rng = np.random.default_rng(64)
+    shapes = {}
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            a = a.ravel()[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+        np.save(path / f"{name}.npy", a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def rank_states(rank: int, n: int):
@@ -761,7 +815,7 @@ NOTES = {
                          "all launches' bytes / wall time / 8 TB/s",
     "traffic": "roofline.traffic = rocprofv3 --pmc HBM-side bytes / algorithmic bytes of the class x this launch's bytes",
     "precision": "max angular error of any state slot vs its Zeta16 codeword over all stages of one encrypt; margin pi/16",
-    "parity": "every timed output of every leg decoded and checked against FIPS-197 AES after the timed region; residues "
+    "parity": "--full: every timed output of every leg decoded and checked against FIPS-197 AES after the timed region; residues "
               "bit-exact vs the C oracle in tests/",
     "evaluation": "deferred relin/rescale, fused LUT kernels, batched key switches, periodic layout + sparse bootstraps (DESIGN.md 3-4)",
 }
@@ -861,7 +915,7 @@ def compact_line(full: dict, detail_path: str | None = None) -> dict:
     roofline_step / cpu_baseline objects as numbers, each leg's value and step fraction, and the
     prose once under `notes` (VERDICT r4 'do this' 1: <= 12 KB)."""
     line = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
-                                 "scaling", "vs_baseline", "dtype", "data") if k in full}
+                                 "scaling", "vs_baseline", "dtype", "data", "dumped_outputs") if k in full}
     line["value"] = _sig(line.get("value"), 6)
     line["ms_per_step"] = _sig(line.get("ms_per_step"), 6)
     cfg = full.get("config", {})
@@ -990,9 +1044,12 @@ def main():
 
     coeffs = load_all_coeffs()
     signature = 2 if args.no_final_bootstrap else 1
+    if args.dump_outputs and args.seed is None:
+        args.seed = DUMP_SEED
     seed = shared_seed(dist, args.seed)  # one key set for every rank (broadcast once, untimed)
     ctx = EngineContext(signature=signature, max_level=17, thread_count=1, device_id=local, seed=seed, lazy=not args.eager,
-                        concurrent=args.concurrent and not args.serial, boot_fresh_level=args.fresh_level, dnum=args.dnum)
+                        concurrent=args.concurrent and not args.serial, boot_fresh_level=args.fresh_level, dnum=args.dnum,
+                        enc_nonce=DUMP_NONCE + rank if args.dump_outputs else None)
     xor4 = XOR4LUT(ctx, coeffs["xor4"])
     from state_encoder import SlotLayout
     layout = SlotLayout(ctx.engine.slot_count, 1, periodic=not args.ref_layout)
@@ -1012,7 +1069,8 @@ def main():
         pipe.encrypt(states[i], rks)
     E.sync()
     import mi355x_ckks
-    tj = json.loads(Path(args.traffic_json).read_text()) if args.traffic_json and Path(args.traffic_json).exists() else {}
+    full = args.full
+    tj = json.loads(Path(args.traffic_json).read_text()) if full and args.traffic_json and Path(args.traffic_json).exists() else {}
     every = 1 if args.profile_all else args.profile_every
     # the sampled kernel classes (PROF_KIDS: the roofline kernels and the per-class fractions)
     kernels = list(mi355x_ckks.KERNEL_IDS) if args.profile_all else list(dict.fromkeys([args.kernel, args.kernel2] + PROF_KIDS))
@@ -1021,11 +1079,12 @@ def main():
     # written there (the algorithmic bytes of the counter pass's launches); without it (the counter pass
     # itself: no in-kernel timestamps under the counters) nothing is written
     whole = bool(args.whole_stats)
+    profiled = full and not whole  # a plain run times its steps with no kernel sampled
     account = whole and bool(os.environ.get("AESFHE_PROFILE_FROM_START"))
     pre = {}
     if whole:  # whole-process accounting: keep the from-start configuration, fold the pre-timed part in
         pre = E.kernel_stats(reset=True) if account else {}
-    else:
+    elif profiled:
         E.profile(kernels, every=every)
         # one profiled, untimed encrypt allocates the profiler's clock slots outside the timing
         pipe.encrypt(states[0], rks)
@@ -1035,7 +1094,7 @@ def main():
     outs = []
     E.sync()
     empty_pools(E)
-    leg = Leg(E).start() if not whole else None
+    leg = Leg(E).start() if profiled else None
     barrier(dist)
     # AESFHE_MARK_TIMED=1: a 250 ms idle gap on each side of the timed region (outside the timing),
     # so tools/trace_window.py can pick the timed launches out of a rocprofv3 kernel trace
@@ -1062,39 +1121,45 @@ def main():
         stats = E.kernel_stats(reset=True)
         tot = {k: {f: pre.get(k, {}).get(f, 0) + v.get(f, 0) for f in ("launches", "ms", "bytes")} for k, v in stats.items()}
         Path(args.whole_stats).write_text(json.dumps(tot, indent=1))
-    elif not whole:
+    elif profiled:
         leg.stop()
     elapsed = max_over_ranks(dist, elapsed)
     launches_per_encrypt = (launches1 - launches0) / args.steps
     # (a --whole-stats run skips it: its rocprofv3 --pmc pass must count exactly the accounted launches)
-    precision = measure_precision(pipe, ctx, rks, states[0], "one C2 state") if rank == 0 and not whole else None
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(Path(args.dump_outputs) / (f"rank{rank}" if rank else ""), pipe, ctx, outs[-1])
+    precision = measure_precision(pipe, ctx, rks, states[0], "one C2 state") if rank == 0 and profiled else None
 
-    batch = run_batch(ctx, coeffs, rks, args, rank, world, dist, tj) if args.batch_states > 0 else None
+    batch = run_batch(ctx, coeffs, rks, args, rank, world, dist, tj) if full and args.batch_states > 0 else None
     pairs_c3 = run_pairs(ctx, coeffs, rks, args, rank, world, dist, args.pair_states, 1, max(1, args.pair_stack), args.pair_steps,
                          f"C3 literally: {args.pair_states} ciphertext pairs (hi/lo) per GPU with ONE state each "
                          f"(REF/state_encoder.py:17-28), stacked {args.pair_stack} pairs per operand (DESIGN.md 3.16), full "
-                         f"AES-128 encrypt, N=2^16, renorm on, shared key", tj) if args.pair_states > 0 else None
+                         f"AES-128 encrypt, N=2^16, renorm on, shared key", tj) if full and args.pair_states > 0 else None
     pairs_packed = run_pairs(ctx, coeffs, rks, args, rank, world, dist, args.packed_pairs, 2048, args.packed_pairs,
                              args.packed_pair_steps,
                              f"{args.packed_pairs} x 2048 states per GPU: {args.packed_pairs} slot-packed ciphertext pairs stacked "
                              f"into one operand (DESIGN.md 3.9 + 3.16), full AES-128 encrypt, N=2^16, renorm on, shared key",
-                             tj) if args.packed_pairs > 0 else None
+                             tj) if full and args.packed_pairs > 0 else None
     folded = (run_folded(ctx, coeffs, rks, args, rank, world, dist, layout, 10.0 * args.steps * world / elapsed)
-              if args.folded_steps > 0 and not args.no_final_bootstrap and not whole else None)
+              if full and args.folded_steps > 0 and not args.no_final_bootstrap and not whole else None)
     true_fhe = (run_true_fhe(ctx, coeffs, rks, args, rank, world, dist, tj)
-                if args.true_fhe_steps > 0 and not args.no_final_bootstrap else None)
-    E.profile(())
-    eager = run_ref_calls(coeffs, rks, args, rank, world, dist, local, seed, tj, lazy=False) if args.eager_steps > 0 else None
-    deferred = run_ref_calls(coeffs, rks, args, rank, world, dist, local, seed, tj, lazy=True) if args.deferred_steps > 0 else None
+                if full and args.true_fhe_steps > 0 and not args.no_final_bootstrap else None)
+    if full:
+        E.profile(())
+    eager = run_ref_calls(coeffs, rks, args, rank, world, dist, local, seed, tj, lazy=False) if full and args.eager_steps > 0 else None
+    deferred = run_ref_calls(coeffs, rks, args, rank, world, dist, local, seed, tj, lazy=True) if full and args.deferred_steps > 0 else None
 
-    # correctness of the timed outputs (outside the timed region)
-    ok = all(np.array_equal(pipe.encoder.decode(*o), aes_plain.ref_encrypt(states[args.warmup + j], rks))
-             for j, o in enumerate(outs))
-    ok = all(r[0] for r in all_gather_ints(dist, [int(ok)]))  # every rank's outputs verified
+    # correctness of the timed outputs (outside the timed region; --full)
+    ok = None
+    if full:
+        ok = all(np.array_equal(pipe.encoder.decode(*o), aes_plain.ref_encrypt(states[args.warmup + j], rks))
+                 for j, o in enumerate(outs))
+        ok = all(r[0] for r in all_gather_ints(dist, [int(ok)]))  # every rank's outputs verified
 
     states_done = args.steps * world
     value = 10.0 * states_done / elapsed
-    if whole:
+    if not profiled:
         roof = dict(roofline=None, roofline_secondary=None, roofline_valu=None, roofline_step=None)
     else:
         roof = dict(
@@ -1134,8 +1199,8 @@ def main():
                     "inputs dropped to the renorm floor before renormalised steps (3.11), batched products (3.12); "
                     "the engine op counts per round are in op_counts_per_round; REF's own call sequence through the "
                     "same engine is the eager_ref_calls leg"),
-                   "blocks_per_s": states_done / elapsed, "verified_against_plaintext_model": bool(ok)},
-        "parity": "decoded bytes verified against FIPS-197 AES (oracle/aes_plain.py) for every timed output of every leg; "
+                   "blocks_per_s": states_done / elapsed, "verified_against_plaintext_model": None if ok is None else bool(ok)},
+        "parity": "decoded bytes verified against FIPS-197 AES (oracle/aes_plain.py) for every timed output of every leg (--full); "
                   "engine residues bit-exact against the C oracle (oracle/ckks_oracle.c) in tests/test_gpu_parity.py; "
                   "raw-ciphertext parity with the reference's desilofhe engine is unpinnable (closed binary, absent)",
         **roof,
@@ -1146,6 +1211,8 @@ def main():
         "precision": precision,
         "op_counts_per_round": {k: v / (10.0 * args.steps) for k, v in counters.items()},
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if batch is not None:
         line["batch"] = batch
     if pairs_c3 is not None:
@@ -1161,7 +1228,7 @@ def main():
     if deferred is not None:
         line["deferred_ref_calls"] = deferred
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(coeffs, boot_tallies(ctx, 2 * layout.period if layout.periodic else None))
         print(emit_line(line, args.detail_json or None), flush=True)
     if dist is not None:

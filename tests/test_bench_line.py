@@ -71,3 +71,59 @@ def test_sig_rounding():
     assert bench._sig(0.362346652, 3) == 0.362
     assert bench._sig(47095808.0, 4) == 47100000.0
     assert bench._sig(5) == 5 and bench._sig(None) is None and bench._sig(True) is True
+
+
+def test_plain_run_is_the_default_and_full_keeps_the_detail_file(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.detail_json == "" and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.detail_json.endswith("bench_detail.json") and a.dump_outputs == "d"
+
+
+def test_plain_record_gives_a_line_with_the_contract_keys():
+    """a plain run's record: no roofline, precision, leg or baseline, verification not done (None)"""
+    full = {k: v for k, v in _full().items() if k not in bench.LEG_KEYS + ("cpu_baseline",)}
+    full.update(roofline=None, roofline_secondary=None, roofline_valu=None, roofline_step=None, precision=None,
+                dumped_outputs={"bytes": [16]})
+    full["config"]["verified_against_plaintext_model"] = None
+    line = json.loads(bench.emit_line(full, None))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert line[k] is not None, k
+    assert line["roofline"] is None and line["dumped_outputs"] == {"bytes": [16]} and "cpu_baseline" not in line
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays per ciphertext and the decoded bytes; an array over its share of the
+    size limit is written as the same seeded sample every time"""
+    import numpy as np
+
+    class Eng:
+        def export(self, ct):
+            return np.arange(2 * 3 * 64, dtype=np.uint32).reshape(2, 3, 64) + ct
+
+    class Ctx:
+        engine = Eng()
+
+        def decrypt(self, ct):
+            return np.exp(2j * np.pi * (np.arange(32) + ct) / 16)
+
+    class Pipe:
+        class encoder:
+            @staticmethod
+            def decode(hi, lo):
+                return np.arange(16, dtype=np.uint8)
+
+    shapes = bench.dump_outputs(tmp_path / "a", Pipe, Ctx(), (1, 2))
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["bytes.npy", "ct_hi_residues.npy", "ct_hi_slots.npy", "ct_lo_residues.npy", "ct_lo_slots.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["ct_lo_residues.npy"], Eng().export(2)) and shapes["ct_hi_slots"] == [2, 32]
+    assert np.array_equal(got["bytes.npy"], np.arange(16))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5 * 800)  # 100 float64 per array: the residues (384) are sampled
+    bench.dump_outputs(tmp_path / "b", Pipe, Ctx(), (1, 2))
+    bench.dump_outputs(tmp_path / "c", Pipe, Ctx(), (1, 2))
+    b, c = np.load(tmp_path / "b" / "ct_hi_residues.npy"), np.load(tmp_path / "c" / "ct_hi_residues.npy")
+    assert b.shape == (100,) and np.array_equal(b, c) and np.isin(b, got["ct_hi_residues.npy"]).all()
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= 5 * 800 + 5 * 128

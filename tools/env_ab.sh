@@ -7,7 +7,7 @@
 set -e -o pipefail
 O=gpurun_out/$1; shift
 mkdir -p $O
-ARGS=${AB_ARGS:-"--no-cpu-baseline --batch-states 0 --folded-steps 0 --true-fhe-steps 0 --pair-states 0 --packed-pairs 0 --eager-steps 0 --deferred-steps 0 --steps 10"}
+ARGS=${AB_ARGS:-"--full --no-cpu-baseline --batch-states 0 --folded-steps 0 --true-fhe-steps 0 --pair-states 0 --packed-pairs 0 --eager-steps 0 --deferred-steps 0 --steps 10"}
 for pass in $(seq 1 ${PASSES:-2}); do
   for cfg in "$@"; do
     envs=()

@@ -26,7 +26,7 @@ O=gpurun_out/${1:?out dir}
 shift
 mkdir -p $O
 export TMPDIR=/tmp
-C2="--no-cpu-baseline --batch-states 0 --folded-steps 0 --true-fhe-steps 0 --pair-states 0 --packed-pairs 0 --eager-steps 0 --deferred-steps 0"
+C2="--full --no-cpu-baseline --batch-states 0 --folded-steps 0 --true-fhe-steps 0 --pair-states 0 --packed-pairs 0 --eager-steps 0 --deferred-steps 0"
 for t in "$@"; do
   echo "[gpu_task] $t $(date +%T)"
   case $t in
@@ -36,7 +36,7 @@ for t in "$@"; do
     smoke)
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 ;;
     bench)
-      timeout -k 10 900 python3 bench.py --detail-json $O/bench_detail.json ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err ;;
+      timeout -k 10 900 python3 bench.py --full --detail-json $O/bench_detail.json ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err ;;
     c2)
       timeout -k 10 400 python3 bench.py --steps 12 --warmup 2 $C2 ${BENCH_ARGS:-} > $O/c2.json 2> $O/c2.err ;;
     rocwin)
@@ -82,13 +82,13 @@ for t in "$@"; do
       rm -rf $O/pmcb_fetch $O/pmcb_write ;;
     twogpu)
       AESFHE_DIST_BACKEND=gloo timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr=127.0.0.1 \
-          --master-port=29517 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --batch-states 1024 --c5-states 256 \
+          --master-port=29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --batch-states 1024 --c5-states 256 \
           --pair-states 0 --packed-pairs 0 --true-fhe-steps 0 --eager-steps 0 --deferred-steps 0 > $O/bench_2rank_1gpu.json 2> $O/twogpu.err ;;
     rccl1)
       # the RCCL ("nccl") process-group path of bench.py on ONE MI355X: one rank under torch.distributed.run
       # with AESFHE_FORCE_DIST=1 (key broadcast, barriers, all_gather and max-over-ranks as GPU tensors)
       AESFHE_FORCE_DIST=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr=127.0.0.1 \
-          --master-port=29531 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --batch-states 256 --c5-states 256 \
+          --master-port=29531 bench.py --full --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --batch-states 256 --c5-states 256 \
           --pair-states 0 --packed-pairs 0 --true-fhe-steps 0 --eager-steps 0 --deferred-steps 0 > $O/bench_rccl_1rank.json 2> $O/rccl1.err ;;
     boot)
       timeout -k 10 300 python3 tools/boot_phases.py 32 ${BOOT_SET:-7 4} > $O/boot_phases.json 2> $O/boot.err ;;
