@@ -211,6 +211,7 @@ public:
         for (auto& pl : pools_) pl.release_all();
         for (void* p : owned_) (void)hipFree(p);
         for (auto& kv : ksk_) (void)hipFree(kv.second);
+        for (auto& kv : ksk_low_) (void)hipFree(kv.second);
         for (int k = 0; k < kStreams; ++k) {
             (void)hipEventDestroy(fj_ev_[k]);
             (void)hipStreamDestroy(streams_[k]);
@@ -347,6 +348,131 @@ public:
     LimbMap extmap(int nl) const { return LimbMap{nl, 0, hp_.p_off()}; }
     static LimbMap single(int prime) { return LimbMap{1, prime, 0}; }
 
+    // ------------------------------------------------------------------ key-switching basis of a level
+    // The special basis a key switch at `level` runs over: all n_p special primes
+    // with the dnum-digit keys, or -- AESFHE_LOW_P / aesfhe_set_low_p, levels of nl < alpha limbs
+    // (one digit) -- P_l = the first nl + 1 special primes with that level's own single-digit keys.
+    // P_l is a prefix of the special primes, so extmap(nl) and the P LimbMaps serve both.
+    struct KsBasis {
+        bool low = false, built = false;
+        int np = 0;        // special primes
+        int nkey = 0;      // key rows per polynomial
+        int nks = 0;       // key row of the first special prime
+        const u32* gadget = nullptr;    // [nl] pairs: P mod q_t
+        const u32* modup = nullptr;     // digit 0's ModUp table of this limb count (digit j: modup_tab)
+        const u32* modup_qh = nullptr;  // the ModUp INTT's post factors
+        const u32* moddown = nullptr;   // [np][nl] pairs
+        const u32* phinv = nullptr;     // [np] pairs
+        const u32* pinv = nullptr;      // [nl] pairs: P^-1 mod q_t
+        const u32* negp = nullptr;      // [nl]: -P mod q_t
+        const u32* mdr = nullptr;       // ModDown fused with the rescale (nullptr: not available)
+    };
+    bool low_p_ = env_int("AESFHE_LOW_P", 0) != 0;
+    int full_p_scope_ = 0;  // > 0: inside a path that keeps the full basis (FullP)
+    struct FullP {          // the hoisted linear-transform paths of the bootstrap keep the full basis
+        Engine& e;
+        explicit FullP(Engine& e_) : e(e_) { ++e.full_p_scope_; }
+        ~FullP() { --e.full_p_scope_; }
+    };
+    void set_low_p(bool on) { low_p_ = on; }
+    bool low_p() const { return low_p_; }
+    bool low_level(int level) const { return low_p_ && !full_p_scope_ && level >= 0 && level <= hp_.L && hp_.nl(level) < hp_.alpha; }
+    int np_at(int level) const { return low_level(level) ? hp_.nl(level) + 1 : hp_.n_p; }
+    const KsBasis& kb(int level) {
+        const bool low = low_level(level);
+        auto& v = low ? kb_low_ : kb_full_;
+        if (v.empty()) v.resize(hp_.L + 3);
+        KsBasis& b = v[level + 1];
+        if (b.built) return b;
+        const int nl = hp_.nl(level);
+        b.low = low;
+        if (!low) {
+            b.np = hp_.n_p, b.nkey = hp_.n_ks + hp_.n_p, b.nks = hp_.n_ks;
+            b.gadget = d_gadget_;
+            b.modup = d_modup_ + modup_off_[(size_t)nl * hp_.dnum];
+            b.modup_qh = d_modup_qh_ + modup_qh_off_[nl];
+            b.moddown = d_moddown_ + moddown_off_[nl];
+            b.phinv = d_moddown_phinv_, b.pinv = d_pinv_, b.negp = d_negp_;
+            b.mdr = level >= 1 && level <= hp_.L && mdr_off_[level] != SIZE_MAX ? d_mdr_ + mdr_off_[level] : nullptr;
+        } else {
+            build_low_basis(b, level);
+        }
+        b.built = true;
+        return b;
+    }
+    // digit j's ModUp table at `level`: [h][ne] qhat pairs, [h] qhat^-1 pairs, [ne] -Q_digit
+    const u32* modup_tab(const KsBasis& b, int level, int j) const {
+        return b.low ? b.modup : d_modup_ + modup_off_[(size_t)hp_.nl(level) * hp_.dnum + j];
+    }
+    // the reduced basis' tables: the layouts of build_tables' full-basis tables with np = nl + 1
+    void build_low_basis(KsBasis& b, int level) {
+        const auto& q = hp_.mod;
+        auto mulm = [](u64 a, u64 c, u32 m) { return (u32)(a % m * (c % m) % m); };
+        const int nl = hp_.nl(level), np = nl + 1, ne = nl + np, po = hp_.p_off();
+        b.np = np, b.nkey = ne, b.nks = nl;
+        auto tq = [&](int x) { return x < nl ? q[x] : q[po + x - nl]; };
+        auto prod = [&](const std::vector<u32>& src, int skip, u32 m) {
+            u32 v = 1;
+            for (int i = 0; i < (int)src.size(); ++i)
+                if (i != skip) v = mulm(v, src[i], m);
+            return v;
+        };
+        std::vector<u32> Q(q.begin(), q.begin() + nl), P(q.begin() + po, q.begin() + po + np);
+        // P_l must exceed the digit's modulus Q_l by about one prime: every prime lies in
+        // (2^29, 2^30) and the special primes are the largest of them, so the surplus is ~2^30; checked
+        double surplus = 0.0;
+        for (u32 v : P) surplus += std::log2((double)v);
+        for (u32 v : Q) surplus -= std::log2((double)v);
+        if (surplus < 29.0) throw std::runtime_error("low-P basis: P_l / Q_l below 2^29 at level " + std::to_string(level));
+        std::vector<u32> t;
+        auto pair_ = [&](u32 v, u32 m) { t.push_back(v), t.push_back(shoup_pre(v, m)); };
+        const size_t o_gad = t.size();
+        for (int x = 0; x < nl; ++x) pair_(prod(P, -1, q[x]), q[x]);
+        const size_t o_up = t.size();  // [nl][ne] qhat pairs, [nl] qhat^-1 pairs, [ne] -Q_l
+        for (int i = 0; i < nl; ++i)
+            for (int x = 0; x < ne; ++x) pair_(prod(Q, i, tq(x)), tq(x));
+        const size_t o_qh = t.size();
+        for (int i = 0; i < nl; ++i) pair_(hinvm(prod(Q, i, q[i]), q[i]), q[i]);
+        for (int x = 0; x < ne; ++x) {
+            const u32 v = prod(Q, -1, tq(x));
+            t.push_back(v ? tq(x) - v : 0);
+        }
+        const size_t o_dn = t.size();  // [np][nl] pairs of phat_k mod q_t
+        for (int k = 0; k < np; ++k)
+            for (int x = 0; x < nl; ++x) pair_(prod(P, k, q[x]), q[x]);
+        const size_t o_ph = t.size();
+        for (int k = 0; k < np; ++k) pair_(hinvm(prod(P, k, P[k]), P[k]), P[k]);
+        const size_t o_pinv = t.size();
+        for (int x = 0; x < nl; ++x) pair_(hinvm(prod(P, -1, q[x]), q[x]), q[x]);
+        const size_t o_negp = t.size();
+        for (int x = 0; x < nl; ++x) {
+            const u32 v = prod(P, -1, q[x]);
+            t.push_back(v ? q[x] - v : 0);
+        }
+        // ModDown fused with the rescale (build_tables' d_mdr_ layout): the k dropped limbs, then P_l
+        size_t o_mdr = SIZE_MAX;
+        if (level >= 1) {
+            const int r = hp_.nl(level - 1), k = nl - r, h = k + np;
+            if (k >= 1 && h <= kMaxConvH) {
+                std::vector<u32> src(q.begin() + r, q.begin() + nl);
+                src.insert(src.end(), P.begin(), P.end());
+                o_mdr = t.size();
+                for (int i = 0; i < h; ++i)
+                    for (int x = 0; x < r; ++x) pair_(prod(src, i, q[x]), q[x]);
+                for (int i = 0; i < h; ++i) pair_(hinvm(prod(src, i, src[i]), src[i]), src[i]);
+                for (int x = 0; x < r; ++x) {
+                    const u32 v = prod(src, -1, q[x]);
+                    t.push_back(v ? q[x] - v : 0);
+                }
+                for (int x = 0; x < r; ++x) pair_(hinvm(prod(src, -1, q[x]), q[x]), q[x]);
+            }
+        }
+        const u32* d = dev_upload(t);
+        b.gadget = d + o_gad, b.modup = d + o_up, b.modup_qh = d + o_qh, b.moddown = d + o_dn, b.phinv = d + o_ph;
+        b.pinv = d + o_pinv, b.negp = d + o_negp, b.mdr = o_mdr == SIZE_MAX ? nullptr : d + o_mdr;
+    }
+    std::vector<KsBasis> kb_full_, kb_low_;
+
     void ntt(u32* d, int rows, int nl, LimbMap m) {
         launch_ntt_fwd(S(), T_, d, rows, nl, m);
         cnt_[C_NTT_ROWS] += rows;
@@ -456,22 +582,8 @@ public:
         HIP_OK(hipMalloc(&raw, ksk_words(g) * sizeof(u32)));
         u32* key = (u32*)raw;
         // source secret s' (Q limbs 0..n_ks-1) and target secret (all primes) of the key
-        u32* sp = tmp(nks);
+        u32* sp = key_source(g);
         const u32* target = d_s_;
-        if (g == 0) {
-            launch_square(S(), T_, sp, d_s_, nks, nks, qmap());
-        } else if (g == tag_s2d()) {  // sparse s_sp -> dense s
-            launch_copy_rows(S(), T_, sp, sparse_secret(), nks);
-        } else if (is_tag_s2d_rot(g)) {  // sigma_g'(s_sp) -> dense s
-            launch_automorph(S(), T_, sp, sparse_secret(), g - 8ull * n, nks);
-        } else if (is_tag_sq(g)) {    // sigma_g'(s)^2 -> s: the automorphism of a 3-polynomial tensor
-            u32* s2 = tmp(nks);
-            launch_square(S(), T_, s2, d_s_, nks, nks, qmap());
-            launch_automorph(S(), T_, sp, s2, g - 4ull * n, nks);
-            untmp(s2, nks);
-        } else {
-            launch_automorph(S(), T_, sp, d_s_, g, nks);
-        }
         u32* e = tmp(nkey);
         const LimbMap em = extmap(nks);
         for (int j = 0; j < hp_.dnum; ++j) {
@@ -488,6 +600,57 @@ public:
         ksk_[g] = key;
         HIP_OK(hipStreamSynchronize(S()));  // shared by every stream from now on
         return key;
+    }
+    // the switching key of tag g for a key switch at `level`: the full key, or on a reduced level
+    // (low_level) that level's own key over Q_l * P_l, [2][nl + np][N] -- one digit, so
+    // (-a s + e + (P_l mod q_t) s', a) with fresh a, e (PRNG streams 10 / 11, sub-stream = level);
+    // made on first use and kept resident
+    const u32* ksk_at(u64 g, int level) {
+        if (!low_level(level)) return ksk(g);
+        const auto id = std::make_pair(g, level);
+        auto it = ksk_low_.find(id);
+        if (it != ksk_low_.end()) return it->second;
+        if (!d_s_) throw std::runtime_error("keys not generated");
+        if (g == tag_d2s()) throw std::runtime_error("ksk_at: the dense -> sparse key has its own basis");
+        const KsBasis& B = kb(level);
+        const int n = hp_.n, nl = hp_.nl(level), nkey = B.nkey;
+        void* raw = nullptr;
+        HIP_OK(hipMalloc(&raw, (size_t)2 * nkey * n * sizeof(u32)));
+        u32* b = (u32*)raw;
+        u32* a = b + (size_t)nkey * n;
+        u32* sp = key_source(g);
+        u32* e = tmp(nkey);
+        const LimbMap em = extmap(nl);
+        launch_sample_uniform(S(), T_, a, nkey, em, pkey(), stream_id(10, g, level));
+        launch_sample_small(S(), T_, e, nkey, em, pkey(), stream_id(11, g, level), 1);
+        ntt(e, nkey, nkey, em);
+        launch_keygen_combine(S(), T_, b, a, d_s_, e, sp, B.gadget, nkey, em, 0, nl);
+        untmp(e, nkey);
+        untmp(sp, hp_.n_ks);
+        ksk_low_[id] = b;
+        HIP_OK(hipStreamSynchronize(S()));  // shared by every stream from now on
+        return b;
+    }
+    std::map<std::pair<u64, int>, u32*> ksk_low_;
+    // source secret s' of the key of tag g on Q limbs 0..n_ks-1 (tmp; the caller untmps n_ks rows)
+    u32* key_source(u64 g) {
+        const int n = hp_.n, nks = hp_.n_ks;
+        u32* sp = tmp(nks);
+        if (g == 0) {
+            launch_square(S(), T_, sp, d_s_, nks, nks, qmap());
+        } else if (g == tag_s2d()) {  // sparse s_sp -> dense s
+            launch_copy_rows(S(), T_, sp, sparse_secret(), nks);
+        } else if (is_tag_s2d_rot(g)) {  // sigma_g'(s_sp) -> dense s
+            launch_automorph(S(), T_, sp, sparse_secret(), g - 8ull * n, nks);
+        } else if (is_tag_sq(g)) {    // sigma_g'(s)^2 -> s: the automorphism of a 3-polynomial tensor
+            u32* s2 = tmp(nks);
+            launch_square(S(), T_, s2, d_s_, nks, nks, qmap());
+            launch_automorph(S(), T_, sp, s2, g - 4ull * n, nks);
+            untmp(s2, nks);
+        } else {
+            launch_automorph(S(), T_, sp, d_s_, g, nks);
+        }
+        return sp;
     }
 
     // ------------------------------------------------------------------ codec
@@ -744,7 +907,7 @@ public:
     Ct relin_raw(const Ct& c) {
         const int nl = hp_.nl(c.level), n = hp_.n;
         const size_t ms = (size_t)3 * nl * n;  // member stride of a batched tensor
-        Ct r = keyswitch(c.data + (size_t)2 * nl * n, c.level, ksk(0), c.data, c.data + (size_t)nl * n, c.nb, ms, ms);
+        Ct r = keyswitch(c.data + (size_t)2 * nl * n, c.level, ksk_at(0, c.level), c.data, c.data + (size_t)nl * n, c.nb, ms, ms);
         r.pend = c.pend;
         r.lazy = c.lazy && c.pend > 0;
         cnt_[C_RELIN]++;
@@ -1448,7 +1611,8 @@ public:
     // the fused key-switch core, ki_core)
     u32* modup(const u32* d, int level, int nb = 1, size_t d_ms = 0, const TensorPtrs* tp = nullptr, bool rev = false,
                bool cols_only = false) {
-        const int n = hp_.n, nl = hp_.nl(level), np = hp_.n_p, ne = nl + np, alpha = hp_.alpha;
+        const KsBasis& B = kb(level);
+        const int n = hp_.n, nl = hp_.nl(level), np = B.np, ne = nl + np, alpha = hp_.alpha;
         const int nd = (nl + alpha - 1) / alpha;
         if (alpha > kMaxConvH || np > kMaxConvH || nb * nd > kMaxConvGroups) throw std::runtime_error("keyswitch: digit too large");
         const LimbMap em = extmap(nl);
@@ -1458,7 +1622,7 @@ public:
         // k_bx_cols: the INTT's row pass here, its column pass + the conversion + the ext rows'
         // forward column pass in one launch
         const bool bx = bx_ok() && alpha <= kBxMaxH;
-        const u32* up_post = conv_pre_ && !bx ? d_modup_qh_ + modup_qh_off_[nl] : nullptr;
+        const u32* up_post = conv_pre_ && !bx ? B.modup_qh : nullptr;
         if (bx) {
             const RowMap rm{nl, nb > 1 ? (int)(d_ms / n) : nl, nl, 0, 0};
             if (rev) launch_ntt_inv_rows(S(), T_, coef, d, nb * nl, rm, qmap(), nullptr, true);
@@ -1472,10 +1636,9 @@ public:
             launch_ntt_inv_prod(S(), T_, coef, *tp, nb * nl, RowMap{nl, nl, nl, 0, 0}, qmap(), up_post);
             cnt_[C_NTT_ROWS] += nb * nl;
         } else {
-            intt(coef, d, nb * nl, RowMap{nl, nb > 1 ? (int)(d_ms / n) : nl, nl, 0, 0}, qmap(), fz ? d_modup_qh_ + modup_qh_off_[nl] : up_post);
+            intt(coef, d, nb * nl, RowMap{nl, nb > 1 ? (int)(d_ms / n) : nl, nl, 0, 0}, qmap(), fz ? B.modup_qh : up_post);
         }
         u32* ext = tmp((size_t)nb * nd * ne);
-        const size_t* toff = &modup_off_[(size_t)nl * hp_.dnum];
         ConvBatch up;
         up.n = nb * nd;
         up.pre = up_post != nullptr;
@@ -1485,7 +1648,7 @@ public:
                 up.h[gi] = h, up.d0[gi] = lo, up.skip0[gi] = lo;
                 up.src[gi] = coef + ((size_t)m * nl + lo) * n;
                 up.dst[gi] = ext + (size_t)gi * ne * n;
-                up.tab[gi] = d_modup_ + toff[j];
+                up.tab[gi] = modup_tab(B, level, j);
                 up.qhinv[gi] = up.tab[gi] + (size_t)2 * h * ne;
                 up.negq[gi] = up.qhinv[gi] + 2 * h;
             }
@@ -1536,25 +1699,27 @@ public:
         const u32* key;
     };
     void ki_core(u32* acc, u32* ys, int level, int kept, int nb, const KiSrc* src, int nsrc, size_t d_ms, KsFold fold) {
-        const int nl = hp_.nl(level), np = hp_.n_p, ne = nl + np, n = hp_.n;
+        const KsBasis& B = kb(level);
+        const int nl = hp_.nl(level), np = B.np, ne = nl + np, n = hp_.n;
         KiArgs a;
         for (int i = 0; i < nsrc; ++i) a.ext[i] = src[i].ext, a.d[i] = src[i].d, a.key[i] = src[i].key;
         a.nsrc = nsrc;
         a.nd = (nl + hp_.alpha - 1) / hp_.alpha, a.ne = ne, a.nl = nl, a.alpha = hp_.alpha;
-        a.nkey = hp_.n_ks + np, a.nks = hp_.n_ks;
+        a.nkey = B.nkey, a.nks = B.nks;
         a.kept = kept, a.ys_rows = ne - kept, a.nb = nb;
         a.ext_ms = (size_t)a.nd * ne * n, a.d_ms = d_ms, a.acc_ms = (size_t)2 * ne * n, a.ys_ms = (size_t)2 * (ne - kept) * n;
         a.acc = acc, a.ys = ys, a.fold = fold;
         launch_ntt_ki(S(), T_, a, extmap(nl));  // its row passes are counted with the column passes they pair with
     }
-    int ext_rows(int level) const { return (hp_.nl(level) + hp_.alpha - 1) / hp_.alpha * (hp_.nl(level) + hp_.n_p); }
+    int ext_rows(int level) const { return (hp_.nl(level) + hp_.alpha - 1) / hp_.alpha * (hp_.nl(level) + np_at(level)); }
     // acc (2 x ne rows, Q*P) = sum_j ext_j * key_j; g != 0 reads ext and d through X -> X^g
     // nb batched ciphertexts (ext = [m][nd][ne], d + m d_ms, acc = [m][2][ne]) share the key reads
     void key_inner(u32* acc, const u32* ext, const u32* d, const u32* key, int level, u64 g, int nb = 1, size_t d_ms = 0,
                    KsFold fold = {}, bool accum = false) {
-        const int nl = hp_.nl(level), np = hp_.n_p, ne = nl + np, n = hp_.n;
+        const KsBasis& B = kb(level);
+        const int nl = hp_.nl(level), np = B.np, ne = nl + np, n = hp_.n;
         const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner(S(), T_, acc, ext, d, key, nd, ne, nl, hp_.alpha, hp_.n_ks + np, hp_.n_ks, extmap(nl), g, nb,
+        launch_key_inner(S(), T_, acc, ext, d, key, nd, ne, nl, hp_.alpha, B.nkey, B.nks, extmap(nl), g, nb,
                          (size_t)nd * ne * n, d_ms, (size_t)2 * ne * n, fold, accum);
     }
     // ModDown by P: coefficients of the P rows (read in place from acc), conversion of both
@@ -1566,7 +1731,8 @@ public:
     // ys_in: the P rows already through the INTT's row pass (ki_core, [m][2][np]): only its column pass runs here
     Ct moddown(const u32* acc, int level, const u32* add0, const u32* add1, int nb = 1, size_t add_ms = 0, u32* dst = nullptr,
                u32* const* outm = nullptr, bool add_rev = false, u32* ys_in = nullptr) {
-        const int n = hp_.n, nl = hp_.nl(level), np = hp_.n_p, ne = nl + np, npl = 2 * nb;
+        const KsBasis& B = kb(level);
+        const int n = hp_.n, nl = hp_.nl(level), np = B.np, ne = nl + np, npl = 2 * nb;
         if (npl > kMaxConvGroups) throw std::runtime_error("moddown: batch too large");
         const bool fz = fused_conv(false);
         u32* yp = ys_in ? ys_in : tmp((size_t)npl * np);
@@ -1576,13 +1742,12 @@ public:
             cnt_[C_NTT_ROWS] += (size_t)npl * np;
         } else if (ys_in) {
             if (fz) throw std::runtime_error("moddown: a fused-core input needs the separate conversion");
-            launch_ntt_inv_cols(S(), T_, yp, npl * np, rows_dense(np), LimbMap{np, hp_.p_off(), 0}, conv_pre_ ? d_moddown_phinv_ : nullptr);
+            launch_ntt_inv_cols(S(), T_, yp, npl * np, rows_dense(np), LimbMap{np, hp_.p_off(), 0}, conv_pre_ ? B.phinv : nullptr);
             cnt_[C_NTT_ROWS] += (size_t)npl * np;
         } else {
-            intt(yp, acc, npl * np, RowMap{np, ne, np, nl, 0}, LimbMap{np, hp_.p_off(), 0}, fz || conv_pre_ ? d_moddown_phinv_ : nullptr);
+            intt(yp, acc, npl * np, RowMap{np, ne, np, nl, 0}, LimbMap{np, hp_.p_off(), 0}, fz || conv_pre_ ? B.phinv : nullptr);
         }
         u32* conv = tmp((size_t)npl * nl);
-        const size_t doff = moddown_off_[nl];
         ConvBatch dn;
         dn.n = npl;
         dn.pre = conv_pre_ && !bx;
@@ -1590,9 +1755,9 @@ public:
             dn.h[p] = np, dn.d0[p] = hp_.p_off(), dn.skip0[p] = 1 << 30;
             dn.src[p] = yp + (size_t)p * np * n;
             dn.dst[p] = conv + (size_t)p * nl * n;
-            dn.tab[p] = d_moddown_ + doff;
-            dn.qhinv[p] = d_moddown_phinv_;
-            dn.negq[p] = d_negp_;
+            dn.tab[p] = B.moddown;
+            dn.qhinv[p] = B.phinv;
+            dn.negq[p] = B.negp;
         }
         if (bx) launch_bx_cols(S(), T_, dn, nl, qmap());
         else if (!fz) launch_base_convert(S(), T_, dn, nl, qmap());
@@ -1604,11 +1769,11 @@ public:
         }
         if (fz && add_rev) throw std::runtime_error("moddown: the reversed addend needs the separate conversion");
         if (bx)
-            launch_ntt_finish_rows(S(), T_, o.data, conv, acc, ne, d_pinv_, add0, add1, npl, nl, add_ms, outm, add_rev);
+            launch_ntt_finish_rows(S(), T_, o.data, conv, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm, add_rev);
         else if (fz)
-            launch_ntt_finish_conv(S(), T_, o.data, conv, dn, acc, ne, d_pinv_, add0, add1, npl, nl, add_ms, outm);
+            launch_ntt_finish_conv(S(), T_, o.data, conv, dn, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm);
         else
-            launch_ntt_finish(S(), T_, o.data, conv, acc, ne, d_pinv_, add0, add1, npl, nl, add_ms, outm, 0u, nullptr, add_rev);
+            launch_ntt_finish(S(), T_, o.data, conv, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm, 0u, nullptr, add_rev);
         cnt_[C_NTT_ROWS] += (size_t)npl * nl;
         if (!ys_in) untmp(yp, (size_t)npl * np);
         untmp(conv, (size_t)npl * nl);
@@ -1620,7 +1785,7 @@ public:
     // chunks, each chunk's ModDown writing its rows of the one stacked result.
     Ct keyswitch(const u32* d, int level, const u32* key, const u32* add0, const u32* add1, int nb = 1, size_t d_ms = 0,
                  size_t add_ms = 0, u32* dst = nullptr) {
-        const int ne = hp_.nl(level) + hp_.n_p, ch = ks_chunk(level);
+        const int ne = hp_.nl(level) + np_at(level), ch = ks_chunk(level);
         if (nb > ch) {
             Ct o;
             if (dst) {
@@ -1637,7 +1802,7 @@ public:
             return o;
         }
         if (fused_ki_ok()) {
-            const int np = hp_.n_p;
+            const int np = np_at(level);
             u32* ext = modup(d, level, nb, d_ms, nullptr, false, true);
             u32* acc = tmp(2 * (size_t)ne * nb);
             u32* ys = tmp(2 * (size_t)np * nb);
@@ -1741,15 +1906,15 @@ public:
         const int nd = (hp_.nl(level) + hp_.alpha - 1) / hp_.alpha;
         return std::max(1, std::min(kMaxKsBatch, kMaxConvGroups / nd));
     }
-    bool fused_relin_rescale_ok(const Ct& c) const {
+    bool fused_relin_rescale_ok(const Ct& c) {
         if (!fuse_rr_ || pm(c) != 3 || c.pend < 1 || c.level < 1 || c.zero) return false;
-        return mdr_off_[c.level] != SIZE_MAX && 2 * ks_chunk(c.level) <= kMaxConvGroups;
+        return kb(c.level).mdr && 2 * ks_chunk(c.level) <= kMaxConvGroups;
     }
     // a stack of more than ks_chunk members in chunks, each chunk's ModDown writing its rows of
     // the one stacked result
     // outm (nb <= ks_chunk): member m's result straight into outm[m]; the returned Ct has no data
     Ct relin_rescale(const Ct& c, u32* const* outm = nullptr) {
-        const int l = c.level, n = hp_.n, nl = hp_.nl(l), ne = nl + hp_.n_p, nb = c.nb, ch = ks_chunk(l);
+        const int l = c.level, n = hp_.n, nl = hp_.nl(l), ne = nl + np_at(l), nb = c.nb, ch = ks_chunk(l);
         if (outm && nb > ch) throw std::runtime_error("relin_rescale: per-member outputs need one chunk");
         const size_t ms = (size_t)3 * nl * n;
         Ct o;
@@ -1759,13 +1924,13 @@ public:
             for (int m0 = 0; m0 < nb; m0 += ch) {
                 const int k = std::min(ch, nb - m0);
                 const u32* base = c.data + m0 * ms;
-                const KsFold fold{base, base + (size_t)nl * n, ms, d_gadget_};
+                const KsFold fold{base, base + (size_t)nl * n, ms, kb(l).gadget};
                 if (fused_ki_ok()) {
                     const int h = ne - hp_.nl(l - 1);
                     u32* ext = modup(base + (size_t)2 * nl * n, l, k, ms, nullptr, false, true);
                     u32* acc = tmp(2 * (size_t)ne * k);
                     u32* ys = tmp(2 * (size_t)h * k);
-                    const KiSrc src{ext, base + (size_t)2 * nl * n, ksk(0)};
+                    const KiSrc src{ext, base + (size_t)2 * nl * n, ksk_at(0, l)};
                     ki_core(acc, ys, l, hp_.nl(l - 1), k, &src, 1, ms, fold);
                     untmp(ext, (size_t)k * ext_rows(l));
                     moddown_rescale(acc, l, k, o.data + m0 * oms, nullptr, nullptr, ys);
@@ -1775,20 +1940,20 @@ public:
                 }
                 u32* ext = modup(base + (size_t)2 * nl * n, l, k, ms);
                 u32* acc = tmp(2 * (size_t)ne * k);
-                key_inner(acc, ext, base + (size_t)2 * nl * n, ksk(0), l, 0, k, ms, fold);
+                key_inner(acc, ext, base + (size_t)2 * nl * n, ksk_at(0, l), l, 0, k, ms, fold);
                 untmp(ext, (size_t)k * ext_rows(l));
                 moddown_rescale(acc, l, k, o.data + m0 * oms);
                 untmp(acc, 2 * (size_t)ne * k);
             }
         } else {
             const u32* d2 = c.data + (size_t)2 * nl * n;
-            const KsFold fold{c.data, c.data + (size_t)nl * n, ms, d_gadget_};
+            const KsFold fold{c.data, c.data + (size_t)nl * n, ms, kb(l).gadget};
             if (fused_ki_ok()) {
                 const int h = ne - hp_.nl(l - 1);
                 u32* ext = modup(d2, l, nb, ms, nullptr, false, true);
                 u32* acc = tmp(2 * (size_t)ne * nb);
                 u32* ys = tmp(2 * (size_t)h * nb);
-                const KiSrc src{ext, d2, ksk(0)};
+                const KiSrc src{ext, d2, ksk_at(0, l)};
                 ki_core(acc, ys, l, hp_.nl(l - 1), nb, &src, 1, ms, fold);
                 untmp(ext, (size_t)nb * ext_rows(l));
                 o = moddown_rescale(acc, l, nb, nullptr, outm, nullptr, ys);
@@ -1797,7 +1962,7 @@ public:
             } else {
                 u32* ext = modup(d2, l, nb, ms);
                 u32* acc = tmp(2 * (size_t)ne * nb);
-                key_inner(acc, ext, d2, ksk(0), l, 0, nb, ms, fold);
+                key_inner(acc, ext, d2, ksk_at(0, l), l, 0, nb, ms, fold);
                 untmp(ext, (size_t)nb * ext_rows(l));
                 o = moddown_rescale(acc, l, nb, nullptr, outm);
                 untmp(acc, 2 * (size_t)ne * nb);
@@ -1823,10 +1988,10 @@ public:
     // residues k_tensor_ptrs would have written, so the result is the same bit for bit, one launch
     // and 3 written + 3 re-read tensor rows per limb fewer (AESFHE_FUSED_TENSOR=0: tensor first)
     void relin_rescale_tensor(const TensorPtrs& tp, int l, int nb, u32* const* outm, const Affine* af = nullptr) {
-        const int n = hp_.n, nl = hp_.nl(l), ne = nl + hp_.n_p;
+        const int n = hp_.n, nl = hp_.nl(l), ne = nl + np_at(l);
         if (nb > ks_chunk(l) || nb > kMaxKsBatch) throw std::runtime_error("relin_rescale_tensor: more members than one chunk");
         TensorPtrs t1;  // a1, b1
-        KsFold f{nullptr, nullptr, 0, d_gadget_};
+        KsFold f{nullptr, nullptr, 0, kb(l).gadget};
         f.tnl = nl;
         for (int m = 0; m < nb; ++m) {
             t1.a[m] = tp.a[m] + (size_t)nl * n, t1.b[m] = tp.b[m] + (size_t)nl * n;
@@ -1837,7 +2002,7 @@ public:
             u32* ext = modup(nullptr, l, nb, 0, &t1, false, true);
             u32* acc = tmp(2 * (size_t)ne * nb);
             u32* ys = tmp(2 * (size_t)h * nb);
-            const KiSrc src{ext, nullptr, ksk(0)};
+            const KiSrc src{ext, nullptr, ksk_at(0, l)};
             ki_core(acc, ys, l, hp_.nl(l - 1), nb, &src, 1, 0, f);
             untmp(ext, (size_t)nb * ext_rows(l));
             moddown_rescale(acc, l, nb, nullptr, outm, af, ys);
@@ -1850,7 +2015,7 @@ public:
         }
         u32* ext = modup(nullptr, l, nb, 0, &t1);
         u32* acc = tmp(2 * (size_t)ne * nb);
-        key_inner(acc, ext, nullptr, ksk(0), l, 0, nb, 0, f);
+        key_inner(acc, ext, nullptr, ksk_at(0, l), l, 0, nb, 0, f);
         untmp(ext, (size_t)nb * ext_rows(l));
         Ct o = moddown_rescale(acc, l, nb, nullptr, outm, af);
         (void)o;
@@ -1876,12 +2041,13 @@ public:
     // ys_in: the dropped + P rows already through the INTT's row pass (ki_core, [m][2][h]): only its column pass runs here
     Ct moddown_rescale(const u32* acc, int l, int nb, u32* dst = nullptr, u32* const* outm = nullptr, const Affine* af = nullptr,
                        u32* ys_in = nullptr) {
-        const int n = hp_.n, nl = hp_.nl(l), r = hp_.nl(l - 1), k = nl - r, np = hp_.n_p, ne = nl + np;
+        const KsBasis& B = kb(l);
+        const int n = hp_.n, nl = hp_.nl(l), r = hp_.nl(l - 1), k = nl - r, np = B.np, ne = nl + np;
         const int npl = 2 * nb, h = k + np;
-        if (mdr_off_[l] == SIZE_MAX || npl > kMaxConvGroups) throw std::runtime_error("moddown_rescale: unsupported level or batch");
+        if (!B.mdr || npl > kMaxConvGroups) throw std::runtime_error("moddown_rescale: unsupported level or batch");
         const bool fz = fused_conv(false);
         if (fz && af && af->any()) throw std::runtime_error("moddown_rescale: the epilogue needs the separate conversion");
-        const size_t off = mdr_off_[l];
+        const u32* mdr = B.mdr;
         u32* ys = ys_in ? ys_in : tmp((size_t)npl * h);
         const bool bx = bx_ok() && h <= kBxMaxH;
         if (bx) {  // the dropped + P rows through the INTT's row pass only (k_bx_cols runs the rest)
@@ -1889,10 +2055,10 @@ public:
             cnt_[C_NTT_ROWS] += (size_t)npl * h;
         } else if (ys_in) {
             if (fz) throw std::runtime_error("moddown_rescale: a fused-core input needs the separate conversion");
-            launch_ntt_inv_cols(S(), T_, ys, npl * h, rows_dense(h), LimbMap{k, r, hp_.p_off()}, conv_pre_ ? d_mdr_ + off + 2 * (size_t)h * r : nullptr);
+            launch_ntt_inv_cols(S(), T_, ys, npl * h, rows_dense(h), LimbMap{k, r, hp_.p_off()}, conv_pre_ ? mdr + 2 * (size_t)h * r : nullptr);
             cnt_[C_NTT_ROWS] += (size_t)npl * h;
         } else {
-            intt(ys, acc, npl * h, RowMap{h, ne, h, r, 0}, LimbMap{k, r, hp_.p_off()}, fz || conv_pre_ ? d_mdr_ + off + 2 * (size_t)h * r : nullptr);
+            intt(ys, acc, npl * h, RowMap{h, ne, h, r, 0}, LimbMap{k, r, hp_.p_off()}, fz || conv_pre_ ? mdr + 2 * (size_t)h * r : nullptr);
         }
         u32* conv = tmp((size_t)npl * r);
         ConvBatch cb;
@@ -1902,9 +2068,9 @@ public:
             cb.h[p] = h, cb.d0[p] = r, cb.split[p] = k, cb.d1[p] = hp_.p_off(), cb.skip0[p] = 1 << 30;
             cb.src[p] = ys + (size_t)p * h * n;
             cb.dst[p] = conv + (size_t)p * r * n;
-            cb.tab[p] = d_mdr_ + off;                           // [h][r] pairs
-            cb.qhinv[p] = d_mdr_ + off + 2 * (size_t)h * r;     // [h] pairs
-            cb.negq[p] = d_mdr_ + off + 2 * (size_t)h * (r + 1);  // [r]
+            cb.tab[p] = mdr;                           // [h][r] pairs
+            cb.qhinv[p] = mdr + 2 * (size_t)h * r;     // [h] pairs
+            cb.negq[p] = mdr + 2 * (size_t)h * (r + 1);  // [r]
         }
         if (bx) launch_bx_cols(S(), T_, cb, r, qmap());
         else if (!fz) launch_base_convert(S(), T_, cb, r, qmap());
@@ -1914,7 +2080,7 @@ public:
         } else {
             o = alloc_ct(l - 1, npl, nb);
         }
-        const u32* qinv = d_mdr_ + off + 2 * (size_t)h * (r + 1) + r;
+        const u32* qinv = mdr + 2 * (size_t)h * (r + 1) + r;
         if (bx)
             launch_ntt_finish_rows(S(), T_, o.data, conv, acc, ne, qinv, nullptr, nullptr, npl, r, 0, outm, false, af ? af->dbl : 0u,
                                    af && af->any() ? af->cst : nullptr);
@@ -2420,7 +2586,7 @@ public:
             by_level[s.level].push_back(i);
         }
         for (auto& kv : by_level) {
-            const int l = kv.first, nl = hp_.nl(l), ne = nl + hp_.n_p, nd = (nl + hp_.alpha - 1) / hp_.alpha;
+            const int l = kv.first, nl = hp_.nl(l), ne = nl + np_at(l), nd = (nl + hp_.alpha - 1) / hp_.alpha;
             const auto& items = kv.second;
             const int max_src = std::max(1, kMaxConvGroups / nd);
             size_t pos = 0;
@@ -2468,13 +2634,13 @@ public:
                 for (int m = 0; m < nm; ++m) {
                     const int i = chunk[m];
                     const KsSrc& s = src_of.at(C[i]->data);
-                    ka.key[m] = ksk(G[i]);
+                    ka.key[m] = ksk_at(G[i], l);
                     ka.g[m] = G[i];
                     ka.src[m] = src_index(s);
                     am.src[m] = s.c0;
                     am.g[m] = G[i];
                 }
-                launch_key_inner_multi(S(), T_, acc, ext, c1s, ka, nm, ns, nd, ne, nl, hp_.alpha, hp_.n_ks + hp_.n_p, hp_.n_ks, extmap(nl),
+                launch_key_inner_multi(S(), T_, acc, ext, c1s, ka, nm, ns, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
                                        (size_t)ext_rows(l) * nn, d_ms, (size_t)2 * ne * nn);
                 untmp(ext, (size_t)ns * ext_rows(l));
                 if (c1buf) untmp(c1buf, (size_t)ns * nl);
@@ -2534,7 +2700,7 @@ public:
     }
     bool lazy_galois_ = std::getenv("AESFHE_LAZY_GALOIS") == nullptr || std::getenv("AESFHE_LAZY_GALOIS")[0] != '0';
     Ct galois_lazy(const Ct& c, u64 g) {
-        const int l = c.level, nl = hp_.nl(l), np = hp_.n_p, ne = nl + np, n = hp_.n, k = pm(c);
+        const int l = c.level, nl = hp_.nl(l), np = np_at(l), ne = nl + np, n = hp_.n, k = pm(c);
         if (g == conj_galois() && conj_rev_ && !fused_conv(true) && !fused_conv(false)) {
             // the conjugation (X -> X^(2N-1)) is the index reversal i -> N - 1 - i in this NTT order:
             // read reversed where the permuted copy was read -- the ModUp's inverse NTT, the own
@@ -2546,8 +2712,8 @@ public:
                 u32* ext = modup(c.data + (size_t)nl * n, l, nsrc, (size_t)nl * n, nullptr, true, true);
                 u32* acc = tmp(2 * (size_t)ne);
                 u32* ys = tmp(2 * (size_t)np);
-                const KiSrc src[2] = {{ext, c.data + (size_t)nl * n, ksk(g)},
-                                      {ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, nsrc == 2 ? ksk(tag_sq(g)) : nullptr}};
+                const KiSrc src[2] = {{ext, c.data + (size_t)nl * n, ksk_at(g, l)},
+                                      {ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, nsrc == 2 ? ksk_at(tag_sq(g), l) : nullptr}};
                 ki_core(acc, ys, l, nl, 1, src, nsrc, 0, fr);
                 untmp(ext, (size_t)nsrc * ext_rows(l));
                 Ct o = moddown(acc, l, c.data, nullptr, 1, 0, nullptr, nullptr, true, ys);
@@ -2561,9 +2727,9 @@ public:
             }
             u32* ext = modup(c.data + (size_t)nl * n, l, nsrc, (size_t)nl * n, nullptr, true);
             u32* acc = tmp(2 * (size_t)ne);
-            key_inner(acc, ext, c.data + (size_t)nl * n, ksk(g), l, 0, 1, 0, fr);
+            key_inner(acc, ext, c.data + (size_t)nl * n, ksk_at(g, l), l, 0, 1, 0, fr);
             if (nsrc == 2)
-                key_inner(acc, ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, ksk(tag_sq(g)), l, 0, 1, 0, fr, true);
+                key_inner(acc, ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, ksk_at(tag_sq(g), l), l, 0, 1, 0, fr, true);
             untmp(ext, (size_t)nsrc * ext_rows(l));
             Ct o = moddown(acc, l, c.data, nullptr, 1, 0, nullptr, nullptr, true);
             untmp(acc, 2 * (size_t)ne);
@@ -2579,9 +2745,9 @@ public:
         const int nsrc = k - 1;
         u32* ext = modup(perm + (size_t)nl * n, l, nsrc, (size_t)nl * n);
         u32* acc = tmp(2 * (size_t)ne);
-        key_inner(acc, ext, perm + (size_t)nl * n, ksk(g), l, 0);
+        key_inner(acc, ext, perm + (size_t)nl * n, ksk_at(g, l), l, 0);
         if (nsrc == 2)
-            key_inner(acc, ext + (size_t)ext_rows(l) * n, perm + (size_t)2 * nl * n, ksk(tag_sq(g)), l, 0, 1, 0, KsFold{}, true);
+            key_inner(acc, ext + (size_t)ext_rows(l) * n, perm + (size_t)2 * nl * n, ksk_at(tag_sq(g), l), l, 0, 1, 0, KsFold{}, true);
         untmp(ext, (size_t)nsrc * ext_rows(l));
         Ct o = moddown(acc, l, perm, nullptr);
         untmp(acc, 2 * (size_t)ne);
@@ -2607,14 +2773,14 @@ public:
         if (vis_npoly(c_in) != 2) throw std::runtime_error("rotation/conjugation expects a 2-polynomial ciphertext");
         Ct c = normalize(c_in);
         const int nl = hp_.nl(c.level), n = hp_.n;
-        const u32* key = ksk(g);
+        const u32* key = ksk_at(g, c.level);
         if (g == conj_galois() && conj_rev_ && c.nb == 1 && !fused_conv(true) && !fused_conv(false)) {
             // the conjugation as reversed reads (galois_lazy): no permuted copy
-            const int ne = nl + hp_.n_p;
+            const int ne = nl + np_at(c.level);
             KsFold fr{};
             fr.rev_d = 1;
             if (fused_ki_ok()) {
-                const int np = hp_.n_p;
+                const int np = np_at(c.level);
                 u32* ext = modup(c.data + (size_t)nl * n, c.level, 1, 0, nullptr, true, true);
                 u32* acc = tmp(2 * (size_t)ne);
                 u32* ys = tmp(2 * (size_t)np);
@@ -2663,7 +2829,7 @@ public:
             if (c.data != c_in.data) release(c);
             return out;
         }
-        const int l = c.level, nl = hp_.nl(l), ne = nl + hp_.n_p, n = hp_.n;
+        const int l = c.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n;
         const u32* c1 = c.data + (size_t)nl * n;
         u32* ext = modup(c1, l, 1, 0);
         for (size_t i = 0; i < steps.size(); ++i) {
@@ -2673,7 +2839,7 @@ public:
             }
             const u64 g = rot_galois(steps[i]);
             u32* acc = tmp(2 * (size_t)ne);
-            key_inner(acc, ext, c1, ksk(g), l, g);
+            key_inner(acc, ext, c1, ksk_at(g, l), l, g);
             u32* p0 = tmp(nl);
             launch_automorph(S(), T_, p0, c.data, g, nl);
             out[i] = moddown(acc, l, p0, nullptr);
@@ -3348,7 +3514,7 @@ public:
     Ct trace4(const Ct& x_in, int a) {
         if (vis_npoly(x_in) != 2) throw std::runtime_error("trace4: 2-polynomial ciphertext expected");
         Ct x = normalize(x_in);
-        const int l = x.level, nl = hp_.nl(l), ne = nl + hp_.n_p, n = hp_.n, nb = x.nb;
+        const int l = x.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n, nb = x.nb;
         const size_t qs = (size_t)2 * nl * n;
         const u32* c1 = x.data + (size_t)nl * n;
         u32* ext = modup(c1, l, nb, qs);
@@ -3357,9 +3523,9 @@ public:
         // automorphisms in another (bit for bit the separate launches' sums)
         KsSumArgs ka;
         ka.J = 3;
-        for (int j = 1; j <= 3; ++j) ka.g[j - 1] = rot_galois(-j * a), ka.key[j - 1] = ksk(ka.g[j - 1]);
+        for (int j = 1; j <= 3; ++j) ka.g[j - 1] = rot_galois(-j * a), ka.key[j - 1] = ksk_at(ka.g[j - 1], l);
         const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, hp_.n_ks + hp_.n_p, hp_.n_ks, extmap(nl),
+        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
                              (size_t)ext_rows(l) * n, qs, (size_t)2 * ne * n);
         untmp(ext, (size_t)nb * ext_rows(l));
         u32* c0s = tmp(2 * (size_t)nl * nb);  // member stride qs, first nl rows used (moddown's add0)
@@ -3382,17 +3548,17 @@ public:
     // than keyswitch(s2d) followed by trace4.  Same plaintext; the key-switch noise terms differ.
     bool s2d_trace_ = env_int("AESFHE_S2D_TRACE", 1) != 0;
     Ct s2d_trace4(const Ct& raised, int a) {
-        const int l = raised.level, nl = hp_.nl(l), ne = nl + hp_.n_p, n = hp_.n, nb = raised.nb;
+        const int l = raised.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n, nb = raised.nb;
         const size_t qs = (size_t)2 * nl * n;
         const u32* c1 = raised.data + (size_t)nl * n;
         u32* ext = modup(c1, l, nb, qs);
         u32* acc = tmp(2 * (size_t)ne * nb);
         KsSumArgs ka;
         ka.J = 4;
-        ka.g[0] = 1, ka.key[0] = ksk(tag_s2d());
-        for (int j = 1; j <= 3; ++j) ka.g[j] = rot_galois(-j * a), ka.key[j] = ksk(tag_s2d_rot(ka.g[j]));
+        ka.g[0] = 1, ka.key[0] = ksk_at(tag_s2d(), l);
+        for (int j = 1; j <= 3; ++j) ka.g[j] = rot_galois(-j * a), ka.key[j] = ksk_at(tag_s2d_rot(ka.g[j]), l);
         const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, hp_.n_ks + hp_.n_p, hp_.n_ks, extmap(nl),
+        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
                              (size_t)ext_rows(l) * n, qs, (size_t)2 * ne * n);
         untmp(ext, (size_t)nb * ext_rows(l));
         KsSumArgs kc;  // c0 + its three automorphisms
@@ -3601,6 +3767,9 @@ public:
     //   inner = ModDown(sum_b P_b u_b) + (sum_b P_b a_b, P_0 c1),  a_0 = c0,
     // then rescales and takes its giant rotation (a full key switch).
     Ct lin_group(const Ct& in, BootGroupDev& G) {
+        // the group's diagonals are encoded on the whole P block and its giant steps share Q*P sums:
+        // this path keeps the full special basis at every level
+        const FullP full_basis(*this);
         const LinGroup& g = *G.g;
         const int l = in.level, nl = hp_.nl(l), np = hp_.n_p, ne = nl + np, n = hp_.n;
         if (g.B > kMacMax) throw std::runtime_error("lin_group: more than 16 baby steps");
@@ -3630,10 +3799,10 @@ public:
                 if (!used) continue;
                 const u64 gal = rot_galois(-(int)((long)g.h * b));  // left rotation by h b
                 if (fused_baby) {
-                    bkey[b] = ksk(gal);
+                    bkey[b] = ksk_at(gal, l);
                 } else {
                     u[b] = tmp(2 * (size_t)ne * nb);
-                    key_inner(u[b], ext, c1, ksk(gal), l, gal, nb, qs);
+                    key_inner(u[b], ext, c1, ksk_at(gal, l), l, gal, nb, qs);
                 }
                 gals[b] = gal;  // c0's automorphism is read inside k_lin_mac
                 cnt_[C_ROT] += nb;
@@ -4426,7 +4595,7 @@ public:
         const size_t tms = (size_t)2 * nlt * n;
         const bool fuse_s2d = sv && s2d_trace_ && trace4_ && 4 * sv->n <= slot_count() && stop_after != 12;
         Ct u = fuse_s2d ? s2d_trace4(raised, sv->n)
-                        : keyswitch(raised.data + (size_t)nlt * n, top, ksk(tag_s2d()), raised.data, nullptr, nb, tms, tms);
+                        : keyswitch(raised.data + (size_t)nlt * n, top, ksk_at(tag_s2d(), top), raised.data, nullptr, nb, tms, tms);
         release(raised);
         if (stop_after == 12) return u;  // debug: back on the dense secret, before the sparse trace
         // 4b. sparse: the trace to the subring, x += rot(x, n 2^i) for 2^i < M / n (the overflow's
@@ -4622,7 +4791,7 @@ public:
         const int nl = hp_.nl(level);
         u32* d = tmp(nl);
         HIP_OK(hipMemcpyAsync(d, d_host, sizeof(u32) * nl * hp_.n, hipMemcpyHostToDevice, S()));
-        Ct o = keyswitch(d, level, ksk(g), nullptr, nullptr);
+        Ct o = keyswitch(d, level, ksk_at(g, level), nullptr, nullptr);
         export_dev(o.data, o.words, out);
         release(o);
         untmp(d, nl);
@@ -4647,7 +4816,7 @@ public:
         auto run = [&]() {
             if (op == 0) ntt(buf, buf, arg, rows_dense(nl), qmap());
             else if (op == 1) intt(buf, buf, arg, rows_dense(nl), qmap());
-            else if (op == 2) release(keyswitch(buf + (size_t)2 * nl * n, arg, ksk(0), buf, buf + (size_t)nl * n));
+            else if (op == 2) release(keyswitch(buf + (size_t)2 * nl * n, arg, ksk_at(0, arg), buf, buf + (size_t)nl * n));
             else if (op == 3) release(rescale(c));
             else release(mul(c, c, true));
         };
@@ -5254,6 +5423,16 @@ int aesfhe_lut_free(aesfhe_ctx* ctx, aesfhe_handle lut) {
 }
 int aesfhe_set_enc_nonce(aesfhe_ctx* ctx, uint64_t nonce) {
     API_BEGIN ctx->eng->set_enc_nonce(nonce);
+    API_END
+}
+int aesfhe_set_low_p(aesfhe_ctx* ctx, int on) {
+    API_BEGIN ctx->eng->set_low_p(on != 0);
+    API_END
+}
+int aesfhe_ks_special_primes(aesfhe_ctx* ctx, int level, int32_t* out) {
+    API_BEGIN
+    if (level < 0 || level > ctx->eng->hp().L) throw std::runtime_error("aesfhe_ks_special_primes: level out of range");
+    *out = ctx->eng->np_at(level);
     API_END
 }
 int aesfhe_set_lazy(aesfhe_ctx* ctx, int on) {

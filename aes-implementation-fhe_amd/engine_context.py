@@ -15,6 +15,7 @@ randomness, include/aesfhe.h aesfhe_set_enc_nonce; random unless pinned).
 from __future__ import annotations
 
 import hashlib
+import os
 import threading
 import weakref
 import time
@@ -49,6 +50,11 @@ class EngineContext:
                              device_id=device_id, log_n=log_n, dnum=dnum, seed=seed, lazy=lazy,
                              concurrent=concurrent, allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls, **kw)
         eng = self.engine
+        # the bootstrappable sets sized by boot_fresh_level carry alpha + 1 special primes for the top
+        # of the bootstrap, while the AES rounds key-switch at levels of fewer than alpha limbs: those
+        # run over nl + 1 special primes (AESFHE_LOW_P=0 keeps the full basis)
+        if signature == 1 and use_bootstrap and boot_fresh_level and os.environ.get("AESFHE_LOW_P", "1") != "0":
+            eng.set_low_p(True)
         # REF/engine_context.py:44-50
         self.secret_key = eng.create_secret_key()
         self.public_key = eng.create_public_key(self.secret_key)

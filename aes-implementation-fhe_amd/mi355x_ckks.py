@@ -48,6 +48,7 @@ EXPORTED = [
     "aesfhe_galois_multi", "aesfhe_debug_boot_stage_sparse", "aesfhe_debug_sparse_group", "aesfhe_debug_sparse_group_plain",
     "aesfhe_debug_mono_pack", "aesfhe_debug_mono_split", "aesfhe_alg_bytes", "aesfhe_stack", "aesfhe_unstack", "aesfhe_members",
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
+    "aesfhe_set_low_p", "aesfhe_ks_special_primes",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -140,6 +141,8 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_lut_free"] = [vp, _H]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
+    sig["aesfhe_set_low_p"] = [vp, c_int]
+    sig["aesfhe_ks_special_primes"] = [vp, c_int, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_launch_count"] = []
     sig["aesfhe_launch_census"] = [ctypes.c_char_p, ctypes.c_uint64, c_int]
     sig["aesfhe_alg_bytes"] = [_dp, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS"), c_int]
@@ -332,6 +335,7 @@ class Engine:
             enc_nonce = int(os.environ["AESFHE_ENC_NONCE"], 0)
         self.enc_nonce = (int.from_bytes(os.urandom(8), "little") if enc_nonce is None else int(enc_nonce)) & 0xFFFFFFFFFFFFFFFF
         self._ctx.check(L.aesfhe_set_enc_nonce(self._ctx.ptr, self.enc_nonce))
+        self.low_p = os.environ.get("AESFHE_LOW_P", "0") not in ("", "0")  # the engine reads the same variable
         self.fresh_level = max_level
         self.slot_count = int(L.aesfhe_slot_count(self._ctx.ptr))
         self.max_level = int(L.aesfhe_max_level(self._ctx.ptr))
@@ -423,6 +427,20 @@ class Engine:
         """Deferred relinearisation / rescale of products; False = eager."""
         self.lazy = bool(on)
         self._ctx.check(self._ctx.lib.aesfhe_set_lazy(self._ctx.ptr, int(self.lazy)))
+
+    def set_low_p(self, on: bool):
+        """Per-level special basis (aesfhe_set_low_p): key switches at levels of fewer
+        than alpha limbs run over nl + 1 special primes with that level's own keys.  Off in a raw
+        Engine (residues then match the C oracle's full basis); EngineContext turns it on for the
+        bootstrappable sets it builds with boot_fresh_level."""
+        self.low_p = bool(on)
+        self._ctx.check(self._ctx.lib.aesfhe_set_low_p(self._ctx.ptr, int(self.low_p)))
+
+    def ks_special_primes(self, level: int) -> int:
+        """special primes a key switch at `level` runs over under the current set_low_p setting"""
+        out = np.zeros(1, np.int32)
+        self._ctx.check(self._ctx.lib.aesfhe_ks_special_primes(self._ctx.ptr, int(level), out))
+        return int(out[0])
 
     # ------------------------------------------------------------------ internals
     @property

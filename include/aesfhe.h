@@ -52,6 +52,16 @@ int aesfhe_create_keyed(aesfhe_ctx** out, int log_n, int max_level, int dnum, in
  * Engine draws a random one per process (os.urandom) unless pinned.  No reference counterpart:
  * desilofhe.Engine.encrypt (REF/engine_context.py:56-57) samples internally. */
 int aesfhe_set_enc_nonce(aesfhe_ctx* ctx, uint64_t nonce);
+/* Per-level special basis.  on != 0: a key switch at a level of nl < alpha limbs
+ * (one digit) runs over the first nl + 1 special primes only, with that level's own switching keys
+ * (generated on first use from the context key, kept resident); levels of nl >= alpha limbs and the
+ * bootstrap's linear transforms keep all n_p special primes.  Decoded results are unchanged,
+ * ciphertext residues are not (different keys).  Default off (or the environment's AESFHE_LOW_P):
+ * every residue is then the full-basis engine's.  Set it before the first key switch it should
+ * cover; it may be changed between operations. */
+int aesfhe_set_low_p(aesfhe_ctx* ctx, int on);
+/* special primes a key switch at `level` runs over under the current setting */
+int aesfhe_ks_special_primes(aesfhe_ctx* ctx, int level, int32_t* out);
 /* limbs per level 0..max_level (a ciphertext at level l has npoly x limbs[l] x N words) */
 int aesfhe_level_limbs(aesfhe_ctx* ctx, int32_t* out);
 int aesfhe_destroy(aesfhe_ctx* ctx);
