@@ -34,3 +34,9 @@ class AddRoundKey:
             return self.xor4.apply_pair(ct_hi, key_hi, ct_lo, key_lo, out_level)
         return pair(self.xor4.ctx, lambda: self.xor4.apply(ct_hi, key_hi, out_level),
                     lambda: self.xor4.apply(ct_lo, key_lo, out_level))
+
+    def public(self, ct_hi, ct_lo, nib_hi, nib_lo, out_level=None) -> Tuple[Any, Any]:
+        """AddRoundKey with one PUBLIC operand (a counter block, an AES-CTR ciphertext): nib_hi / nib_lo are its
+        uint8 nibble slot arrays (StateEncoder.nibble_slots); the public bytes are never encrypted
+        (XOR4LUT.apply_public_pair: depth utils.PUBLIC_XOR_DEPTH)"""
+        return self.xor4.apply_public_pair(ct_hi, nib_hi, ct_lo, nib_lo, out_level)

@@ -148,6 +148,10 @@ struct Lut {
     std::vector<double> re, im;
     double c0_re = 0.0, c0_im = 0.0;
     std::map<std::string, std::pair<u32*, size_t>> cst;  // (output level, element levels) -> constants
+    // public-operand form (lut_eval_public): D[t][b] = sum_q C[rows[t], q] zeta16^(q b), [rows][16] complex double
+    std::pair<u32*, size_t> pub{nullptr, 0};
+    std::vector<int> pub_rows;  // rows with a non-zero coefficient
+    double pub_mag = 0.0;       // sum_t max_b |D[t][b]|
 };
 
 struct Pt {
@@ -305,6 +309,7 @@ public:
         auto il = luts_.find(h);
         if (il != luts_.end()) {
             for (auto& e : il->second.cst) give_back(e.second.first, e.second.second);
+            if (il->second.pub.first) give_back(il->second.pub.first, il->second.pub.second);
             luts_.erase(il);
             return;
         }
@@ -1595,6 +1600,183 @@ public:
             o = r;
         }
         return o;
+    }
+
+    // ------------------------------------------------------------------ public-operand LUT evaluation
+    // D[t][b] = sum_q C[rows[t], q] zeta16^(q b) of a bivariate LUT with n_b = 16 (zeta16 = e^{-2 pi i / 16},
+    // utils.ZetaEncoder): computed in fp64 and uploaded on the LUT's first public evaluation, kept with its
+    // other constants (free_handle releases it).  The upload waits for its copy once, as lut_consts does: the
+    // table serves every stream afterwards, and the evaluations themselves never synchronise.
+    void lut_public_table(Lut& L) {
+        if (L.pub.first) return;
+        if (L.n_b != kLutMax) throw std::runtime_error("lut_eval_public: a bivariate LUT with n_b = 16 (one column per Zeta16 power)");
+        std::vector<int> rows;
+        for (int p = 0; p < L.n_a; ++p)
+            for (int q = 0; q < L.n_b; ++q)
+                if (L.re[(size_t)p * L.n_b + q] != 0.0 || L.im[(size_t)p * L.n_b + q] != 0.0) {
+                    rows.push_back(p);
+                    break;
+                }
+        if (rows.empty()) throw std::runtime_error("lut_eval_public: all coefficients are zero");
+        double zr[16], zi[16];
+        for (int k = 0; k < 16; ++k) zr[k] = std::cos(2.0 * M_PI * k / 16.0), zi[k] = -std::sin(2.0 * M_PI * k / 16.0);
+        std::vector<double> h(rows.size() * 32);
+        double mag = 0.0;
+        for (size_t t = 0; t < rows.size(); ++t) {
+            double top = 0.0;
+            for (int b = 0; b < 16; ++b) {
+                double re = 0.0, im = 0.0;
+                for (int q = 0; q < 16; ++q) {
+                    const size_t c = (size_t)rows[t] * 16 + q;
+                    const int k = (q * b) & 15;
+                    re += L.re[c] * zr[k] - L.im[c] * zi[k];
+                    im += L.re[c] * zi[k] + L.im[c] * zr[k];
+                }
+                h[(t * 16 + b) * 2] = re, h[(t * 16 + b) * 2 + 1] = im;
+                top = std::max(top, std::hypot(re, im));
+            }
+            mag += top;
+        }
+        ensure_slot_pos();
+        const size_t words = (2 * h.size() + (size_t)hp_.n - 1) / hp_.n * hp_.n;
+        u32* d = alloc_words(words);
+        HIP_OK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, S()));
+        HIP_OK(hipStreamSynchronize(S()));  // cached for every stream; host vector dies here
+        L.pub = {d, words};
+        L.pub_rows = rows;
+        L.pub_mag = mag;
+    }
+    // the public nibbles checked and copied into this stream's staging buffers (host, then device: the caller's
+    // array is free again when the call returns)
+    const uint8_t* stage_nibbles(const uint8_t* nib, int n_slots) {
+        const int s = slot_count();
+        if (!nib || n_slots != s) throw std::runtime_error("lut_eval_public: one nibble per slot (n_slots must equal slot_count)");
+        std::vector<uint8_t>& h = h_pub_nib_[t_sidx];
+        h.resize(s);
+        for (int j = 0; j < s; ++j) {
+            if (nib[j] >= 16) throw std::runtime_error("lut_eval_public: nibble out of range (>= 16) at slot " + std::to_string(j));
+            h[j] = nib[j];
+        }
+        if (!d_pub_nib_[t_sidx]) d_pub_nib_[t_sidx] = (uint8_t*)dev_alloc(((size_t)s + 3) / 4);
+        HIP_OK(hipMemcpyAsync(d_pub_nib_[t_sidx], h.data(), (size_t)s, hipMemcpyHostToDevice, S()));
+        return d_pub_nib_[t_sidx];
+    }
+    // the per-slot coefficient plaintexts of one or two LUTs' used rows, encoded on the device at `scale` on nl
+    // limbs: k_public_slots -> inverse FFT -> untwist / round / reduce -> forward NTT.  Returns nch x nl rows
+    // (tmp; the caller untmps); the FFT scratch goes back to the pool here
+    u32* public_encode(const Lut& L1, const Lut* L2, const uint8_t* d_nib, double scale, int nl) {
+        const int n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0);
+        u32* wb = tmp((size_t)4 * nch);  // [nch][N] complex double: 4 rows per channel
+        u32* m = nullptr;
+        try {
+            m = tmp((size_t)nch * nl);
+            launch_public_slots(S(), T_, (double*)wb, (const double*)L1.pub.first, n1, L2 ? (const double*)L2->pub.first : nullptr, nch, d_nib,
+                                d_slot_pos_);
+            launch_fft2(S(), T_, (double*)wb, -1, nch);
+            launch_encode_untwist(S(), T_, m, (const double*)wb, scale, nl, nch);
+            ntt(m, nch * nl, nl, qmap());
+        } catch (...) {
+            untmp(wb, (size_t)4 * nch);
+            if (m) untmp(m, (size_t)nch * nl);
+            throw;
+        }
+        untmp(wb, (size_t)4 * nch);
+        return m;
+    }
+    // out_k = sum_p D_k,p[nib] (.) a[p] for lut1 (and lut2): the operands canonical and dropped exactly to their
+    // common lowest logical level l, the coefficient plaintexts encoded at ptscale[l], ONE k_lut_public_mac launch
+    // for both sums; each output owes its rescale as mul_pt_sum's (applied here when the raw scale has no headroom)
+    void lut_eval_public(aesfhe_handle h1, aesfhe_handle h2, const aesfhe_handle* A, const uint8_t* nib, int n_slots, Ct* o1, Ct* o2) {
+        Lut& L1 = lut(h1);
+        Lut* L2 = h2 ? &lut(h2) : nullptr;
+        if (!A) throw std::runtime_error("lut_eval_public: missing element handles");
+        if (L2 && (L2->n_a != L1.n_a)) throw std::runtime_error("lut_eval_public: both LUTs need the same n_a");
+        lut_public_table(L1);
+        if (L2) lut_public_table(*L2);
+        std::vector<int> rows = L1.pub_rows;
+        if (L2)
+            for (int p : L2->pub_rows)
+                if (std::find(rows.begin(), rows.end(), p) == rows.end()) rows.push_back(p);
+        const int n = (int)rows.size();
+        if (n > kMaxMembers) throw std::runtime_error("lut_eval_public: at most 8 used rows");
+        int l = 1 << 30;
+        for (int p : rows) {
+            if (!A[p]) throw std::runtime_error("lut_eval_public: missing element handle of a used row");
+            const Ct& c = ct(A[p]);
+            if (c.nb != 1) throw std::runtime_error("lut_eval_public: stacked operands are not supported (single ciphertexts only)");
+            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("lut_eval_public: nonzero 2-polynomial ciphertexts");
+            l = std::min(l, c.level - c.pend);
+        }
+        if (l < 1) throw std::runtime_error("not enough level for the public-operand LUT (level 0)");
+        const uint8_t* d_nib = stage_nibbles(nib, n_slots);
+        const int nl = hp_.nl(l), n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0);
+        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
+        u32* m = nullptr;
+        Ct out[2];
+        try {
+            PubMacArgs a;
+            for (int t = 0; t < n; ++t) {
+                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
+                const Ct& c = ct(A[rows[t]]);
+                Ct x = c;
+                if (pm(c) != 2 || c.pend || !c.ntt) {
+                    x = normalize(c, true);
+                    if (x.data != c.data) own.push_back(x);
+                }
+                if (x.level != l) {
+                    const u32* before = x.data;
+                    x = level_down(x, l);
+                    if (x.data != before && x.data != c.data) own.push_back(x);
+                }
+                a.a[t] = x.data;
+                auto chan = [&](const std::vector<int>& r, int base) {
+                    auto it = std::find(r.begin(), r.end(), rows[t]);
+                    return it == r.end() ? -1 : base + (int)(it - r.begin());
+                };
+                a.c1[t] = chan(L1.pub_rows, 0);
+                a.c2[t] = L2 ? chan(L2->pub_rows, n1) : -1;
+                cnt_[C_PTMUL]++;
+            }
+            m = public_encode(L1, L2, d_nib, hp_.ptscale[l], nl);
+            const int no = L2 ? 2 : 1;
+            for (int k = 0; k < no; ++k) res.push_back(out[k] = alloc_ct(l, 2));
+            launch_lut_public_mac(S(), T_, out[0].data, L2 ? out[1].data : nullptr, a, n, nch, m, nl, qmap());
+            untmp(m, (size_t)nch * nl), m = nullptr;
+            for (int k = 0; k < no; ++k) {
+                out[k].pend = 1;
+                out[k].lazy = true;
+                if (!headroom(l, 1, k ? L2->pub_mag : L1.pub_mag)) {
+                    Ct r = rescale(out[k]);
+                    own.push_back(out[k]);
+                    res[k] = out[k] = r;
+                }
+            }
+        } catch (...) {
+            if (m) untmp(m, (size_t)nch * nl);
+            for (const Ct& x : own) release(x);
+            for (const Ct& x : res) release(x);
+            throw;
+        }
+        for (const Ct& x : own) release(x);
+        cnt_[C_LUT]++;
+        *o1 = out[0];
+        if (o2 && L2) *o2 = out[1];
+    }
+    // tests: the encoded coefficient rows of one LUT (used rows x nl(level) x N, NTT form) and their scale
+    void debug_public_pt(aesfhe_handle h, const uint8_t* nib, int n_slots, int level, u32* out, double* scale) {
+        Lut& L = lut(h);
+        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_public_pt: level out of range (1..max level)");
+        if (!out || !scale) throw std::runtime_error("debug_public_pt: missing output buffers");
+        lut_public_table(L);
+        const uint8_t* d_nib = stage_nibbles(nib, n_slots);
+        const int nl = hp_.nl(level);
+        const size_t rows = L.pub_rows.size() * (size_t)nl;
+        u32* m = public_encode(L, nullptr, d_nib, hp_.ptscale[level], nl);
+        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
+        if (e == hipSuccess) e = hipStreamSynchronize(S());
+        untmp(m, rows);
+        HIP_OK(e);
+        *scale = hp_.ptscale[level];
     }
 
     // ------------------------------------------------------------------ key switching
@@ -5228,6 +5410,8 @@ private:
     int codec_flip_[kStreams] = {};  // which of the stream's two accumulators the next decode uses
     bool snap_encode_ = !(std::getenv("AESFHE_SNAP_ENCODE") && std::atoi(std::getenv("AESFHE_SNAP_ENCODE")) == 0);
     int* d_nib_[kStreams] = {};
+    uint8_t* d_pub_nib_[kStreams] = {};        // lut_eval_public: the public nibbles, one byte per slot
+    std::vector<uint8_t> h_pub_nib_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;
@@ -5416,6 +5600,20 @@ int aesfhe_lut_create(aesfhe_ctx* ctx, int n_a, int n_b, const double* re, const
 }
 int aesfhe_lut_eval(aesfhe_ctx* ctx, aesfhe_handle lut, const aesfhe_handle* a, const aesfhe_handle* b, aesfhe_handle* out) {
     CT_OP(e.lut_eval(lut, a, b))
+}
+int aesfhe_lut_eval_public(aesfhe_ctx* ctx, aesfhe_handle lut1, aesfhe_handle lut2, const aesfhe_handle* a, const uint8_t* nib, int n_slots,
+                           aesfhe_handle* out1, aesfhe_handle* out2) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out1 || (lut2 && !out2)) throw std::runtime_error("lut_eval_public: missing output handles");
+    Ct o1, o2;
+    e.lut_eval_public(lut1, lut2, a, nib, n_slots, &o1, &o2);
+    *out1 = e.put_ct(o1);
+    if (lut2) *out2 = e.put_ct(o2);
+    API_END
+}
+int aesfhe_debug_public_pt(aesfhe_ctx* ctx, aesfhe_handle lut, const uint8_t* nib, int n_slots, int level, uint32_t* out, double* scale) {
+    API_BEGIN ctx->eng->debug_public_pt(lut, nib, n_slots, level, out, scale);
+    API_END
 }
 int aesfhe_lut_free(aesfhe_ctx* ctx, aesfhe_handle lut) {
     API_BEGIN ctx->eng->free_lut(lut);

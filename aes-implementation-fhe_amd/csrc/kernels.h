@@ -564,3 +564,23 @@ struct LutChunk {
 void launch_lut_univariate(hipStream_t st, const DevTables& T, u32* out, const u32* acc, const LutChunk& ch, int n, const u32* cst,
                            int npoly, int nl, int members = 1, const LimbConsts* cadd = nullptr);
 
+
+// --- public-operand LUT evaluation -------------------------------------
+// The second operand of a bivariate LUT known in clear, one Zeta16 nibble per slot: the LUT is then
+// sum_p D_p[nib_j] a_p with per-slot PLAINTEXT coefficients D_p[b] = sum_q C[p,q] zeta16^(q b).
+// launch_public_slots writes them as the FFT codec's input (the layout launch_snap_slots makes for
+// launch_fft2(w, -1, nch)): w[c][slot_pos[j]] = tab_c[nib[j]], w[c][N - 1 - slot_pos[j]] = its
+// conjugate, channel c < n1 reading row c of tab1, the others row c - n1 of tab2 (rows of 16 complex
+// doubles in device memory); launch_fft2 and launch_encode_untwist then encode all channels at once.
+void launch_public_slots(hipStream_t st, const DevTables& T, double* w, const double* tab1, int n1, const double* tab2, int nch,
+                         const uint8_t* nib, const u32* slot_pos);
+// out1 = sum_{t < n} a[t] (.) pt[c1[t]], out2 = sum_t a[t] (.) pt[c2[t]] (2 polys of nl limbs; a[t] 2 polys of
+// nl limbs; pt: channels of nl limbs, NTT form; a channel index < 0: no term; out2 may be null) in ONE
+// launch -- every ciphertext word read once for both sums, 64-bit sums of the 60-bit products, n <= kMaxMembers
+struct PubMacArgs {
+    const u32* a[kMaxMembers] = {};
+    int c1[kMaxMembers] = {};
+    int c2[kMaxMembers] = {};
+};
+void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* out2, const PubMacArgs& a, int n, int nch, const u32* pt,
+                           int nl, LimbMap map);

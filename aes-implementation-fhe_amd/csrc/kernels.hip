@@ -119,6 +119,22 @@ __global__ void k_mul_poly_sum(u32* out, PtSumArgs a, int n, int nl, LimbMap map
     for (int i = 0; i < n; ++i) acc += (u64)a.in[i][idx] * a.pt[i][pidx];
     out[idx] = reduce64(acc, P.q, P.mu, P.r32);
 }
+// out1 = sum_t a_t (.) pt[c1_t], out2 = sum_t a_t (.) pt[c2_t] over n <= kMaxMembers ciphertexts and the channels of
+// one encoded plaintext buffer (the public-operand LUT's S1 and S2, launch_lut_public_mac): every ciphertext word
+// read once for both sums, 64-bit sums of the 60-bit products (8 x 2^60 fits), one reduction each
+__global__ void k_lut_public_mac(u32* out1, u32* out2, PubMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc,
+                                 int logn) {
+    EW_PROLOGUE
+    const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
+    u64 acc1 = 0, acc2 = 0;
+    for (int t = 0; t < n; ++t) {
+        const u64 v = a.a[t][idx];
+        if (a.c1[t] >= 0) acc1 += v * pt[(size_t)a.c1[t] * chan + pidx];
+        if (a.c2[t] >= 0) acc2 += v * pt[(size_t)a.c2[t] * chan + pidx];
+    }
+    out1[idx] = reduce64(acc1, P.q, P.mu, P.r32);
+    if (out2) out2[idx] = reduce64(acc2, P.q, P.mu, P.r32);
+}
 __global__ void k_tensor(u32* out, const u32* a, const u32* b, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     // row = m * nl + limb: ciphertext m of a stacked batch ([m][2][nl] in, [m][3][nl] out)
     const int row = blockIdx.y;
@@ -1317,6 +1333,23 @@ __global__ void __launch_bounds__(kBlock) k_encode_untwist(u32* out, const doubl
     }
 }
 
+// the public operand of a LUT as the codec's FFT input (launch_public_slots): slot j of channel c takes
+// row c's table entry of the slot's nibble, written at the slot's position and, conjugated, at its mirror --
+// k_snap_slots' output order.  One byte per lane, consecutive lanes consecutive bytes; the 16-entry rows sit in L1/L2
+__global__ void __launch_bounds__(kBlock) k_public_slots(double2* w, const double2* tab1, int n1, const double2* tab2, const uint8_t* nib,
+                                                         const u32* slot_pos, int logn) {
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
+    const int n = 1 << logn;
+    if (j >= n / 2) return;
+    const double2* row = c < n1 ? tab1 + 16 * c : tab2 + 16 * (c - n1);
+    const double2 v = row[nib[j] & 15];
+    const u32 t = slot_pos[j];
+    double2* wc = w + ((size_t)c << logn);
+    wc[t] = v;
+    wc[n - 1 - t] = make_double2(v.x, -v.y);
+}
+
 // ------------------------------------------------------------------------------------
 // fused LUT evaluation: one launch per LUT instead of a tensor + constant + add per term
 // ------------------------------------------------------------------------------------
@@ -2085,4 +2118,19 @@ void launch_lut_univariate(hipStream_t st, const DevTables& T, u32* out, const u
                 dim3((1u << T.logn) / kBlock, nl, members), dim3(kBlock), 0, st, out, acc, ch, n, cst, npoly, nl, T.pc, T.logn,
                 cadd ? *cadd : kNoC, cadd ? 1 : 0);
 }
-
+void launch_public_slots(hipStream_t st, const DevTables& T, double* w, const double* tab1, int n1, const double* tab2, int nch,
+                         const uint8_t* nib, const u32* slot_pos) {
+    if (nch < 1 || nch > kLutMax || n1 < 0 || n1 > nch || (n1 < nch && !tab2)) throw std::runtime_error("launch_public_slots: 1..16 channels");
+    const double s = (double)(1u << (T.logn - 1));
+    const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
+    prof_launch(KID_ELEMENTWISE, nch * (1.0 * s + 4.0 * s + 32.0 * s), k_public_slots, dim3(gx, nch), dim3(kBlock), 0, st, (double2*)w,
+                (const double2*)tab1, n1, (const double2*)tab2, nib, slot_pos, T.logn);
+}
+void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* out2, const PubMacArgs& a, int n, int nch, const u32* pt,
+                           int nl, LimbMap map) {
+    if (n < 1 || n > kMaxMembers) throw std::runtime_error("launch_lut_public_mac: 1..8 ciphertexts");
+    for (int t = 0; t < n; ++t)
+        if (!a.a[t] || a.c1[t] >= nch || a.c2[t] >= nch) throw std::runtime_error("launch_lut_public_mac: bad operand");
+    prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + (out2 ? 2 : 1)) + (double)nch * nl), k_lut_public_mac, ew_grid(T.logn, 2 * nl),
+                dim3(kBlock), 0, st, out1, out2, a, n, pt, nl, map, T.pc, T.logn);
+}

@@ -1,0 +1,37 @@
+"""Counter mode over a 16-byte block function: plain byte helpers, no engine.
+
+The block function is whatever the caller passes -- for this project the cipher AESPipeline.encrypt
+computes (oracle/aes_plain.ref_encrypt: the reference's MixColumns mixes along rows),
+which is NOT FIPS-197, so the NIST SP 800-38A vectors do not apply.  Nothing here looks inside a block:
+a counter block is 16 bytes handed to the block function as they are, and the keystream is XORed byte
+for byte, so another byte order inside the block function changes nothing in this module.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def counter_blocks(nonce12, counter0: int, n: int) -> np.ndarray:
+    """(n, 16) uint8: block i = nonce12 || be32((counter0 + i) mod 2^32)"""
+    nonce = np.frombuffer(bytes(nonce12), dtype=np.uint8) if isinstance(nonce12, (bytes, bytearray)) else np.asarray(nonce12, dtype=np.uint8)
+    if nonce.shape != (12,):
+        raise ValueError("the nonce is 12 bytes")
+    if n < 0 or not 0 <= int(counter0) < 1 << 32:
+        raise ValueError("counter0 must lie in [0, 2^32) and n be >= 0")
+    ctr = (int(counter0) + np.arange(n, dtype=np.uint64)) % np.uint64(1 << 32)
+    out = np.empty((n, 16), dtype=np.uint8)
+    out[:, :12] = nonce
+    for k in range(4):
+        out[:, 12 + k] = (ctr >> np.uint64(8 * (3 - k))) & np.uint64(0xFF)
+    return out
+
+
+def ctr_xor(block_fn, data, nonce12, counter0: int) -> np.ndarray:
+    """data (n, 16) XOR the keystream block_fn(counter block i): encryption and decryption alike (the
+    byte model of AESPipeline.transcipher's input and of its tests)"""
+    data = np.asarray(data, dtype=np.uint8)
+    if data.ndim != 2 or data.shape[1] != 16:
+        raise ValueError("data: an (n, 16) uint8 array of blocks")
+    ks = np.stack([np.asarray(block_fn(b), dtype=np.uint8) for b in counter_blocks(nonce12, counter0, data.shape[0])]) \
+        if data.shape[0] else np.zeros((0, 16), np.uint8)
+    return data ^ ks

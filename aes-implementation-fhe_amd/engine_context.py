@@ -387,3 +387,10 @@ class EngineContext:
     def lut_eval(self, lut, a, b=None):
         """sum C[p,q] a[p] b[q] (or c0 + sum C[k] a[k]) in one fused kernel."""
         return self.engine.lut_eval(lut, a, b)
+
+    def lut_eval_public(self, lut1, lut2, a, nibbles):
+        """(S1, S2 | None): bivariate LUT(s) whose second operand is PUBLIC, one Zeta16 nibble per slot
+        (`nibbles`: contiguous uint8, slot_count entries) -- one engine call, the per-slot coefficient
+        plaintexts encoded on the device (Engine.lut_eval_public).  Modules test for it
+        with getattr(ctx, "lut_eval_public", None)."""
+        return self.engine.lut_eval_public(lut1, lut2, a, nibbles)

@@ -48,7 +48,7 @@ EXPORTED = [
     "aesfhe_galois_multi", "aesfhe_debug_boot_stage_sparse", "aesfhe_debug_sparse_group", "aesfhe_debug_sparse_group_plain",
     "aesfhe_debug_mono_pack", "aesfhe_debug_mono_split", "aesfhe_alg_bytes", "aesfhe_stack", "aesfhe_unstack", "aesfhe_members",
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
-    "aesfhe_set_low_p", "aesfhe_ks_special_primes",
+    "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -139,6 +139,9 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_lut_create"] = [vp, c_int, c_int, _dp, _dp, c_dbl, c_dbl, _Hp]
     sig["aesfhe_lut_eval"] = [vp, _H, _Hp, _Hp, _Hp]
     sig["aesfhe_lut_free"] = [vp, _H]
+    _bp = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
+    sig["aesfhe_lut_eval_public"] = [vp, _H, _H, _Hp, _bp, c_int, _Hp, _Hp]
+    sig["aesfhe_debug_public_pt"] = [vp, _H, _bp, c_int, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -251,7 +254,7 @@ class Plaintext(_Handle):
 class LookupTable(_Handle):
     """Coefficient set of a fused LUT evaluation (aesfhe_lut_create)."""
 
-    __slots__ = ("n_a", "n_b")
+    __slots__ = ("n_a", "n_b", "used_rows")
 
 
 class _Key:
@@ -979,6 +982,7 @@ class Engine:
                                                     c0.real, c0.imag, ctypes.byref(h)))
         t = LookupTable(self._ctx, h.value)
         t.n_a, t.n_b = c2.shape[0], (c2.shape[1] if c.ndim == 2 else 1)
+        t.used_rows = int(np.count_nonzero(np.any(c2 != 0, axis=1)))  # rows the public-operand form encodes
         return t
 
     def lut_eval(self, lut: LookupTable, a, b=None) -> Ciphertext:
@@ -996,6 +1000,48 @@ class Engine:
         ha = handles(a, lut.n_a)
         hb = handles(b, lut.n_b) if lut.n_b > 1 else None
         return self._new(self._lib.aesfhe_lut_eval, lut.handle, ha, hb)
+
+    @staticmethod
+    def _nibble_array(nibbles) -> np.ndarray:
+        nib = np.asarray(nibbles)
+        if nib.dtype != np.uint8 or nib.ndim != 1 or not nib.flags["C_CONTIGUOUS"]:
+            raise TypeError("nibbles: a contiguous one-dimensional uint8 array of slot_count entries")
+        return nib
+
+    def lut_eval_public(self, lut1: LookupTable, lut2: Optional[LookupTable], a, nibbles):
+        """(ct1, ct2 | None): the bivariate LUT(s) with a PUBLIC second operand (aesfhe_lut_eval_public),
+        out_k = sum_p (sum_q C_k[p,q] zeta^(q nibbles[j])) a[p] at slot j -- lut2 (None = none) shares the
+        element reads with lut1 (a conjugate-split LUT's S1 and S2).  `a` as in lut_eval; `nibbles`: a
+        contiguous uint8 array of slot_count entries < 16.  Raises RuntimeError with "level" in the message
+        when the elements sit at level 0, with "nibble" for an entry >= 16."""
+        nib = self._nibble_array(nibbles)
+        self._ensure_keys()
+        ha = (ctypes.c_uint64 * lut1.n_a)()
+        for k, ct in (a.items() if isinstance(a, dict) else enumerate(a)):
+            if ct is not None and 0 <= k < lut1.n_a:
+                ha[k] = ct.handle
+        o1, o2 = ctypes.c_uint64(), ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_lut_eval_public(self._ctx.ptr, lut1.handle, lut2.handle if lut2 is not None else 0, ha, nib,
+                                                         int(nib.size), ctypes.byref(o1), ctypes.byref(o2)))
+        return Ciphertext(self._ctx, o1.value), (Ciphertext(self._ctx, o2.value) if lut2 is not None else None)
+
+    def debug_public_pt(self, lut: LookupTable, nibbles, level: int):
+        """tests: (rows, scale) -- the coefficient plaintexts lut_eval_public multiplies by at `level`, one
+        per used row of `lut` in row order as (rows, nl(level), N) uint32 in NTT form, and their scale"""
+        nib = self._nibble_array(nibbles)
+        self._ensure_keys()
+        c = self._lut_used_rows(lut)
+        out = np.zeros((c, self.nl(level), self.n), np.uint32)
+        scale = ctypes.c_double(0.0)
+        self._ctx.check(self._lib.aesfhe_debug_public_pt(self._ctx.ptr, lut.handle, nib, int(nib.size), int(level), out, ctypes.byref(scale)))
+        return out, scale.value
+
+    @staticmethod
+    def _lut_used_rows(lut: LookupTable) -> int:
+        rows = getattr(lut, "used_rows", None)
+        if rows is None:
+            raise ValueError("debug_public_pt needs a LookupTable made by lut_create")
+        return rows
 
     def lut_free(self, lut: LookupTable):
         """release a LUT's device coefficient set now (otherwise: when the handle is collected)"""

@@ -433,6 +433,11 @@ class AESPipeline:
         self._log_pair(debug, "enc.input", *ct)
         rk = self._prepare_round_keys(round_keys)
         ct = self.ark(*ct, *rk[0], out_level=self._floor())
+        return self._encrypt_tail(ct, rk, round_keys, debug)
+
+    def _encrypt_tail(self, ct, rk, round_keys, debug):
+        """encrypt after round 0's AddRoundKey: its renorm, rounds 1..9, the final round (shared by encrypt
+        and encrypt_public, whose round 0 differs)"""
         self._log_pair(debug, "enc.r0.ark", *ct)
         ct = self._renorm_pair(*ct, level=self.need_sub)
         self._log_pair(debug, "enc.r0.renorm", *ct)
@@ -463,6 +468,43 @@ class AESPipeline:
         ct = self._renorm_pair(*ct)
         self._log_pair(debug, "enc.output", *ct)
         return tag_layout(self.layout, *ct)
+
+    # ---------------------------------------------------------------- public state / counter mode
+    def _no_pairs(self, what: str) -> None:
+        if self.pairs > 1:
+            raise ValueError(f"{what}: multi-pair batches (pairs > 1) take no public operands")
+
+    def encrypt_public(self, state: np.ndarray, round_keys: List[np.ndarray], debug: Dict[str, Any] | None = None):
+        """encrypt of a PUBLIC state (a counter block): round 0 XORs the encrypted round key 0 with the
+        state's nibbles in clear (AddRoundKey.public; the state is never encrypted), everything after it is
+        encrypt's own path.  Same bytes and the same layout-tagged pair as encrypt(state, round_keys); the
+        debug stages keep encrypt's names (no "enc.input": there is no input ciphertext)."""
+        self._no_pairs("encrypt_public")
+        if debug is not None:
+            debug.clear()
+        rk = self._prepare_round_keys(round_keys)
+        ct = self.ark.public(*rk[0], *self.encoder.nibble_slots(state), out_level=self._floor())
+        return self._encrypt_tail(ct, rk, round_keys, debug)
+
+    def ctr_keystream(self, nonce12, counter0: int, round_keys: List[np.ndarray]):
+        """the encrypted keystream blocks of counters counter0 .. counter0 + states - 1 (mod 2^32) under the
+        encrypted key: encrypt_public of ctr_mode.counter_blocks, one block per state"""
+        from ctr_mode import counter_blocks
+        self._no_pairs("ctr_keystream")
+        blocks = counter_blocks(nonce12, counter0, self.states)
+        return self.encrypt_public(blocks[0] if self.states == 1 else blocks, round_keys)
+
+    def transcipher(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray]):
+        """AES-CTR transciphering: aes_ct ((states, 16), or (16,) for one state) holds the client's
+        m ^ keystream under this pipeline's cipher in counter mode (ctr_mode.ctr_xor); returns a clean
+        layout-tagged pair that encoder.decode reads as m, at the level encrypt's output has.  The keystream
+        is evaluated under the encrypted key and XORed with the public ciphertext bytes (AddRoundKey.public),
+        then renormalised by the pipeline's own renorm (secret-key, or bootstrap + snap with true_fhe)."""
+        self._no_pairs("transcipher")
+        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
+        ks = self.ctr_keystream(nonce12, counter0, round_keys)
+        ct = self.ark.public(*ks, *nib, out_level=self._floor())
+        return tag_layout(self.layout, *self._renorm_pair(*ct))
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray], debug: Dict[str, Any] | None = None):

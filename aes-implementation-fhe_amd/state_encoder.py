@@ -144,6 +144,22 @@ class StateEncoder:
         grid[:, :nibbles.shape[0]] = ZetaEncoder.to_zeta(nibbles.astype(np.uint8).T, 16)
         return self.layout.tile(grid.reshape(-1))
 
+    def nibble_slots(self, state: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(hi, lo): the uint8 nibble of every slot for a PUBLIC byte state in this encoder's layout -- what
+        _pack encodes, before the Zeta16 map: to_zeta(nibble_slots(s)[k]) equals the packed slot vector slot
+        for slot (slots that hold no state carry nibble 0 = the 1 + 0j _pack fills them with).  The public
+        operand of AddRoundKey.public / Engine.lut_eval_public."""
+        if self.pairs > 1:
+            raise ValueError("nibble_slots: public operands of multi-pair batches (pairs > 1) are not supported")
+        st = self._as_batch(state)
+
+        def slots(nib):
+            grid = np.zeros((16, self.stride), dtype=np.uint8)
+            grid[:, :nib.shape[0]] = nib.T
+            return np.ascontiguousarray(self.layout.tile(grid.reshape(-1)))
+
+        return slots(st >> 4), slots(st & 0x0F)
+
     def _take(self, slots: np.ndarray) -> np.ndarray:
         """slot vector -> (B, 16) state slots"""
         return slots[:16 * self.stride].reshape(16, self.stride)[:, :self.states].T

@@ -32,6 +32,7 @@ class ZetaEncoder:
 # fused LUT sums (the per-term loops take over: 45.5 rounds/s).  AESFHE_RENORM_FLOOR overrides (A/B runs)
 RENORM_FLOOR = int(os.environ.get("AESFHE_RENORM_FLOOR", "1"))
 LUT2_DEPTH = 5       # bivariate nibble LUT (XOR4, GF multipliers): basis 3 + product + coefficient
+PUBLIC_XOR_DEPTH = 4  # XOR4 with a public operand (xor4_lut.apply_public): powers up to x^7 3 + plaintext product 1
 SUBBYTES_DEPTH = 13  # lift, b = hi * L(lo), baby/giant steps (sub_bytes_lut.py)
 SHIFTROWS_DEPTH = 1  # masked rotations (shift_rows.py)
 # the level each renorm re-encrypts at = what the step after it needs (engine renorm `level`)

@@ -18,7 +18,9 @@ import os
 from typing import Any, Dict
 
 import numpy as np
-from utils import LUT2_DEPTH, ConjSum, can_fork, conj_many, drop_to, fused_lut, mul_many, pair
+from collections import namedtuple
+
+from utils import LUT2_DEPTH, PUBLIC_XOR_DEPTH, ConjSum, ZetaEncoder, can_fork, conj_many, drop_to, fused_lut, mul_many, pair
 
 
 def basis16(ctx, ct, *, retry_intt: bool = True) -> Dict[int, Any]:
@@ -218,6 +220,26 @@ def split_lut2(ctx, split: SplitLUT2, key, a, b, keep_b=None, defer_conj: bool =
     return split.eval(ctx, key, A, B, defer_conj)
 
 
+# ---------------------------------------------------------------- public second operand
+PublicTables = namedtuple("PublicTables", "D d1 d2 c1 c2 need")
+
+
+def public_tables(coeffs, tol: float = 1e-12) -> PublicTables:
+    """The bivariate LUT sum_{p,q} C[p,q] A^p B^q with B KNOWN per slot (a Zeta16 codeword zeta^b): a
+    univariate sum with per-slot plaintext coefficients,
+        LUT(a, b) = sum_p D[p, b] A^p,              D[p, b] = sum_q C[p,q] zeta^(q b)      (16 x 16, direct form)
+                  = S1 + conj(S2),  S1 = sum_{p <= 8} d1[p, b] a^p,  S2 = sum_{p' < 8} d2[p', b] a^p'
+    with d1 / d2 the same sums over SplitLUT2's c1 / c2 (the clear value of basis element q is zeta^(q b) for
+    every q, the mirrors included: conj(x^(16-q)) = x^q on codewords).  c2 is returned padded to c1's nine
+    rows (the engine evaluates both with one element array); need: the powers of a the split form uses."""
+    sp = SplitLUT2(np.asarray(coeffs, np.complex128), tol)
+    C = np.where(np.abs(coeffs) > tol, np.asarray(coeffs, np.complex128), 0)
+    Z = ZetaEncoder.to_zeta(np.outer(np.arange(16), np.arange(16)), 16)  # Z[q, b] = zeta^(q b)
+    c2 = np.zeros_like(sp.c1)
+    c2[:8] = sp.c2
+    return PublicTables(C @ Z, sp.c1 @ Z, c2 @ Z, sp.c1, c2, frozenset(sp.need_a))
+
+
 class XOR4LUT:
     def __init__(self, ctx, coeffs: np.ndarray):
         self.ctx = ctx
@@ -286,5 +308,97 @@ class XOR4LUT:
                 if out is not None:
                     return out
         return pair(ctx, lambda: self.apply(a0, b0, out_level), lambda: self.apply(a1, b1, out_level))
+
+    # ------------------------------------------------------------ public second operand
+    def _public(self) -> PublicTables:
+        if not hasattr(self, "_pub"):
+            self._pub = public_tables(self.coeffs)
+        return self._pub
+
+    def _public_engine(self, A, nibbles):
+        """S1 and S2 from ONE engine call on the powers A of a (Engine.lut_eval_public), summed as S1 + conj(S2)
+        by the caller; None: the context has no such op, or the powers sit too low for it (level)"""
+        ctx = self.ctx
+        ev = getattr(ctx, "lut_eval_public", None)
+        if ev is None or not getattr(ctx, "fused_luts", False):
+            return None
+        T = self._public()
+        try:
+            return ev(ctx.lut(("xor4pub", 1), T.c1, owner=self), ctx.lut(("xor4pub", 2), T.c2, owner=self), A, nibbles)
+        except RuntimeError as e:
+            if "level" in str(e):
+                return None
+            raise
+
+    def _public_loop(self, B, nibbles):
+        """the reference's product loop (REF/xor4_lut.py:63-74) with plaintext coefficients: sum over the
+        std basis B of a of B[p] times the encoded per-slot vector D[p, nibbles] -- existing calls only"""
+        ctx, D = self.ctx, self._public().D
+        acc = None
+        for p in sorted(B):
+            t = ctx.multiply(B[p], ctx.encode(D[p, nibbles]))
+            acc = t if acc is None else ctx.add(acc, t)
+        return acc
+
+    def _public_rows(self):
+        return {p for p in range(16) if np.any(self._public().D[p])}
+
+    @staticmethod
+    def _check_nibbles(nibbles, sc):
+        nib = np.ascontiguousarray(nibbles, dtype=np.uint8)
+        if nib.shape != (sc,):
+            raise ValueError(f"public nibbles: one uint8 per slot ({sc}), got shape {nib.shape}")
+        if nib.size and int(nib.max()) >= 16:
+            raise ValueError("public nibbles must be < 16")
+        return nib
+
+    def apply_public(self, a_ct, nibbles, out_level=None, defer_conj: bool = False):
+        """XOR4(a, b) with b PUBLIC: `nibbles` holds b's nibble of every slot (uint8, slot_count entries;
+        StateEncoder.nibble_slots).  Only a's odd powers up to 7 are formed (depth 3) and multiplied by the
+        per-slot plaintext coefficients (public_tables; depth 1): utils.PUBLIC_XOR_DEPTH = 4 levels, no
+        encryption of b, no second basis.  out_level / defer_conj as apply."""
+        ctx = self.ctx
+        nib = self._check_nibbles(nibbles, self.sc)
+        if out_level is not None:
+            a_ct = drop_to(ctx, a_ct, out_level + PUBLIC_XOR_DEPTH)
+        if getattr(ctx, "lut_eval_public", None) is not None and getattr(ctx, "fused_luts", False):
+            try:
+                A = powers(ctx, a_ct, self._public().need)
+            except RuntimeError as e:
+                if "level" not in str(e):
+                    raise
+            else:
+                out = self._public_engine(A, nib)
+                if out is not None:
+                    s1, s2 = out
+                    return ConjSum(s1, s2) if defer_conj else ctx.add(s1, ctx.conjugate(s2))
+        return self._public_loop(std_basis(ctx, a_ct, self._public_rows()), nib)
+
+    def apply_public_pair(self, a0, n0, a1, n1, out_level=None):
+        """(XOR4(a0, n0), XOR4(a1, n1)) with public n0 / n1 -- the hi / lo halves of an AddRoundKey with a
+        public operand: the two power chains share mul_many batches (joint_bases) and the two conjugations
+        one conj_many, as apply_pair does for the encrypted-operand form"""
+        ctx = self.ctx
+        n0, n1 = self._check_nibbles(n0, self.sc), self._check_nibbles(n1, self.sc)
+        if not batched(ctx):
+            return pair(ctx, lambda: self.apply_public(a0, n0, out_level), lambda: self.apply_public(a1, n1, out_level))
+        if out_level is not None:
+            a0, a1 = (drop_to(ctx, c, out_level + PUBLIC_XOR_DEPTH) for c in (a0, a1))
+        if getattr(ctx, "lut_eval_public", None) is not None and getattr(ctx, "fused_luts", False):
+            need = self._public().need
+            try:
+                A0, A1 = joint_bases(ctx, [(a0, need, "pow"), (a1, need, "pow")])
+            except RuntimeError as e:
+                if "level" not in str(e):
+                    raise
+            else:
+                o0 = self._public_engine(A0, n0)
+                o1 = self._public_engine(A1, n1) if o0 is not None else None
+                if o0 is not None and o1 is not None:
+                    c0, c1 = conj_many(ctx, [o0[1], o1[1]])
+                    return ctx.add(o0[0], c0), ctx.add(o1[0], c1)
+        rows = self._public_rows()
+        B0, B1 = joint_bases(ctx, [(a0, rows, "std"), (a1, rows, "std")])
+        return self._public_loop(B0, n0), self._public_loop(B1, n1)
 
     __call__ = apply

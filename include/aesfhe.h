@@ -134,6 +134,28 @@ int aesfhe_mul(aesfhe_ctx* ctx, aesfhe_handle a, aesfhe_handle b, int relin, aes
 int aesfhe_lut_create(aesfhe_ctx* ctx, int n_a, int n_b, const double* re, const double* im, double c0_re, double c0_im,
                       aesfhe_handle* out);
 int aesfhe_lut_eval(aesfhe_ctx* ctx, aesfhe_handle lut, const aesfhe_handle* a, const aesfhe_handle* b, aesfhe_handle* out);
+/* Bivariate LUT(s) with a PUBLIC second operand: out_k = sum_p (sum_q C_k[p,q] zeta16^(q * nib[j])) a[p]
+ * at slot j: aesfhe_lut_eval with b an exact Zeta16 codeword known in clear (zeta16 = e^(-2 pi i / 16), the
+ * clear value of basis element q at nibble v being zeta16^(q v) for every q, mirrors included).  The XORs of
+ * a counter mode -- public counter block with the encrypted round key, encrypted keystream with the public
+ * AES ciphertext -- where REF/xor4_lut.py:63-74 would first encrypt the public bytes and form a second
+ * power basis; no reference counterpart.  lut1 / lut2 (0 = none): bivariate LUT handles with n_b = 16 and
+ * the same n_a, evaluated together (a conjugate-split LUT's S1 and S2): every a[p] is read once for both.
+ * a[0..n_a): single 2-polynomial ciphertexts (stacks are refused); entries of rows that are zero in both
+ * LUTs may be 0; at most 8 rows may be used.  nib: n_slots = slot_count bytes, each < 16 (else an error
+ * whose message contains "nibble"), copied before the call returns.  The operands are brought to canonical
+ * form and dropped exactly to their common lowest logical level l (l < 1: an error containing "level"); the
+ * per-slot coefficients are encoded on the device (fp64 FFT codec, no host encode, nothing cached per call)
+ * and each output is at level l - 1, owing its rescale as aesfhe_mul_pt_sum's result does.  The per-LUT
+ * table D[row][v] is built and uploaded on a LUT's first public evaluation (aesfhe_lut_free releases it);
+ * the evaluations themselves never synchronise the stream. */
+int aesfhe_lut_eval_public(aesfhe_ctx* ctx, aesfhe_handle lut1, aesfhe_handle lut2 /* 0 = none */,
+                           const aesfhe_handle* a, const uint8_t* nib, int n_slots,
+                           aesfhe_handle* out1, aesfhe_handle* out2);
+/* tests only: the coefficient plaintexts aesfhe_lut_eval_public multiplies by at `level` (>= 1) -- one per
+ * used row of `lut` in row order, nl(level) limbs of N words each, NTT form -- and the scale they were
+ * encoded at (the level's plaintext scale) */
+int aesfhe_debug_public_pt(aesfhe_ctx* ctx, aesfhe_handle lut, const uint8_t* nib, int n_slots, int level, uint32_t* out, double* scale);
 /* Releases a LUT's coefficient set and every per-level device constant cached for it (the
  * evaluator's plaintext caches, REF/lut.py:71-94 keeps them per object); fails if `lut` is not
  * a LUT handle.  aesfhe_free also accepts LUT handles; this entry states the intent. */
