@@ -158,6 +158,7 @@ struct Pt {
     std::vector<double> re, im;
     bool constant = false;
     std::map<int, std::pair<u32*, size_t>> enc;  // 2*level + mult -> (NTT-form encoding, words)
+    std::map<int, std::pair<u32*, size_t>> encx; // (level << 8) | special primes -> encoding over Q*P (rot_pt_sum)
 };
 
 enum Counter { C_MUL, C_RELIN, C_ROT, C_CONJ, C_PTMUL, C_SCALAR, C_RESCALE, C_NTT_ROWS, C_KS, C_ENC, C_DEC, C_BOOT, C_ADD, C_LUT, C_N };
@@ -210,7 +211,8 @@ public:
         (void)hipDeviceSynchronize();
         for (auto& kv : cts_) pools_[0].put(kv.second.data, kv.second.words);
         for (auto& kv : pts_)
-            for (auto& e : kv.second.enc) pools_[0].put(e.second.first, e.second.second);
+            for (auto* m : {&kv.second.enc, &kv.second.encx})
+                for (auto& e : *m) pools_[0].put(e.second.first, e.second.second);
         for (auto& d : deferred_) pools_[0].put(d.first, d.second);
         for (auto& pl : pools_) pl.release_all();
         for (void* p : owned_) (void)hipFree(p);
@@ -316,6 +318,7 @@ public:
         auto ip = pts_.find(h);
         if (ip != pts_.end()) {
             for (auto& e : ip->second.enc) give_back(e.second.first, e.second.second);
+            for (auto& e : ip->second.encx) give_back(e.second.first, e.second.second);
             pts_.erase(ip);
         }
     }
@@ -3035,6 +3038,116 @@ public:
         if (c.data != c_in.data) release(c);
         return out;
     }
+    // a mask encoded for the double-hoisted sum at `level` (rot_pt_sum): scale ptscale[level] on the nl Q limbs
+    // AND the np special primes of the level's key-switching basis (a prefix of the special primes: extmap),
+    // NTT form, cached on the plaintext per (level, np) and released with its handle
+    u32* pt_ext_at(Pt& p, int level, int np) {
+        const int key = (level << 8) | np;
+        auto it = p.encx.find(key);
+        if (it != p.encx.end()) return it->second.first;
+        const int nl = hp_.nl(level), ne = nl + np;
+        std::vector<u32> host;
+        encode_host(p.re.data(), p.im.data(), hp_.ptscale[level], nl, host, np);
+        u32* d = tmp(ne);
+        try {
+            HIP_OK(hipMemcpyAsync(d, host.data(), host.size() * sizeof(u32), hipMemcpyHostToDevice, S()));
+            HIP_OK(hipStreamSynchronize(S()));  // host vector may die after return
+            ntt(d, ne, ne, extmap(nl));
+            HIP_OK(hipStreamSynchronize(S()));  // cached for every stream
+        } catch (...) {
+            untmp(d, ne);
+            throw;
+        }
+        p.encx[key] = {d, (size_t)ne * hp_.n};
+        return d;
+    }
+    // out[j] = sum_i pts[j n + i] (.) rotate(c, steps[i]), double-hoisted (aesfhe_rot_pt_sum):
+    // c1 is ModUp'ed ONCE, k_rot_mask_mac forms every used rotation's key inner product through its
+    // automorphism, multiplies it by the term's mask and sums in Q*P -- one ModDown per output, under the
+    // level's own special basis (np_at / ksk_at; no FullP).  Each output owes its rescale as mul_pt_sum's.
+    std::vector<Ct> rot_pt_sum(const Ct& c_in, const std::vector<int>& steps, int n_out, const aesfhe_handle* pts) {
+        const int n = (int)steps.size();
+        if (n < 1 || n > kRotMacMax) throw std::runtime_error("rot_pt_sum: 1..16 terms");
+        if (n_out < 1 || n_out > kRotMacOut) throw std::runtime_error("rot_pt_sum: 1..2 outputs");
+        if (c_in.nb != 1) throw std::runtime_error("rot_pt_sum: a single ciphertext (stacks are refused)");
+        if (vis_npoly(c_in) != 2) throw std::runtime_error("rot_pt_sum: expects a 2-polynomial ciphertext");
+        if (c_in.level - c_in.pend < 1) throw std::runtime_error("not enough level to multiply by a plaintext (level 0)");
+        // every temporary and, until the call succeeds, every output goes back to the pool on the way out
+        struct Guard {
+            Engine& e;
+            std::vector<std::pair<u32*, size_t>> rows;
+            std::vector<Ct> cts;
+            u32* get(size_t r) {
+                u32* p = e.tmp(r);
+                rows.push_back({p, r});
+                return p;
+            }
+            ~Guard() {
+                for (auto& x : rows) e.untmp(x.first, x.second);
+                for (const Ct& c : cts) e.release(c);
+            }
+        } G{*this, {}, {}};
+        Ct c = normalize(c_in);
+        if (c.data != c_in.data) G.cts.push_back(c);
+        const int l = c.level, nl = hp_.nl(l), np = np_at(l), ne = nl + np, N = hp_.n;
+        const KsBasis& B = kb(l);
+        const long sc = slot_count();
+        RotMacArgs a;
+        a.c0 = c.data, a.c1 = c.data + (size_t)nl * N;
+        a.n = n, a.n_out = n_out;
+        a.nd = (nl + hp_.alpha - 1) / hp_.alpha, a.alpha = hp_.alpha, a.nkey = B.nkey, a.nks = B.nks;
+        bool rot_out[kRotMacOut] = {};
+        int nrot = 0, nmask = 0;
+        for (int i = 0; i < n; ++i) {
+            bool used = false;
+            for (int j = 0; j < n_out; ++j)
+                if (const aesfhe_handle h = pts[(size_t)j * n + i]) a.pt[j][i] = pt_ext_at(pt(h), l, np), used = true, ++nmask;
+            if (!used || (((long)steps[i] % sc + sc) % sc) == 0) continue;
+            a.gal[i] = rot_galois(steps[i]);
+            a.key[i] = ksk_at(a.gal[i], l);
+            for (int j = 0; j < n_out; ++j) rot_out[j] = rot_out[j] || a.pt[j][i];
+            ++nrot;
+        }
+        if (nrot) {
+            u32* ext = modup(a.c1, l, 1, 0);
+            G.rows.push_back({ext, (size_t)ext_rows(l)});
+            a.ext = ext;
+        }
+        std::vector<Ct> out(n_out);
+        for (int j = 0; j < n_out; ++j) {
+            out[j] = alloc_ct(l, 2);
+            G.cts.push_back(out[j]);
+            if (rot_out[j]) {
+                a.out0[j] = G.get(nl), a.out1[j] = G.get(nl), a.outp[j] = G.get(2 * (size_t)ne);
+            } else {  // no rotated term: the Q-side sums are the result
+                a.out0[j] = out[j].data, a.out1[j] = out[j].data + (size_t)nl * N;
+            }
+        }
+        launch_rot_mask_mac(S(), T_, a, nl, ne, extmap(nl));
+        for (int j = 0; j < n_out; ++j) {
+            if (rot_out[j]) moddown(a.outp[j], l, a.out0[j], a.out1[j], 1, 0, out[j].data);
+            out[j].pend = 1;
+            out[j].lazy = true;
+        }
+        cnt_[C_ROT] += nrot;
+        cnt_[C_KS] += nrot;
+        cnt_[C_PTMUL] += nmask;
+        tally(LV_KS, l, nrot);  // a hoisted rotation: one key switch each, as rotate_hoisted counts them
+        if (!headroom(l, 1, 1.0))
+            for (int j = 0; j < n_out; ++j) {
+                Ct r = rescale(out[j]);
+                G.cts.push_back(r);
+                out[j] = r;
+            }
+        // success: the outputs leave the guard (the rescaled ones' sources stay in it)
+        for (const Ct& o : out)
+            for (size_t x = 0; x < G.cts.size(); ++x)
+                if (G.cts[x].data == o.data) {
+                    G.cts.erase(G.cts.begin() + x);
+                    break;
+                }
+        return out;
+    }
     Ct rotate(const Ct& c, int steps) {
         const long s = slot_count();
         if (((long)steps % s + s) % s == 0) return copy(c);
@@ -5655,6 +5768,15 @@ int aesfhe_rotate_hoisted(aesfhe_ctx* ctx, aesfhe_handle c, int n, const int* st
     if (n < 0 || (n > 0 && (!steps || !out))) throw std::runtime_error("rotate_hoisted: bad arguments");
     std::vector<Ct> r = e.rotate_hoisted(e.canon(c), std::vector<int>(steps, steps + n));
     for (int i = 0; i < n; ++i) out[i] = e.put_ct(r[i]);
+    API_END
+}
+int aesfhe_rot_pt_sum(aesfhe_ctx* ctx, aesfhe_handle c, int n, const int* steps, int n_out, const aesfhe_handle* pts, aesfhe_handle* out) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!steps || !pts || !out) throw std::runtime_error("rot_pt_sum: bad arguments");
+    if (n < 1 || n > kRotMacMax) throw std::runtime_error("rot_pt_sum: 1..16 terms");
+    if (e.ct(c).nb != 1) throw std::runtime_error("rot_pt_sum: a single ciphertext (stacks are refused)");
+    std::vector<Ct> r = e.rot_pt_sum(e.canon(c), std::vector<int>(steps, steps + n), n_out, pts);
+    for (int j = 0; j < n_out; ++j) out[j] = e.put_ct(r[j]);
     API_END
 }
 int aesfhe_mul_many(aesfhe_ctx* ctx, int n, const aesfhe_handle* a, const aesfhe_handle* b, aesfhe_handle* out) {

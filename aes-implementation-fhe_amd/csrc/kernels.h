@@ -408,6 +408,28 @@ struct LinMacArgs {
     int pt_shift = 0, pt_logc = 0;
 };
 void launch_lin_mac(hipStream_t st, const DevTables& T, const LinMacArgs& m, int nl, int ne, LimbMap map);
+// masked rotation sum of ONE ciphertext (c0, c1), double-hoisted (aesfhe_rot_pt_sum):
+// row t < ne of the level's extended basis, for each output j < n_out:
+//   outp[j] = sum_{i: key[i]} pt[j][i] <ext, key[i]> read through X -> X^gal[i]   (2 polys of ne rows)
+//   out0[j] = sum_i pt[j][i] c0(X^gal[i]),  out1[j] = sum_{i: !key[i]} pt[j][i] c1   (t < nl)
+// pt[j][i]: term i's mask for output j over the ne rows (nullptr: absent); key[i] == nullptr: step 0.
+// ext: the hoisted ModUp of c1 ([nd][ne]); outp[j] may be nullptr when no term of output j rotates.
+constexpr int kRotMacMax = 16, kRotMacOut = 2;
+struct RotMacArgs {
+    const u32* c0 = nullptr;
+    const u32* c1 = nullptr;
+    const u32* ext = nullptr;
+    const u32* key[kRotMacMax] = {};
+    u64 gal[kRotMacMax] = {};
+    const u32* pt[kRotMacOut][kRotMacMax] = {};
+    u32* out0[kRotMacOut] = {};
+    u32* out1[kRotMacOut] = {};
+    u32* outp[kRotMacOut] = {};
+    int n = 0, n_out = 0;
+    int nd = 0, alpha = 1, nkey = 0, nks = 0;
+};
+static_assert(sizeof(RotMacArgs) <= sizeof(LinMacArgs), "RotMacArgs: the by-value kernel argument stays within LinMacArgs'");
+void launch_rot_mask_mac(hipStream_t st, const DevTables& T, const RotMacArgs& m, int nl, int ne, LimbMap map);
 
 // --- fused public-key encryption of a batch of messages (renorm re-encryption) -----------
 // one launch samples v, e0, e1 of every member (member m: streams stream_id(6|7|8, 0, base + m),

@@ -1838,6 +1838,103 @@ void launch_lin_mac(hipStream_t st, const DevTables& T, const LinMacArgs& m, int
     }
 }
 
+namespace {
+// see launch_rot_mask_mac (kernels.h); grid (N / 256, ne rows), one coefficient of one Q*P row per
+// thread.  Term i's key inner product is formed in place from the hoisted ModUp, read through
+// X -> X^gal[i] (lin_mac_body's baby-step form), and goes into both outputs' accumulators before the
+// next term is touched: each ext and key word is loaded once.  8 u64 accumulators, no LDS.
+// ND as k_lin_mac's: the digit loop unrolled so a term's 2 * ND key loads and ND gathers are in flight together
+template <int ND>
+__global__ void __launch_bounds__(kBlock) k_rot_mask_mac(RotMacArgs m, int nl, int ne, LimbMap map, const PrimeConst* pc, int logn, int xcd) {
+    int t = blockIdx.y, bx = blockIdx.x;
+    if (xcd) xcd_rows(logn - 8, ne, bx, t);
+    const size_t k = (size_t)bx * kBlock + threadIdx.x;
+    const PrimeConst P = pc[map.prime(t)];
+    const bool qrow = t < nl;
+    const size_t row = (size_t)t << logn, at = row + k;
+    const size_t po = (size_t)ne << logn;  // poly stride of outp
+    u64 a0[kRotMacOut] = {}, a1[kRotMacOut] = {}, p0[kRotMacOut] = {}, p1[kRotMacOut] = {};
+    const int krow = qrow ? t : m.nks + (t - nl);
+    const int own = qrow ? t / m.alpha : -1;
+    for (int i = 0; i < m.n; ++i) {
+        if (i && (i & 7) == 0) {
+#pragma unroll
+            for (int j = 0; j < kRotMacOut; ++j) {
+                a0[j] = fold64(a0[j], P.q, P.r32), a1[j] = fold64(a1[j], P.q, P.r32);
+                p0[j] = fold64(p0[j], P.q, P.r32), p1[j] = fold64(p1[j], P.q, P.r32);
+            }
+        }
+        if (!m.pt[0][i] && !m.pt[1][i]) continue;
+        u32 c0v = 0, c1v = 0, u0 = 0, u1 = 0;
+        if (m.key[i]) {
+            const size_t ks = galois_src((u32)k, m.gal[i], logn);
+            if (qrow) c0v = m.c0[row + ks];
+            u64 s0 = 0, s1 = 0;
+            const int nd = ND > 0 ? ND : m.nd;
+#pragma unroll
+            for (int dj = 0; dj < nd; ++dj) {
+                if (dj && (dj & 7) == 0) s0 = fold64(s0, P.q, P.r32), s1 = fold64(s1, P.q, P.r32);
+                const u32* kb = m.key[i] + (((size_t)dj * 2 * m.nkey + krow) << logn) + k;
+                const u64 vb = kb[0], va = kb[(size_t)m.nkey << logn];
+                const u32 e = dj == own ? m.c1[row + ks] : m.ext[(((size_t)dj * ne + t) << logn) + ks];
+                s0 += e * vb;
+                s1 += e * va;
+            }
+            u0 = reduce64(s0, P.q, P.mu, P.r32), u1 = reduce64(s1, P.q, P.mu, P.r32);
+        } else if (qrow) {  // step 0: no key switch, the term stays on the Q limbs
+            c0v = m.c0[at], c1v = m.c1[at];
+        }
+#pragma unroll
+        for (int j = 0; j < kRotMacOut; ++j) {
+            if (!m.pt[j][i]) continue;
+            const u64 pv = m.pt[j][i][at];
+            a0[j] += c0v * pv;  // q < 2^30: 8 products fit beside a folded accumulator
+            a1[j] += c1v * pv;
+            p0[j] += u0 * pv;
+            p1[j] += u1 * pv;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kRotMacOut; ++j) {
+        if (j >= m.n_out) continue;
+        if (qrow) {
+            m.out0[j][at] = reduce64(a0[j], P.q, P.mu, P.r32);
+            m.out1[j][at] = reduce64(a1[j], P.q, P.mu, P.r32);
+        }
+        if (m.outp[j]) {
+            m.outp[j][at] = reduce64(p0[j], P.q, P.mu, P.r32);
+            m.outp[j][po + at] = reduce64(p1[j], P.q, P.mu, P.r32);
+        }
+    }
+}
+}  // namespace
+
+void launch_rot_mask_mac(hipStream_t st, const DevTables& T, const RotMacArgs& m, int nl, int ne, LimbMap map) {
+    if (m.n < 1 || m.n > kRotMacMax || m.n_out < 1 || m.n_out > kRotMacOut) throw std::runtime_error("launch_rot_mask_mac: 1..16 terms, 1..2 outputs");
+    // algorithmic bytes (rows of N words): c0 and c1 once, the hoisted ext once when any term
+    // rotates (its per-term gathers hit L2), every used key and every mask once, every output row written once
+    double rows = 2.0 * nl;
+    bool any_key = false;
+    for (int i = 0; i < m.n; ++i) {
+        if (!m.pt[0][i] && !m.pt[1][i]) continue;
+        if (m.key[i]) rows += 2.0 * m.nd * ne, any_key = true;
+        for (int j = 0; j < m.n_out; ++j)
+            if (m.pt[j][i]) rows += m.key[i] ? ne : nl;
+    }
+    if (any_key) rows += (double)m.nd * ne;
+    for (int j = 0; j < m.n_out; ++j) rows += 2.0 * nl + (m.outp[j] ? 2.0 * ne : 0.0);
+    const double bytes = words(rows * (1u << T.logn));
+    const dim3 g = ew_grid(T.logn, ne), b(kBlock);
+    const int xcd = xcd_rows_on();
+    switch (m.nd) {  // the digit counts of the AES levels (3..9 limbs); others take the run-time loop
+#define ROT_MAC_ND(D) \
+    case D: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<D>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd); break;
+        ROT_MAC_ND(1) ROT_MAC_ND(2) ROT_MAC_ND(3) ROT_MAC_ND(4)
+#undef ROT_MAC_ND
+        default: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<0>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd);
+    }
+}
+
 void launch_mac(hipStream_t st, const DevTables& T, u32* out, const MacTerms& m, size_t xs, size_t os, int rows, int npoly, LimbMap map) {
     if (m.n < 1 || m.n > kMacMax) throw std::runtime_error("launch_mac: 1..16 terms");
     prof_launch(KID_ELEMENTWISE, words((2.0 * m.n + 1.0) * npoly * rows * (1u << T.logn)), k_mac,

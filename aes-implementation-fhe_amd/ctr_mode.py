@@ -1,8 +1,9 @@
 """Counter mode over a 16-byte block function: plain byte helpers, no engine.
 
-The block function is whatever the caller passes -- for this project the cipher AESPipeline.encrypt
-computes (oracle/aes_plain.ref_encrypt: the reference's MixColumns mixes along rows),
-which is NOT FIPS-197, so the NIST SP 800-38A vectors do not apply.  Nothing here looks inside a block:
+The block function is whatever the caller passes: fips_block_fn(rks) is FIPS-197 AES-128, the cipher of
+AESPipeline(fips=True), and makes ctr_xor the standard AES-CTR of NIST SP 800-38A (its 16-byte initial counter
+block split into nonce12 and a 32-bit counter); the default pipeline computes the reference's cipher instead
+(oracle/aes_plain.ref_encrypt: its MixColumns mixes along rows).  Nothing here looks inside a block:
 a counter block is 16 bytes handed to the block function as they are, and the keystream is XORed byte
 for byte, so another byte order inside the block function changes nothing in this module.
 """
@@ -24,6 +25,36 @@ def counter_blocks(nonce12, counter0: int, n: int) -> np.ndarray:
     for k in range(4):
         out[:, 12 + k] = (ctr >> np.uint64(8 * (3 - k))) & np.uint64(0xFF)
     return out
+
+
+def fips_block_fn(rks):
+    """FIPS-197 AES-128 encryption under the 11 round keys rks as a block function for ctr_xor: the standard
+    AES-CTR (SP 800-38A) whose ciphertexts AESPipeline(fips=True).transcipher inverts.  Plain bytes, column-first
+    state (byte r + 4c), MixColumns along the columns as the standard has it"""
+    from aes_keyschedule import SBOX
+    from shift_rows import shift_rows_bytes
+    keys = [np.asarray(k, dtype=np.uint8).reshape(16) for k in rks]
+    if len(keys) != 11:
+        raise ValueError("AES-128 takes 11 round keys")
+
+    def xtime(a):
+        return (((a.astype(np.uint16) << 1) ^ np.where(a & 0x80, 0x1B, 0)) & 0xFF).astype(np.uint8)
+
+    def mix_columns(s):
+        a = s.reshape(4, 4)  # [c, r]
+        out = np.empty_like(a)
+        for r in range(4):
+            x, y = a[:, r], a[:, (r + 1) % 4]
+            out[:, r] = xtime(x) ^ xtime(y) ^ y ^ a[:, (r + 2) % 4] ^ a[:, (r + 3) % 4]
+        return out.reshape(16)
+
+    def block(pt):
+        s = np.asarray(pt, dtype=np.uint8).reshape(16) ^ keys[0]
+        for r in range(1, 10):
+            s = mix_columns(shift_rows_bytes(SBOX[s], -1)) ^ keys[r]
+        return shift_rows_bytes(SBOX[s], -1) ^ keys[10]
+
+    return block
 
 
 def ctr_xor(block_fn, data, nonce12, counter0: int) -> np.ndarray:

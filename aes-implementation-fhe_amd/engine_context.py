@@ -149,6 +149,24 @@ class EngineContext:
         """[rotate(ct, s) for s in steps], hoisted (one ModUp)"""
         return self.engine.rotate_many(ct, steps)
 
+    def rot_pt_sum(self, ct, steps, pts_per_output):
+        """[sum_i pts[i] * rotate(ct, steps[i]) for pts in pts_per_output] (pts entries None: term absent): one
+        double-hoisted engine call (include/aesfhe.h aesfhe_rot_pt_sum); with an engine that
+        lacks the entry point, the same sums from hoisted rotations, plaintext products and additions"""
+        fused = getattr(self.engine, "rot_pt_sum", None)
+        if fused is not None:
+            return fused(ct, steps, pts_per_output)
+        rots = self.rotate_many(ct, steps)
+        out = []
+        for pts in pts_per_output:
+            acc = None
+            for r, p in zip(rots, pts):
+                if p is not None:
+                    term = self.engine.multiply(r, p)
+                    acc = term if acc is None else self.engine.add(acc, term)
+            out.append(acc if acc is not None else self.engine.multiply(ct, 0.0))
+        return out
+
     def rotate(self, ct, steps: int):
         """np.roll(slots, steps) semantics."""
         return self.engine.rotate(ct, self.rotation_key, steps)

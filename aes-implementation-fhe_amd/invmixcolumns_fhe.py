@@ -24,7 +24,10 @@ class InvMixColumnsFHE:
         self.xor4 = xor4
         self.sc = ctx.engine.slot_count
         # states > 1: slot-packed batch; layout.periodic: the periodic layout (state_encoder.py)
-        self.enc = StateEncoder(ctx, states, periodic=bool(layout is not None and layout.periodic))
+        # byte_order follows the caller's layout (AESPipeline(fips=True): transposed), so this module's renorms
+        # accept and hand back the pipeline's tagged ciphertexts
+        self.enc = StateEncoder(ctx, states, periodic=bool(layout is not None and layout.periodic),
+                                **({"byte_order": layout.byte_order} if getattr(layout, "byte_order", "plain") != "plain" else {}))
         self.layout = self.enc.layout
         self.stride = self.layout.unit
         self._coeffs = _CoeffCache()

@@ -49,6 +49,7 @@ EXPORTED = [
     "aesfhe_debug_mono_pack", "aesfhe_debug_mono_split", "aesfhe_alg_bytes", "aesfhe_stack", "aesfhe_unstack", "aesfhe_members",
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
     "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
+    "aesfhe_rot_pt_sum",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -96,6 +97,7 @@ def load_library(path: Optional[Path] = None):
         "aesfhe_mul_many": [vp, c_int, _Hp, _Hp, _Hp], "aesfhe_conjugate_many": [vp, c_int, _Hp, _Hp],
         "aesfhe_mul_pt_sum": [vp, c_int, _Hp, _Hp, _Hp], "aesfhe_renorm_pool": [vp, c_int], "aesfhe_set_stack_pack": [vp, c_int],
         "aesfhe_rotate_hoisted": [vp, _H, c_int, ctypes.POINTER(c_int), _Hp],
+        "aesfhe_rot_pt_sum": [vp, _H, c_int, ctypes.POINTER(c_int), c_int, _Hp, _Hp],
         "aesfhe_to_ntt": [vp, _H, _Hp], "aesfhe_to_intt": [vp, _H, _Hp], "aesfhe_bootstrap": [vp, _H, _Hp],
         "aesfhe_renorm_pair": [vp, _H, _H, _Hp, _Hp],
         "aesfhe_bootstrap_pair": [vp, _H, _H, _Hp, _Hp],
@@ -718,6 +720,22 @@ class Engine:
         st, out = (ctypes.c_int * n)(*steps), (ctypes.c_uint64 * n)()
         self._ctx.check(self._lib.aesfhe_rotate_hoisted(self._ctx.ptr, ct.handle, n, st, out))
         return [Ciphertext(self._ctx, out[i]) for i in range(n)]
+
+    def rot_pt_sum(self, ct, steps, pts_per_output) -> List[Ciphertext]:
+        """[sum_i pts[i] * rotate(ct, steps[i]) for pts in pts_per_output] -- 1..16 steps (0: no key switch), 1..2
+        outputs, each a list of len(steps) plaintexts or None (term absent) -- as one double-hoisted engine call
+        (aesfhe_rot_pt_sum: one ModUp, one kernel, one ModDown per output); the same value as the separate
+        rotations, plaintext products and sums within CKKS rounding, each output owing its rescale"""
+        steps = [int(x) for x in steps]
+        n, n_out = len(steps), len(pts_per_output)
+        if any(len(p) != n for p in pts_per_output):
+            raise ValueError("rot_pt_sum: every output takes one plaintext (or None) per step")
+        self._ensure_keys()
+        st = (ctypes.c_int * max(n, 1))(*steps)
+        pts = (ctypes.c_uint64 * max(n * n_out, 1))(*[0 if q is None else q.handle for p in pts_per_output for q in p])
+        out = (ctypes.c_uint64 * max(n_out, 1))()
+        self._ctx.check(self._lib.aesfhe_rot_pt_sum(self._ctx.ptr, self._settled(ct).handle, n, st, n_out, pts, out))
+        return [Ciphertext(self._ctx, out[j]) for j in range(n_out)]
 
     def galois_multi(self, items) -> List[Ciphertext]:
         """[(ct, g)] -> [ct through X -> X^g, key-switched] for odd g < 2N (aesfhe_galois_multi):

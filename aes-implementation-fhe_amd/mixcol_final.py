@@ -151,7 +151,10 @@ class MixColFinal:
         self.xor4 = xor4
         self.sc = ctx.engine.slot_count
         # states > 1: slot-packed batch; layout.periodic: the periodic layout (state_encoder.py)
-        self.enc = StateEncoder(ctx, states, periodic=bool(layout is not None and layout.periodic))
+        # byte_order follows the caller's layout (AESPipeline(fips=True): transposed), so this module's renorms
+        # accept and hand back the pipeline's tagged ciphertexts
+        self.enc = StateEncoder(ctx, states, periodic=bool(layout is not None and layout.periodic),
+                                **({"byte_order": layout.byte_order} if getattr(layout, "byte_order", "plain") != "plain" else {}))
         self.layout = self.enc.layout
         self.stride = stride if stride is not None else self.layout.unit
         self._coeffs = _CoeffCache()
@@ -260,6 +263,8 @@ class MixColFinal:
         s1 = -4 * self.stride
         if getattr(shift, "direction", None) != -1 or not lay.same(getattr(shift, "layout", None)) or not lay.packable:
             raise ValueError("sr_entry: ShiftRows of this module's packed periodic layout")
+        if getattr(shift, "column_form", False):
+            return self._sc_entry(x_hi, x_lo, shift)
         rh, rl = rot_pair(ctx, x_hi, x_lo, [s1, 2 * s1, 3 * s1])
         R = ((x_hi, *rh), (x_lo, *rl))
         rows = [lay.row_mask(r).real for r in range(4)]
@@ -282,6 +287,25 @@ class MixColFinal:
             return terms[0]
 
         return masked_sum("sr_p0", 0), masked_sum("sr_p1", 1)
+
+    def _sc_entry(self, x_hi, x_lo, shift):
+        """sr_entry for a shift_columns.ShiftColumns: the permutation moves bytes inside groups of 4, so there is
+        no R^4 = id to share three rotations between the two outputs -- pack(SC(x)) reads offsets -3 .. 3 units
+        and pack(rot(SC(x), s1)) offsets 1 .. 7 (shift_columns.entry_terms): 11 steps, 7 masked terms per half
+        and output.  ONE ctx.rot_pt_sum call per half with two outputs (one ModUp, one kernel, two ModDowns:
+        DESIGN.md §3.18), the pack's half masks folded into the cell masks; the halves' results are added.  Both
+        outputs are one level of mask products below x, as the ShiftRows form's."""
+        from shift_columns import entry_terms
+        ctx = self.ctx
+        key = ("sc_entry", shift.direction)
+        cache = self.__dict__.setdefault("_pt_cache", {})
+        if key not in cache:
+            steps, masks = entry_terms(self.layout, shift.direction)
+            cache[key] = (steps, [[[None if m is None else ctx.encode(m) for m in row] for row in half] for half in masks])
+        steps, pts = cache[key]
+        hi0, hi1 = ctx.rot_pt_sum(x_hi, steps, pts[0])
+        lo0, lo1 = ctx.rot_pt_sum(x_lo, steps, pts[1])
+        return ctx.add(hi0, lo0), ctx.add(hi1, lo1)
 
     def mix_packed(self, ct_hi, ct_lo, do_final_bootstrap: bool = True, sr=None, on_sr=None):
         """MixColumns with its XOR stage on packed states (StateEncoder.pack: hi and lo side by side

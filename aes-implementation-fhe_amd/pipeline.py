@@ -35,6 +35,15 @@ runs the reference's pair steps).
 layout (state_encoder.py): ``encrypt`` / ``decrypt`` take and return
 (B, 16) arrays through the same step sequence, and a (16,) round key is shared by all B
 states (a (B, 16) key array gives each state its own).
+
+``fips=True`` computes FIPS-197 AES-128 instead of the reference's cipher (whose MixColumns mixes along
+rows).  With T the 4 x 4 byte transpose, fips_encrypt(p, rks) = T(E'(T p, [T rk_r])) where
+E' is this pipeline's round sequence with ShiftColumns = T . ShiftRows . T in place of ShiftRows
+(shift_columns.py) and MixColumns unchanged; decrypt likewise with the inverses.  So the mode is the two
+ShiftColumns modules plus a byte transpose wherever clear bytes enter or leave (the encoder's
+byte_order="transposed": states, round keys, counter blocks, public AES ciphertext bytes, decode and the debug
+snapshots).  Its pairs are tagged transposed and refused by a plain pipeline (check_layout).  ``fuse_sub_ark``,
+``fuse_sr_mc`` and ``pairs`` > 1 are not available with it (ValueError).
 """
 from __future__ import annotations
 
@@ -69,8 +78,11 @@ class AESPipeline:
                  inv_mixcolumns: InvMixColumnsFHE | None = None, use_hard_renorm_between_steps: bool = False,
                  with_inv_mix_columns: bool = True, states: int = 1, fuse_sub_ark: bool = False,
                  fuse_sr_mc: bool = False, true_fhe: bool = False, periodic: bool | None = None,
-                 packed_xor: bool | None = None, pairs: int = 1):
+                 packed_xor: bool | None = None, pairs: int = 1, fips: bool = False):
         self.ctx = ctx
+        self.fips = bool(fips)
+        if fips and (fuse_sub_ark or fuse_sr_mc or pairs > 1):
+            raise ValueError("fips=True does not combine with fuse_sub_ark, fuse_sr_mc or pairs > 1")
         self.states = states
         # pairs > 1: a multi-pair batch -- `pairs` ciphertext pairs of `states` states each, run as
         # ONE stacked pair through every step (state_encoder.StateEncoder)
@@ -83,7 +95,8 @@ class AESPipeline:
                 lay = getattr(mod, "layout", None)
                 if lay is not None:
                     periodic = lay.periodic
-        self.encoder = StateEncoder(ctx, states, periodic=periodic, pairs=pairs)
+        self.encoder = (StateEncoder(ctx, states, periodic=periodic, pairs=pairs, byte_order="transposed") if fips else
+                        StateEncoder(ctx, states, periodic=periodic, pairs=pairs))
         self.layout = self.encoder.layout
         self.sc = ctx.engine.slot_count
         self.stride = self.layout.unit
@@ -92,8 +105,13 @@ class AESPipeline:
         self.xor4 = XOR4LUT(ctx, np.asarray(coeffs["xor4"]) / 256.0 if true_fhe else coeffs["xor4"])
         self.sub = SubBytesLUT(ctx, coeffs["sub_hi"], coeffs["sub_lo"])
         self.isub = SubBytesLUT(ctx, coeffs["inv_sub_hi"], coeffs["inv_sub_lo"]) if "inv_sub_hi" in coeffs else None
-        self.shift = ShiftRows(ctx, states=states, layout=self.layout)
-        self.invshift = InvShiftRows(ctx, states=states, layout=self.layout)
+        if fips:
+            from shift_columns import InvShiftColumns, ShiftColumns
+            self.shift = ShiftColumns(ctx, states=states, layout=self.layout)
+            self.invshift = InvShiftColumns(ctx, states=states, layout=self.layout)
+        else:
+            self.shift = ShiftRows(ctx, states=states, layout=self.layout)
+            self.invshift = InvShiftRows(ctx, states=states, layout=self.layout)
         self.mix = mixcolumns if mixcolumns is not None else MixColFinal(ctx, self.xor4, states=states, layout=self.layout)
         self.invmix = (inv_mixcolumns if inv_mixcolumns is not None else
                        InvMixColumnsFHE(ctx, self.xor4, states=states, layout=self.layout))

@@ -67,6 +67,12 @@ class SlotLayout:
             m[(r + 4 * c) * self.unit:(r + 4 * c) * self.unit + self.states] = 1.0
         return self.tile(m)
 
+    def cell_mask(self, r: int, c: int) -> np.ndarray:
+        """ones on byte r + 4c of every state (the row masks split by column: shift_columns.py)"""
+        m = np.zeros(self.period, dtype=np.complex128)
+        m[(r + 4 * c) * self.unit:(r + 4 * c) * self.unit + self.states] = 1.0
+        return self.tile(m)
+
     @property
     def packable(self) -> bool:
         """hi and lo fit side by side in one ciphertext: the packed form holds the
@@ -79,8 +85,13 @@ class SlotLayout:
         m[which * self.period:(which + 1) * self.period] = 1.0
         return np.tile(m, self.sc // (2 * self.period))
 
+    # "transposed": the ciphertexts hold T(state) (shift_columns.transpose_bytes; AESPipeline(fips=True)) -- part
+    # of the tag check_layout compares, so a transposed pair never meets a plain pipeline or encoder
+    byte_order = "plain"
+
     def same(self, other) -> bool:
-        return other is not None and (self.sc, self.states, self.periodic) == (other.sc, other.states, other.periodic)
+        return other is not None and (self.sc, self.states, self.periodic, self.byte_order) == (
+            other.sc, other.states, other.periodic, getattr(other, "byte_order", "plain"))
 
 
 def tag_layout(layout: SlotLayout, *cts):
@@ -105,7 +116,8 @@ def check_layout(layout: SlotLayout, *cts) -> None:
 
 
 def _describe(lay: SlotLayout) -> str:
-    return f"{'periodic' if lay.periodic else 'reference'} (states={lay.states})"
+    order = ", transposed bytes" if getattr(lay, "byte_order", "plain") == "transposed" else ""
+    return f"{'periodic' if lay.periodic else 'reference'} (states={lay.states}{order})"
 
 
 class StateEncoder:
@@ -114,10 +126,16 @@ class StateEncoder:
     ciphertext (ctx.stack): encode takes (pairs, states, 16) / (pairs, 16) bytes, decode returns
     them, and every AES module runs on the stacks unchanged."""
 
-    def __init__(self, ctx, states: int = 1, periodic: bool = False, pairs: int = 1):
+    def __init__(self, ctx, states: int = 1, periodic: bool = False, pairs: int = 1, byte_order: str = "plain"):
         self.ctx = ctx
         self.sc = ctx.engine.slot_count
         self.layout = SlotLayout(self.sc, states, periodic)
+        # byte_order="transposed" (AESPipeline(fips=True)): every clear byte state is transposed on its way in
+        # (encode, nibble_slots, encode_packed) and out (decode, decode_packed), so callers see FIPS-197 byte order
+        # while the ciphertexts hold T(state); the layout tag carries it
+        if byte_order not in ("plain", "transposed"):
+            raise ValueError(f"byte_order must be 'plain' or 'transposed', got {byte_order!r}")
+        self.byte_order = self.layout.byte_order = byte_order
         self.stride = self.layout.unit  # rotation unit (REF: slot_count / 16)
         self.states = states
         if pairs < 1:
@@ -131,12 +149,20 @@ class StateEncoder:
         self.renorm_quad_hook = None  # true-FHE: two pairs per bootstrap (renorm_two)
 
     def _as_batch(self, state: np.ndarray) -> np.ndarray:
+        """clear bytes in: the (B, 16) batch in the ciphertexts' byte order"""
         state = np.asarray(state, dtype=np.uint8)
         if state.shape == (16,) and self.states == 1:
-            return state[None, :]
-        if state.shape != (self.states, 16):
+            state = state[None, :]
+        elif state.shape != (self.states, 16):
             raise ValueError(f"expected a ({self.states}, 16) uint8 state array, got {state.shape}")
-        return state
+        return self._order(state)
+
+    def _order(self, state: np.ndarray) -> np.ndarray:
+        """the byte transpose of a transposed encoder (an involution: in and out alike), else the state itself"""
+        if self.byte_order != "transposed":
+            return state
+        from shift_columns import transpose_bytes
+        return transpose_bytes(state)
 
     def _pack(self, nibbles: np.ndarray) -> np.ndarray:
         """nibbles (B, 16) -> slot vector; slot i*unit + b <- zeta^nibbles[b, i] (periodic: tiled)"""
@@ -193,7 +219,7 @@ class StateEncoder:
     def _decode1(self, ct_hi, ct_lo) -> np.ndarray:
         hi = ZetaEncoder.from_zeta(self._take(self.ctx.decrypt(ct_hi)), 16)
         lo = ZetaEncoder.from_zeta(self._take(self.ctx.decrypt(ct_lo)), 16)
-        out = ((hi << 4) | lo).astype(np.uint8)
+        out = self._order(((hi << 4) | lo).astype(np.uint8))
         return out[0] if self.states == 1 else out
 
     # ---------------------------------------------------------------- packed form
@@ -236,7 +262,7 @@ class StateEncoder:
         z = self.ctx.decrypt(ct)
         hi = ZetaEncoder.from_zeta(self._take(z), 16)
         lo = ZetaEncoder.from_zeta(self._take(z[self.layout.period:]), 16)
-        out = ((hi << 4) | lo).astype(np.uint8)
+        out = self._order(((hi << 4) | lo).astype(np.uint8))
         return out[0] if self.states == 1 else out
 
     UNPACK_DEPTH = 1  # unpack(): one mask product after the rotation

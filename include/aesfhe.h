@@ -226,6 +226,20 @@ int aesfhe_members(aesfhe_ctx* ctx, aesfhe_handle h, int* members);
  * row rotations of REF/shift_rows.py:39-56), hoisted: one ModUp for all of them.  Same
  * results as n aesfhe_rotate calls. */
 int aesfhe_rotate_hoisted(aesfhe_ctx* ctx, aesfhe_handle ct, int n, const int* steps, aesfhe_handle* out);
+/* Masked rotation sum of ONE ciphertext, double-hoisted:
+ *   out[j] = sum_i pts[j*n + i] * rotate(ct, steps[i]),  j < n_out (1..2), i < n (1..16);
+ * pts entries may be 0 (term absent); steps[i] may be 0 (no key switch for that term).  The same value as
+ * n aesfhe_rotate calls, aesfhe_mul_pt each and aesfhe_add (REF/engine_context.py:127-132, :65-68, :70-74;
+ * the masked rotations of REF/shift_rows.py:39-56 generalised to a permutation inside the state's columns,
+ * shift_columns.py), within CKKS rounding and not bit-exact: c1 is ModUp'ed once, every used rotation's key
+ * inner product is multiplied by its mask and summed in Q*P, and each output pays ONE ModDown (after the
+ * mask instead of before it).  rotate keeps np.roll's convention.  The input is brought to canonical form;
+ * each output is at that level and owes its rescale as aesfhe_mul_pt_sum's result does.  It runs over the
+ * level's own special basis (aesfhe_set_low_p on or off); the masks are encoded once per (plaintext, level,
+ * special-prime count) over those limbs, cached on the plaintext handle and released with it.  Stacks and
+ * 3-polynomial inputs are refused. */
+int aesfhe_rot_pt_sum(aesfhe_ctx* ctx, aesfhe_handle ct, int n, const int* steps, int n_out, const aesfhe_handle* pts,
+                      aesfhe_handle* out);
 /* engine.make_power_basis(ct, degree, relinearization_key), REF/engine_context.py:100-101;
  * out[k-1] = ct^k, k = 1..degree */
 int aesfhe_power_basis(aesfhe_ctx* ctx, aesfhe_handle ct, int degree, aesfhe_handle* out);
