@@ -3061,11 +3061,29 @@ public:
         p.encx[key] = {d, (size_t)ne * hp_.n};
         return d;
     }
+    // a fill of the affine sum at `level` (rot_pt_affine): the product scale raw_scale(level, 1) an output owing
+    // its rescale carries, on the nl Q limbs (the fill meets c0 before the ModDown's P part is folded in), NTT
+    // form, cached beside the masks per (level, np) under its own key bit and released with the handle
+    u32* pt_fill_at(Pt& p, int level, int np) {
+        const int key = (1 << 30) | (level << 8) | np;
+        auto it = p.encx.find(key);
+        if (it != p.encx.end()) return it->second.first;
+        const int nl = hp_.nl(level);
+        std::vector<u32> host;
+        encode_host(p.re.data(), p.im.data(), raw_scale(level, 1), nl, host);
+        u32* d = upload_ntt(host, nl);
+        HIP_OK(hipStreamSynchronize(S()));  // cached for every stream
+        p.encx[key] = {d, (size_t)nl * hp_.n};
+        return d;
+    }
     // out[j] = sum_i pts[j n + i] (.) rotate(c, steps[i]), double-hoisted (aesfhe_rot_pt_sum):
     // c1 is ModUp'ed ONCE, k_rot_mask_mac forms every used rotation's key inner product through its
     // automorphism, multiplies it by the term's mask and sums in Q*P -- one ModDown per output, under the
     // level's own special basis (np_at / ksk_at; no FullP).  Each output owes its rescale as mul_pt_sum's.
-    std::vector<Ct> rot_pt_sum(const Ct& c_in, const std::vector<int>& steps, int n_out, const aesfhe_handle* pts) {
+    // fills (aesfhe_rot_pt_affine): n_out plaintext handles (0: none), out[j] += fills[j] inside
+    // the same kernel; nullptr or all 0 is the plain sum, launch for launch.
+    std::vector<Ct> rot_pt_sum(const Ct& c_in, const std::vector<int>& steps, int n_out, const aesfhe_handle* pts,
+                               const aesfhe_handle* fills = nullptr) {
         const int n = (int)steps.size();
         if (n < 1 || n > kRotMacMax) throw std::runtime_error("rot_pt_sum: 1..16 terms");
         if (n_out < 1 || n_out > kRotMacOut) throw std::runtime_error("rot_pt_sum: 1..2 outputs");
@@ -3108,6 +3126,9 @@ public:
             for (int j = 0; j < n_out; ++j) rot_out[j] = rot_out[j] || a.pt[j][i];
             ++nrot;
         }
+        int nfill = 0;
+        for (int j = 0; fills && j < n_out; ++j)
+            if (fills[j]) a.fill[j] = pt_fill_at(pt(fills[j]), l, np), ++nfill;
         if (nrot) {
             u32* ext = modup(a.c1, l, 1, 0);
             G.rows.push_back({ext, (size_t)ext_rows(l)});
@@ -3132,6 +3153,7 @@ public:
         cnt_[C_ROT] += nrot;
         cnt_[C_KS] += nrot;
         cnt_[C_PTMUL] += nmask;
+        cnt_[C_ADD] += nfill;
         tally(LV_KS, l, nrot);  // a hoisted rotation: one key switch each, as rotate_hoisted counts them
         if (!headroom(l, 1, 1.0))
             for (int j = 0; j < n_out; ++j) {
@@ -5776,6 +5798,17 @@ int aesfhe_rot_pt_sum(aesfhe_ctx* ctx, aesfhe_handle c, int n, const int* steps,
     if (n < 1 || n > kRotMacMax) throw std::runtime_error("rot_pt_sum: 1..16 terms");
     if (e.ct(c).nb != 1) throw std::runtime_error("rot_pt_sum: a single ciphertext (stacks are refused)");
     std::vector<Ct> r = e.rot_pt_sum(e.canon(c), std::vector<int>(steps, steps + n), n_out, pts);
+    for (int j = 0; j < n_out; ++j) out[j] = e.put_ct(r[j]);
+    API_END
+}
+int aesfhe_rot_pt_affine(aesfhe_ctx* ctx, aesfhe_handle c, int n, const int* steps, int n_out, const aesfhe_handle* pts,
+                         const aesfhe_handle* fills, aesfhe_handle* out) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!steps || !pts || !fills || !out) throw std::runtime_error("rot_pt_affine: bad arguments");
+    if (n < 1 || n > kRotMacMax) throw std::runtime_error("rot_pt_affine: 1..16 terms");
+    if (n_out < 1 || n_out > kRotMacOut) throw std::runtime_error("rot_pt_affine: 1..2 outputs");
+    if (e.ct(c).nb != 1) throw std::runtime_error("rot_pt_affine: a single ciphertext (stacks are refused)");
+    std::vector<Ct> r = e.rot_pt_sum(e.canon(c), std::vector<int>(steps, steps + n), n_out, pts, fills);
     for (int j = 0; j < n_out; ++j) out[j] = e.put_ct(r[j]);
     API_END
 }

@@ -414,6 +414,8 @@ void launch_lin_mac(hipStream_t st, const DevTables& T, const LinMacArgs& m, int
 //   out0[j] = sum_i pt[j][i] c0(X^gal[i]),  out1[j] = sum_{i: !key[i]} pt[j][i] c1   (t < nl)
 // pt[j][i]: term i's mask for output j over the ne rows (nullptr: absent); key[i] == nullptr: step 0.
 // ext: the hoisted ModUp of c1 ([nd][ne]); outp[j] may be nullptr when no term of output j rotates.
+// fill[j] set (aesfhe_rot_pt_affine): a plaintext over the nl Q rows at the product scale, added
+// to out0[j] in the same pass (k_rot_mask_mac's FILL variant; with no fill the launch is rot_pt_sum's own).
 constexpr int kRotMacMax = 16, kRotMacOut = 2;
 struct RotMacArgs {
     const u32* c0 = nullptr;
@@ -425,6 +427,7 @@ struct RotMacArgs {
     u32* out0[kRotMacOut] = {};
     u32* out1[kRotMacOut] = {};
     u32* outp[kRotMacOut] = {};
+    const u32* fill[kRotMacOut] = {};
     int n = 0, n_out = 0;
     int nd = 0, alpha = 1, nkey = 0, nks = 0;
 };

@@ -1844,7 +1844,9 @@ namespace {
 // X -> X^gal[i] (lin_mac_body's baby-step form), and goes into both outputs' accumulators before the
 // next term is touched: each ext and key word is loaded once.  8 u64 accumulators, no LDS.
 // ND as k_lin_mac's: the digit loop unrolled so a term's 2 * ND key loads and ND gathers are in flight together
-template <int ND>
+// FILL (aesfhe_rot_pt_affine): output j's fill plaintext, one coalesced word per thread of a Q row, joins its c0
+// accumulator before the final reduction -- the affine sum in the same pass, no launch of its own
+template <int ND, bool FILL>
 __global__ void __launch_bounds__(kBlock) k_rot_mask_mac(RotMacArgs m, int nl, int ne, LimbMap map, const PrimeConst* pc, int logn, int xcd) {
     int t = blockIdx.y, bx = blockIdx.x;
     if (xcd) xcd_rows(logn - 8, ne, bx, t);
@@ -1898,6 +1900,7 @@ __global__ void __launch_bounds__(kBlock) k_rot_mask_mac(RotMacArgs m, int nl, i
     for (int j = 0; j < kRotMacOut; ++j) {
         if (j >= m.n_out) continue;
         if (qrow) {
+            if (FILL && m.fill[j]) a0[j] += m.fill[j][at];  // < q: fits beside the 8 products (see above)
             m.out0[j][at] = reduce64(a0[j], P.q, P.mu, P.r32);
             m.out1[j][at] = reduce64(a1[j], P.q, P.mu, P.r32);
         }
@@ -1922,17 +1925,29 @@ void launch_rot_mask_mac(hipStream_t st, const DevTables& T, const RotMacArgs& m
             if (m.pt[j][i]) rows += m.key[i] ? ne : nl;
     }
     if (any_key) rows += (double)m.nd * ne;
-    for (int j = 0; j < m.n_out; ++j) rows += 2.0 * nl + (m.outp[j] ? 2.0 * ne : 0.0);
+    bool any_fill = false;
+    for (int j = 0; j < m.n_out; ++j) {
+        rows += 2.0 * nl + (m.outp[j] ? 2.0 * ne : 0.0);
+        if (m.fill[j]) rows += nl, any_fill = true;
+    }
     const double bytes = words(rows * (1u << T.logn));
     const dim3 g = ew_grid(T.logn, ne), b(kBlock);
     const int xcd = xcd_rows_on();
-    switch (m.nd) {  // the digit counts of the AES levels (3..9 limbs); others take the run-time loop
-#define ROT_MAC_ND(D) \
-    case D: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<D>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd); break;
-        ROT_MAC_ND(1) ROT_MAC_ND(2) ROT_MAC_ND(3) ROT_MAC_ND(4)
-#undef ROT_MAC_ND
-        default: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<0>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd);
+    // the digit counts of the AES levels (3..9 limbs); others take the run-time loop
+#define ROT_MAC_ND(D, F) \
+    case D: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<D, F>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd); break;
+#define ROT_MAC_LAUNCH(F) \
+    switch (m.nd) { \
+        ROT_MAC_ND(1, F) ROT_MAC_ND(2, F) ROT_MAC_ND(3, F) ROT_MAC_ND(4, F) \
+        default: prof_launch(KID_KEY_INNER, bytes, k_rot_mask_mac<0, F>, g, b, 0, st, m, nl, ne, map, T.pc, T.logn, xcd); \
     }
+    if (any_fill) {
+        ROT_MAC_LAUNCH(true)
+    } else {  // aesfhe_rot_pt_sum, and an affine call without fills: the kernel without the fill read
+        ROT_MAC_LAUNCH(false)
+    }
+#undef ROT_MAC_LAUNCH
+#undef ROT_MAC_ND
 }
 
 void launch_mac(hipStream_t st, const DevTables& T, u32* out, const MacTerms& m, size_t xs, size_t os, int rows, int npoly, LimbMap map) {

@@ -167,6 +167,20 @@ class EngineContext:
             out.append(acc if acc is not None else self.engine.multiply(ct, 0.0))
         return out
 
+    def rot_pt_affine(self, ct, steps, pts_per_output, fills):
+        """[sum_i pts[i] * rotate(ct, steps[i]) + fill for pts, fill in zip(pts_per_output, fills)] (fill None: the
+        plain sum): one engine call with the fill added inside the sum's kernel at the product scale
+        (include/aesfhe.h aesfhe_rot_pt_affine).  With an engine that lacks the entry point:
+        rot_pt_sum, then the fill added as a plaintext (the engine's add settles the rescale the sum owes first)"""
+        fills = list(fills)
+        if len(fills) != len(pts_per_output):
+            raise ValueError("rot_pt_affine: one fill (or None) per output")
+        fused = getattr(self.engine, "rot_pt_affine", None)
+        if fused is not None:
+            return fused(ct, steps, pts_per_output, fills)
+        out = EngineContext.rot_pt_sum(self, ct, steps, pts_per_output)
+        return [o if f is None else self.engine.add(o, f) for o, f in zip(out, fills)]
+
     def rotate(self, ct, steps: int):
         """np.roll(slots, steps) semantics."""
         return self.engine.rotate(ct, self.rotation_key, steps)

@@ -1,0 +1,243 @@
+"""Homomorphic AES-128 key schedule: the 11 round keys from ONE encrypted 16-byte key.
+
+One schedule step maps the words w0..w3 of round key r - 1 to
+    w_j' = w0 ^ ... ^ w_j ^ SubWord(RotWord(w3)) ^ rcon_r,   j = 0..3
+(FIPS-197 §5.2 unrolled: w_j' = w_{j-1}' ^ w_j).  Written with no step serial over the words:
+
+  prefix   x' = x ^ rcon_r (a PUBLIC operand on row 0 of word 0: AddRoundKey.public), then the prefix XOR over the
+           words in two doubling steps, y = x' ^ shift1(x'), P = y ^ shift2(y); shift_k moves every word k words up
+           and fills the vacated words with the codeword of nibble 0 (1 + 0j in the Zeta16 code, not 0).  Every
+           prefix holds rcon_r exactly once.
+  sub      SubBytes of the whole key (byte-wise, so it runs before the broadcast and independently of the prefix
+           branch), then ONE masked rotation sum that rotates word 3 by one byte and copies it into all four words.
+  out      XOR4 of the two branches.  A renorm follows every LUT step, as everywhere else in the pipeline.
+
+Every move is a rotation by a multiple of layout.unit under SlotLayout.cell_mask masks, built the way
+shift_columns.apply_terms builds its terms, and evaluated by ctx.rot_pt_affine (the engine's aesfhe_rot_pt_affine:
+the masked rotation sum plus a fill plaintext, one kernel).  Words are the columns of the FIPS byte order: with
+byte_order "plain" slot position r + 4c holds row r of word c, with "transposed" (AESPipeline(fips=True)) it holds
+row c of word r; SchedulePlan takes the order and produces the offsets and masks of both.  The state being
+16-unit-periodic (ShiftRows' rotations rely on the same), offsets are taken mod 16 positions: the broadcast's 8
+(row, word) offset classes are 4 rotations.
+
+``schedule_step_slots`` is the numpy model of the plan on nibble slot vectors (no engine); ``KeyExpansion`` runs it on
+an AESPipeline's own modules; ``EncryptedRoundKeys`` is what every pipeline method takes in place of clear round keys.
+No reference counterpart (REF/test/test_aes_pipeline_roundtrip.py:20-48 expands the key in clear).
+"""
+from typing import Any, Dict, List, Optional, Tuple
+
+import numpy as np
+
+from aes_keyschedule import RCON, SBOX
+from state_encoder import check_layout, tag_layout
+from utils import NEED_SR_ARK, NEED_XOR
+
+
+def word_pos(row: int, word: int, byte_order: str = "plain") -> int:
+    """slot position (in units) of row `row` of word `word`"""
+    if byte_order == "plain":
+        return row + 4 * word
+    if byte_order == "transposed":
+        return word + 4 * row
+    raise ValueError(f"byte_order must be 'plain' or 'transposed', got {byte_order!r}")
+
+
+def _centered(d: int) -> int:
+    """the offset d mod 16 positions in -7 .. 8 (the state is 16-unit-periodic)"""
+    return (d + 7) % 16 - 7
+
+
+class MaskedSum:
+    """out = sum_k masks[k] * np.roll(x, steps[k]) + fill: the masks are 0 / 1 and disjoint, fill is 1 on the slots
+    no mask covers (the codeword of nibble 0) and None when the masks cover every slot"""
+
+    def __init__(self, steps: List[int], masks: List[np.ndarray]):
+        self.steps, self.masks = steps, masks
+        rest = 1.0 - np.sum(masks, axis=0)
+        self.fill = rest if rest.any() else None
+
+    def apply_slots(self, x: np.ndarray) -> np.ndarray:
+        """the sum on a slot vector of nibbles: masked slots take the rolled nibble, filled slots nibble 0"""
+        out = np.zeros_like(x)
+        for s, m in zip(self.steps, self.masks):
+            sel = m > 0.5
+            out[sel] = np.roll(x, s)[sel]
+        return out
+
+    def apply_values(self, z: np.ndarray) -> np.ndarray:
+        """the sum on a slot vector of codewords, as the engine evaluates it"""
+        out = sum(m * np.roll(z, s) for s, m in zip(self.steps, self.masks))
+        return out if self.fill is None else out + self.fill
+
+
+class SchedulePlan:
+    """the masked rotation sums of one schedule step for a slot layout and byte order (module docstring):
+    shift[1], shift[2] (the prefix doubling steps) and broadcast (RotWord of word 3 into every word)"""
+
+    def __init__(self, layout, byte_order: Optional[str] = None):
+        self.layout = layout
+        self.byte_order = byte_order if byte_order is not None else getattr(layout, "byte_order", "plain")
+        word_pos(0, 0, self.byte_order)  # validates the order
+        self.shift = {k: self._shift_terms(k) for k in (1, 2)}
+        self.broadcast = self._broadcast_terms()
+
+    def _cell(self, pos: int) -> np.ndarray:
+        return self.layout.cell_mask(pos % 4, pos // 4).real
+
+    def _sum(self, by_offset: Dict[int, np.ndarray]) -> MaskedSum:
+        offs = sorted(by_offset)
+        # np.roll(x, s)[j] = x[j - s]: the byte d units above
+        return MaskedSum([-d * self.layout.unit for d in offs], [by_offset[d] for d in offs])
+
+    def _shift_terms(self, k: int) -> MaskedSum:
+        """word j >= k takes word j - k; the words below k (and the slots that hold no state) take the fill"""
+        by: Dict[int, np.ndarray] = {}
+        for j in range(k, 4):
+            for row in range(4):
+                dst = word_pos(row, j, self.byte_order)
+                d = _centered(word_pos(row, j - k, self.byte_order) - dst)
+                by[d] = by.get(d, np.zeros(self.layout.sc)) + self._cell(dst)
+        return self._sum(by)
+
+    def _broadcast_terms(self) -> MaskedSum:
+        """row rho of every word takes row (rho + 1) % 4 of word 3"""
+        by: Dict[int, np.ndarray] = {}
+        for j in range(4):
+            for row in range(4):
+                dst = word_pos(row, j, self.byte_order)
+                d = _centered(word_pos((row + 1) % 4, 3, self.byte_order) - dst)
+                by[d] = by.get(d, np.zeros(self.layout.sc)) + self._cell(dst)
+        return self._sum(by)
+
+    def sums(self) -> Dict[str, MaskedSum]:
+        return {"shift1": self.shift[1], "shift2": self.shift[2], "broadcast": self.broadcast}
+
+    def used(self) -> np.ndarray:
+        """1 on the slots that hold a state byte"""
+        return np.sum([self._cell(p) for p in range(16)], axis=0)
+
+    def rcon_slots(self, r: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(hi, lo) nibble slot vectors of round r's constant: RCON[r - 1] on row 0 of word 0 of every state, nibble
+        0 elsewhere -- the public operand of AddRoundKey.public"""
+        if not 1 <= r <= 10:
+            raise ValueError(f"AES-128 schedule rounds are 1..10, got {r}")
+        sel = self._cell(word_pos(0, 0, self.byte_order)) > 0.5
+        hi, lo = np.zeros(self.layout.sc, np.uint8), np.zeros(self.layout.sc, np.uint8)
+        hi[sel], lo[sel] = int(RCON[r - 1]) >> 4, int(RCON[r - 1]) & 0x0F
+        return hi, lo
+
+
+def schedule_step_slots(x_slots, r: int, layout, byte_order: Optional[str] = None, stages: Optional[dict] = None):
+    """round key r from round key r - 1 on nibble slot vectors: x_slots = (hi, lo) uint8 arrays as
+    StateEncoder.nibble_slots lays them out; exactly SchedulePlan's rolls, masks and fills, XOR and the S-box in
+    clear.  stages (a dict): filled with the (hi, lo) vectors of prefix, sub, rot and out"""
+    plan = SchedulePlan(layout, byte_order)
+    hi, lo = (np.asarray(v, np.uint8) for v in x_slots)
+    rc = plan.rcon_slots(r)
+    pre = []
+    for v, c in zip((hi, lo), rc):
+        x = v ^ c
+        y = x ^ plan.shift[1].apply_slots(x)
+        pre.append(y ^ plan.shift[2].apply_slots(y))
+    s = SBOX[(hi.astype(np.uint8) << 4) | lo]  # on every slot, the ones that hold no state included
+    sub = (s >> 4, s & 0x0F)
+    rot = tuple(plan.broadcast.apply_slots(v) for v in sub)
+    out = tuple(p ^ b for p, b in zip(pre, rot))
+    if stages is not None:
+        stages.update(prefix=tuple(pre), sub=sub, rot=rot, out=out)
+    return out
+
+
+def schedule_step_bytes(key: np.ndarray, r: int) -> Dict[str, np.ndarray]:
+    """the byte model of the debug stages of round r for a (16,) or (B, 16) round key r - 1 in FIPS byte order:
+    prefix (word j = w0 ^ ... ^ w_j, rcon_r in row 0), sub (SubBytes of the key), rot (SubWord(RotWord(w3)) in
+    every word) and out (round key r)"""
+    k = np.asarray(key, np.uint8)
+    w = k.reshape(*k.shape[:-1], 4, 4).copy()  # [..., word, row]
+    sub = SBOX[k]
+    rot = np.repeat(np.roll(SBOX[w[..., 3, :]], -1, axis=-1)[..., None, :], 4, axis=-2)
+    w[..., 0, 0] ^= RCON[r - 1]
+    pre = np.bitwise_xor.accumulate(w, axis=-2)
+    return {"prefix": pre.reshape(k.shape), "sub": sub, "rot": rot.reshape(k.shape), "out": (pre ^ rot).reshape(k.shape)}
+
+
+class EncryptedRoundKeys:
+    """11 layout-tagged (hi, lo) pairs, the AES-128 round keys under FHE, with the caches a pipeline keeps per key
+    schedule: `packed` (rounds 1..9 in the packed form, filled on first use) and `key_basis` (round -> the packed
+    key's dropped form and XOR4 basis, AESPipeline._ark_packed).  Every AESPipeline method that takes round keys
+    takes one of these; the server then never holds a key byte in clear."""
+
+    def __init__(self, pairs, layout):
+        pairs = [tuple(p) for p in pairs]
+        if len(pairs) != 11 or any(len(p) != 2 for p in pairs):
+            raise ValueError("AES-128 takes 11 round keys, each a (hi, lo) ciphertext pair")
+        for p in pairs:
+            check_layout(layout, *p)
+            tag_layout(layout, *p)
+        self.pairs, self.layout = pairs, layout
+        self.packed: List[Any] = [None] * 11
+        self.key_basis: Dict[int, Dict[str, Any]] = {}
+
+    @classmethod
+    def from_pairs(cls, pairs, layout) -> "EncryptedRoundKeys":
+        """round keys the client expanded and encrypted itself (StateEncoder.encode of each, in `layout`)"""
+        return cls(pairs, layout)
+
+    def __len__(self) -> int:
+        return len(self.pairs)
+
+    def __getitem__(self, r: int):
+        return self.pairs[r]
+
+
+class KeyExpansion:
+    """the schedule on an AESPipeline's own modules (xor4 through ark / ark.public, sub, _renorm_pair, _floor,
+    encoder.layout), so it follows use_hard_renorm_between_steps, true_fhe, states and fips.  Per round: 4 XOR4
+    pairs (one of them public), one SubBytes, 6 masked rotation sums, 5 renorms."""
+
+    def __init__(self, pipe):
+        if pipe.pairs > 1:
+            raise ValueError("KeyExpansion: multi-pair batches (pairs > 1) take no public operands")
+        ctx = pipe.ctx
+        if getattr(ctx, "rot_pt_affine", None) is None:
+            raise TypeError("KeyExpansion needs a context with rot_pt_affine (engine_context.EngineContext)")
+        self.pipe, self.ctx = pipe, ctx
+        self.layout = pipe.encoder.layout
+        self.plan = SchedulePlan(self.layout)
+        self._pts = {name: ([ctx.encode(m) for m in s.masks], None if s.fill is None else ctx.encode(s.fill))
+                     for name, s in self.plan.sums().items()}
+
+    def _move(self, name: str, ct_hi, ct_lo):
+        """one masked rotation sum of the plan on both halves (one level)"""
+        steps = self.plan.sums()[name].steps
+        masks, fill = self._pts[name]
+        return tuple(self.ctx.rot_pt_affine(c, steps, [masks], [fill])[0] for c in (ct_hi, ct_lo))
+
+    def step(self, key, r: int, debug=None):
+        """round key r (a clean pair at the level the last renorm hands out) from round key r - 1"""
+        p = self.pipe
+        fl = p._floor()
+        x = p.ark.public(*key, *self.plan.rcon_slots(r), out_level=fl)
+        x = p._renorm_pair(*x, level=NEED_SR_ARK)  # a masked rotation sum, then an XOR4
+        y = p._renorm_pair(*p.ark(*x, *self._move("shift1", *x), out_level=fl), level=NEED_SR_ARK)
+        pre = p._renorm_pair(*p.ark(*y, *self._move("shift2", *y), out_level=fl), level=NEED_XOR)
+        p._log_pair(debug, f"ks.r{r}.prefix", *pre)
+        sub = p._sub_renorm(key, level=NEED_SR_ARK)
+        p._log_pair(debug, f"ks.r{r}.sub", *sub)
+        rot = self._move("broadcast", *sub)
+        p._log_pair(debug, f"ks.r{r}.rot", *rot)
+        out = tag_layout(self.layout, *p._renorm_pair(*p.ark(*pre, *rot, out_level=fl)))
+        p._log_pair(debug, f"ks.r{r}.out", *out)
+        return out
+
+    def expand(self, key_hi, key_lo, debug: Optional[Dict[str, Any]] = None) -> EncryptedRoundKeys:
+        """the 11 round keys of the encrypted key (hi, lo) (AESPipeline.encrypt_key; with states > 1 every state
+        holds its own key and gets its own schedule).  Round key 0 is the input, renormalised; every key sits at
+        the level the pipeline's renorm hands out with no target (the fresh level in the secret-key renorm mode)."""
+        check_layout(self.layout, key_hi, key_lo)
+        if debug is not None:
+            debug.clear()
+        keys = [tag_layout(self.layout, *self.pipe._renorm_pair(key_hi, key_lo))]
+        for r in range(1, 11):
+            keys.append(self.step(keys[-1], r, debug))
+        return EncryptedRoundKeys(keys, self.layout)

@@ -49,7 +49,7 @@ EXPORTED = [
     "aesfhe_debug_mono_pack", "aesfhe_debug_mono_split", "aesfhe_alg_bytes", "aesfhe_stack", "aesfhe_unstack", "aesfhe_members",
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
     "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
-    "aesfhe_rot_pt_sum",
+    "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -98,6 +98,7 @@ def load_library(path: Optional[Path] = None):
         "aesfhe_mul_pt_sum": [vp, c_int, _Hp, _Hp, _Hp], "aesfhe_renorm_pool": [vp, c_int], "aesfhe_set_stack_pack": [vp, c_int],
         "aesfhe_rotate_hoisted": [vp, _H, c_int, ctypes.POINTER(c_int), _Hp],
         "aesfhe_rot_pt_sum": [vp, _H, c_int, ctypes.POINTER(c_int), c_int, _Hp, _Hp],
+        "aesfhe_rot_pt_affine": [vp, _H, c_int, ctypes.POINTER(c_int), c_int, _Hp, _Hp, _Hp],
         "aesfhe_to_ntt": [vp, _H, _Hp], "aesfhe_to_intt": [vp, _H, _Hp], "aesfhe_bootstrap": [vp, _H, _Hp],
         "aesfhe_renorm_pair": [vp, _H, _H, _Hp, _Hp],
         "aesfhe_bootstrap_pair": [vp, _H, _H, _Hp, _Hp],
@@ -735,6 +736,24 @@ class Engine:
         pts = (ctypes.c_uint64 * max(n * n_out, 1))(*[0 if q is None else q.handle for p in pts_per_output for q in p])
         out = (ctypes.c_uint64 * max(n_out, 1))()
         self._ctx.check(self._lib.aesfhe_rot_pt_sum(self._ctx.ptr, self._settled(ct).handle, n, st, n_out, pts, out))
+        return [Ciphertext(self._ctx, out[j]) for j in range(n_out)]
+
+    def rot_pt_affine(self, ct, steps, pts_per_output, fills) -> List[Ciphertext]:
+        """rot_pt_sum plus one fill plaintext per output (None: no fill), added inside the sum's kernel at the
+        product scale (aesfhe_rot_pt_affine, DESIGN.md §3.19): [sum_i pts[i] * rotate(ct, steps[i]) + fill];
+        with every fill None the outputs are rot_pt_sum's bit for bit"""
+        steps = [int(x) for x in steps]
+        n, n_out = len(steps), len(pts_per_output)
+        if any(len(p) != n for p in pts_per_output):
+            raise ValueError("rot_pt_affine: every output takes one plaintext (or None) per step")
+        if len(fills) != n_out:
+            raise ValueError("rot_pt_affine: one fill (or None) per output")
+        self._ensure_keys()
+        st = (ctypes.c_int * max(n, 1))(*steps)
+        pts = (ctypes.c_uint64 * max(n * n_out, 1))(*[0 if q is None else q.handle for p in pts_per_output for q in p])
+        fl = (ctypes.c_uint64 * max(n_out, 1))(*[0 if f is None else f.handle for f in fills])
+        out = (ctypes.c_uint64 * max(n_out, 1))()
+        self._ctx.check(self._lib.aesfhe_rot_pt_affine(self._ctx.ptr, self._settled(ct).handle, n, st, n_out, pts, fl, out))
         return [Ciphertext(self._ctx, out[j]) for j in range(n_out)]
 
     def galois_multi(self, items) -> List[Ciphertext]:

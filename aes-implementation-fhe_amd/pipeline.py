@@ -44,6 +44,13 @@ ShiftColumns modules plus a byte transpose wherever clear bytes enter or leave (
 byte_order="transposed": states, round keys, counter blocks, public AES ciphertext bytes, decode and the debug
 snapshots).  Its pairs are tagged transposed and refused by a plain pipeline (check_layout).  ``fuse_sub_ark``,
 ``fuse_sr_mc`` and ``pairs`` > 1 are not available with it (ValueError).
+
+Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
+11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
+pairs the server never saw in clear: ``expand_key(*encrypt_key(master))`` derives them homomorphically from ONE
+encrypted 16-byte key, ``EncryptedRoundKeys.from_pairs`` wraps keys the client expanded itself.  Their packed forms are
+built homomorphically and cached on the object.  Refused (ValueError): keys of another layout or byte order,
+``pairs`` > 1, ``fuse_sub_ark`` (its fused keys permute clear key bytes).
 """
 from __future__ import annotations
 
@@ -54,6 +61,7 @@ import numpy as np
 
 from add_round_key import AddRoundKey
 from invmixcolumns_fhe import InvMixColumnsFHE
+from key_expansion import EncryptedRoundKeys, KeyExpansion
 from inv_shiftrows import InvShiftRows
 from mixcol_final import MixColFinal
 from shift_rows import ShiftRows
@@ -212,7 +220,39 @@ class AESPipeline:
         assert key_bytes.shape == ((16,) if self.states == 1 else (self.states, 16))
         return self.encoder.encode(key_bytes)
 
-    def _prepare_round_keys(self, round_keys: List[np.ndarray]):
+    def encrypt_key(self, master: np.ndarray):
+        """client side: the (hi, lo) encryption of a (16,) AES-128 key, or of a (states, 16) array with one key
+        per state (a (16,) key is shared by all states, as _encode_key broadcasts it) -- expand_key's input"""
+        return self._encode_key(master)
+
+    def expand_key(self, key_hi, key_lo, debug: Dict[str, Any] | None = None) -> EncryptedRoundKeys:
+        """the 11 round keys of an encrypted AES-128 key, derived homomorphically (key_expansion.KeyExpansion,
+        DESIGN.md §3.19): what encrypt / decrypt / encrypt_public / ctr_keystream / transcipher take as
+        round_keys in place of clear bytes.  A debug dict gets the stages ks.r{r}.{prefix,sub,rot,out}."""
+        if getattr(self, "_key_expansion", None) is None:
+            self._key_expansion = KeyExpansion(self)
+        return self._key_expansion.expand(key_hi, key_lo, debug)
+
+    def _check_encrypted_keys(self, erk: EncryptedRoundKeys) -> None:
+        if self.pairs > 1:
+            raise ValueError("encrypted round keys: multi-pair batches (pairs > 1) are not supported")
+        if self.fuse_sub_ark:
+            raise ValueError("encrypted round keys do not combine with fuse_sub_ark (its fused keys permute clear key bytes)")
+        for pr in erk.pairs:  # tagged with erk.layout: another slot layout or byte order is refused here
+            check_layout(self.layout, *pr)
+        if not self.layout.same(erk.layout):  # ciphertexts that carry no tag (the CPU oracle's)
+            raise ValueError("encrypted round keys were made for another slot layout or byte order")
+
+    def _encrypted_keys(self) -> EncryptedRoundKeys | None:
+        """the EncryptedRoundKeys of the last _prepare_round_keys, None after clear round keys"""
+        return self._rk_tag if isinstance(self._rk_tag, EncryptedRoundKeys) else None
+
+    def _prepare_round_keys(self, round_keys):
+        if isinstance(round_keys, EncryptedRoundKeys):  # already ciphertexts: cached by the object, nothing encoded
+            self._check_encrypted_keys(round_keys)
+            if self._rk_tag is not round_keys:
+                self._rk_cache, self._rk_raw, self._rk_tag = round_keys.pairs, None, round_keys
+            return self._rk_cache
         tag = b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
         if self._rk_cache is None or self._rk_tag != tag:  # encrypted round keys are reused across calls
             self._rk_cache = [self._encode_key(np.asarray(k, dtype=np.uint8)) for k in round_keys]
@@ -229,11 +269,12 @@ class AESPipeline:
         key = self._packed_round_key(r)
         if not _KEY_BASIS:
             return self.xor4.apply(x, key, out_level=self._floor())
-        if self._kb_tag != self._rk_tag:
+        erk = self._encrypted_keys()
+        if erk is None and self._kb_tag != self._rk_tag:
             self._kb_cache, self._kb_tag = {}, self._rk_tag
         if not self._xor4_keep_b():  # an XOR4 without basis sharing (a caller-supplied LUT object)
             return self.xor4.apply(x, key, out_level=self._floor())
-        kb = self._kb_cache.setdefault(r, {})
+        kb = (self._kb_cache if erk is None else erk.key_basis).setdefault(r, {})
         if defer_conj and FOLDS.conj and self._xor4_defer_ok():
             return self.xor4.apply(x, key, out_level=self._floor(), keep_b=kb, defer_conj=True)
         return self.xor4.apply(x, key, out_level=self._floor(), keep_b=kb)
@@ -310,7 +351,16 @@ class AESPipeline:
         return self._keep_b_ok
 
     def _packed_round_key(self, r: int):
-        """round key r encrypted in the packed form (after _prepare_round_keys of the same keys)"""
+        """round key r encrypted in the packed form (after _prepare_round_keys of the same keys); an encrypted
+        key schedule is packed homomorphically, once, and the packed form kept on the EncryptedRoundKeys"""
+        erk = self._encrypted_keys()
+        if erk is not None:
+            if erk.packed[r] is None:
+                if self.use_hard_renorm_between_steps and not self.true_fhe:
+                    erk.packed[r] = self.encoder.renorm_pack(*erk.pairs[r])  # the packing renorm where it applies
+                else:
+                    erk.packed[r] = self.encoder.pack(*erk.pairs[r])
+            return erk.packed[r]
         if self._pk_cache is None or self._pk_tag != self._rk_tag:
             self._pk_cache, self._pk_tag = [None] * len(self._rk_cache), self._rk_tag
         if self._pk_cache[r] is None:
@@ -444,7 +494,7 @@ class AESPipeline:
         self._log_pair(debug, f"enc.r{r}.ark.renorm", *ct)
         return ct
 
-    def encrypt(self, state: np.ndarray, round_keys: List[np.ndarray], debug: Dict[str, Any] | None = None):
+    def encrypt(self, state: np.ndarray, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
         if debug is not None:
             debug.clear()
         ct = self.encoder.encode(state)
@@ -492,7 +542,7 @@ class AESPipeline:
         if self.pairs > 1:
             raise ValueError(f"{what}: multi-pair batches (pairs > 1) take no public operands")
 
-    def encrypt_public(self, state: np.ndarray, round_keys: List[np.ndarray], debug: Dict[str, Any] | None = None):
+    def encrypt_public(self, state: np.ndarray, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
         """encrypt of a PUBLIC state (a counter block): round 0 XORs the encrypted round key 0 with the
         state's nibbles in clear (AddRoundKey.public; the state is never encrypted), everything after it is
         encrypt's own path.  Same bytes and the same layout-tagged pair as encrypt(state, round_keys); the
@@ -504,7 +554,7 @@ class AESPipeline:
         ct = self.ark.public(*rk[0], *self.encoder.nibble_slots(state), out_level=self._floor())
         return self._encrypt_tail(ct, rk, round_keys, debug)
 
-    def ctr_keystream(self, nonce12, counter0: int, round_keys: List[np.ndarray]):
+    def ctr_keystream(self, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys):
         """the encrypted keystream blocks of counters counter0 .. counter0 + states - 1 (mod 2^32) under the
         encrypted key: encrypt_public of ctr_mode.counter_blocks, one block per state"""
         from ctr_mode import counter_blocks
@@ -512,7 +562,7 @@ class AESPipeline:
         blocks = counter_blocks(nonce12, counter0, self.states)
         return self.encrypt_public(blocks[0] if self.states == 1 else blocks, round_keys)
 
-    def transcipher(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray]):
+    def transcipher(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys):
         """AES-CTR transciphering: aes_ct ((states, 16), or (16,) for one state) holds the client's
         m ^ keystream under this pipeline's cipher in counter mode (ctr_mode.ctr_xor); returns a clean
         layout-tagged pair that encoder.decode reads as m, at the level encrypt's output has.  The keystream
@@ -525,7 +575,7 @@ class AESPipeline:
         return tag_layout(self.layout, *self._renorm_pair(*ct))
 
     # ---------------------------------------------------------------- decrypt
-    def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray], debug: Dict[str, Any] | None = None):
+    def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
         check_layout(self.layout, ct_hi, ct_lo)  # a pair from another layout would decrypt to wrong bytes
         if debug is not None:
             debug.clear()

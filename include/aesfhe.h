@@ -240,6 +240,17 @@ int aesfhe_rotate_hoisted(aesfhe_ctx* ctx, aesfhe_handle ct, int n, const int* s
  * 3-polynomial inputs are refused. */
 int aesfhe_rot_pt_sum(aesfhe_ctx* ctx, aesfhe_handle ct, int n, const int* steps, int n_out, const aesfhe_handle* pts,
                       aesfhe_handle* out);
+/* The affine form of aesfhe_rot_pt_sum (the homomorphic AES key schedule, key_expansion.py):
+ *   out[j] = sum_i pts[j*n + i] * rotate(ct, steps[i]) + fills[j],  j < n_out;
+ * fills holds n_out plaintext handles, 0 = no fill for that output.  Slots no mask covers come out as the
+ * fill's value instead of 0 (which is no Zeta16 codeword).  aesfhe_rot_pt_sum's contract in every other
+ * respect: canonical input, one ModUp, one kernel, one ModDown per output, the level's own special basis with
+ * aesfhe_set_low_p on or off, outputs owing their rescale, the same refusals.  A fill is encoded at the
+ * product scale (the raw scale of an output that owes its rescale) over the output's limbs, cached on its
+ * handle per (level, special-prime count) and released with it, and added inside the sum's kernel.  With
+ * every fill 0 the outputs equal aesfhe_rot_pt_sum's bit for bit. */
+int aesfhe_rot_pt_affine(aesfhe_ctx* ctx, aesfhe_handle ct, int n, const int* steps, int n_out, const aesfhe_handle* pts,
+                         const aesfhe_handle* fills, aesfhe_handle* out);
 /* engine.make_power_basis(ct, degree, relinearization_key), REF/engine_context.py:100-101;
  * out[k-1] = ct^k, k = 1..degree */
 int aesfhe_power_basis(aesfhe_ctx* ctx, aesfhe_handle ct, int degree, aesfhe_handle* out);
