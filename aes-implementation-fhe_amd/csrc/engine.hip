@@ -5095,6 +5095,12 @@ public:
         export_dev(d_pk_, (size_t)2 * hp_.n_q * hp_.n, out);
     }
     void export_ksk(u64 g, u32* out) { export_dev(ksk(g), ksk_words(g), out); }
+    // the key a key switch at `level` uses (ksk_at): the reduced level's own [2][nl + np][N] key, else the full key
+    void export_ksk_at(u64 g, int level, u32* out) {
+        if (level < 0 || level > hp_.L) throw std::runtime_error("export_ksk_at: bad level");
+        const u32* key = ksk_at(g, level);
+        export_dev(key, low_level(level) ? (size_t)2 * kb(level).nkey * hp_.n : ksk_words(g), out);
+    }
     void debug_ntt(u32* data, int rows, int first_prime, int inverse) {
         u32* d = tmp(rows);
         HIP_OK(hipMemcpyAsync(d, data, sizeof(u32) * rows * hp_.n, hipMemcpyHostToDevice, S()));
@@ -6066,6 +6072,10 @@ int aesfhe_export_pk(aesfhe_ctx* ctx, uint32_t* out) {
 }
 int aesfhe_export_ksk(aesfhe_ctx* ctx, uint64_t g, uint32_t* out) {
     API_BEGIN ctx->eng->export_ksk(g, out);
+    API_END
+}
+int aesfhe_export_ksk_at(aesfhe_ctx* ctx, uint64_t g, int level, uint32_t* out) {
+    API_BEGIN ctx->eng->export_ksk_at(g, level, out);
     API_END
 }
 int aesfhe_debug_ntt(aesfhe_ctx* ctx, uint32_t* data, int rows, int first_prime, int inverse) {

@@ -49,7 +49,7 @@ EXPORTED = [
     "aesfhe_debug_mono_pack", "aesfhe_debug_mono_split", "aesfhe_alg_bytes", "aesfhe_stack", "aesfhe_unstack", "aesfhe_members",
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
     "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
-    "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine",
+    "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine", "aesfhe_export_ksk_at",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -107,6 +107,7 @@ def load_library(path: Optional[Path] = None):
         "aesfhe_export": [vp, _H, _up, ctypes.c_uint64], "aesfhe_import": [vp, c_int, c_int, _up, _Hp],
         "aesfhe_export_secret": [vp, _up], "aesfhe_export_pk": [vp, _up],
         "aesfhe_export_ksk": [vp, ctypes.c_uint64, _up],
+        "aesfhe_export_ksk_at": [vp, ctypes.c_uint64, c_int, _up],
         "aesfhe_debug_ntt": [vp, _up, c_int, c_int, c_int],
         "aesfhe_debug_keyswitch": [vp, c_int, ctypes.c_uint64, _up, _up],
         "aesfhe_counters": [vp, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS"), c_int],
@@ -1128,6 +1129,18 @@ class Engine:
         else:
             out = np.zeros((self.dnum, 2, self.n_ks + self.n_p, self.n), np.uint32)
         self._ctx.check(self._lib.aesfhe_export_ksk(self._ctx.ptr, int(galois), out))
+        return out
+
+    def export_ksk_at(self, galois: int, level: int) -> np.ndarray:
+        """the key a key switch of `galois` at `level` runs with (aesfhe_export_ksk_at): on a reduced level
+        (set_low_p) that level's own single-digit key [2][nl + np][N], else the full key as export_ksk"""
+        self._ensure_keys()
+        np_l = self.ks_special_primes(level)
+        if np_l < self.n_p:
+            out = np.zeros((2, self.nl(level) + np_l, self.n), np.uint32)
+        else:
+            out = np.zeros((self.dnum, 2, self.n_ks + self.n_p, self.n), np.uint32)
+        self._ctx.check(self._lib.aesfhe_export_ksk_at(self._ctx.ptr, int(galois), int(level), out))
         return out
 
     def debug_ntt(self, rows: np.ndarray, first_prime: int, inverse: bool = False) -> np.ndarray:

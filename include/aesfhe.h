@@ -392,6 +392,10 @@ int aesfhe_import(aesfhe_ctx* ctx, int level, int npoly, const uint32_t* data, a
 int aesfhe_export_secret(aesfhe_ctx* ctx, uint32_t* out);
 int aesfhe_export_pk(aesfhe_ctx* ctx, uint32_t* out);
 int aesfhe_export_ksk(aesfhe_ctx* ctx, uint64_t galois, uint32_t* out);
+/* the key a key switch of galois g at `level` runs with: on a reduced level (aesfhe_set_low_p, nl = level's limbs
+ * < alpha) that level's own single-digit key, [2][nl + np][N] with np = nl + 1 (Q limbs 0..nl-1, then the first np
+ * special primes); on any other level the full key, as aesfhe_export_ksk */
+int aesfhe_export_ksk_at(aesfhe_ctx* ctx, uint64_t galois, int level, uint32_t* out);
 /* forward / inverse NTT of host rows whose limb l is prime first_prime + l */
 int aesfhe_debug_ntt(aesfhe_ctx* ctx, uint32_t* data, int rows, int first_prime, int inverse);
 /* key switch of a raw polynomial d (level+2 limbs, NTT) with the key of galois g */

@@ -62,6 +62,8 @@ def lib():
         "orc_secret_ntt": (None, [vp, u32p]),
         "orc_gen_pk": (None, [vp, u32p]),
         "orc_gen_ksk": (None, [vp, c_u64, u32p]),
+        "orc_gen_ksk_low": (c_int, [vp, c_u64, c_int, u32p]),
+        "orc_keyswitch_low": (c_int, [vp, c_int, c_int, u32p, u32p, u32p]),
         "orc_rescale": (None, [vp, c_int, c_int, u32p, u32p]),
         "orc_keyswitch": (None, [vp, c_int, u32p, u32p, u32p]),
         "orc_tensor": (None, [vp, c_int, u32p, u32p, u32p]),
@@ -164,6 +166,28 @@ class OracleParams:
     def gen_ksk(self, galois: int) -> np.ndarray:
         out = np.zeros((self.dnum, 2, self.n_ks + self.n_p, self.n), np.uint32)
         self._L.orc_gen_ksk(self.h, galois, out)
+        return out
+
+    def gen_ksk_low(self, galois: int, level: int) -> np.ndarray:
+        """the reduced-basis key of a level of nl < alpha limbs: [2][nl + np][N], np = nl + 1,
+        rows = Q limbs 0..nl-1 then special primes 0..np-1"""
+        nl = self.nl(level)
+        out = np.zeros((2, 2 * nl + 1, self.n), np.uint32)
+        if self._L.orc_gen_ksk_low(self.h, int(galois), int(level), out):
+            raise ValueError(f"level {level} has no reduced basis (nl {nl}, alpha {self.alpha})")
+        return out
+
+    def keyswitch_low(self, level: int, ds, keys) -> np.ndarray:
+        """one-digit key switch over Q_l P_l (P_l = the first nl + 1 special primes) of the 1 or 2 polynomials
+        ds, each with its own gen_ksk_low key; two sources are summed in Q_l P_l before the one ModDown"""
+        nl = self.nl(level)
+        d = np.ascontiguousarray(np.stack([np.asarray(x, np.uint32) for x in ds]))
+        k = np.ascontiguousarray(np.stack([np.asarray(x, np.uint32) for x in keys]))
+        if d.shape != (len(ds), nl, self.n) or k.shape != (len(ds), 2, 2 * nl + 1, self.n):
+            raise ValueError(f"keyswitch_low: shapes {d.shape} / {k.shape} at level {level}")
+        out = np.zeros((2, nl, self.n), np.uint32)
+        if self._L.orc_keyswitch_low(self.h, int(level), len(ds), d, k, out):
+            raise ValueError(f"level {level} has no reduced basis, or not 1 or 2 sources")
         return out
 
     # -- ciphertext primitives (NTT form arrays) ------------------------------------

@@ -548,18 +548,12 @@ static void automorph_limb(const orc_t *o, int li, u64 g, const u32 *in, u32 *ou
     free(c);
 }
 
-/* key-switching key for s' -> s, s' = s^2 (g == 0), s(X^g) (g < 2N), or s(X^g')^2 for the tag
- * g = 4N + g' (the conjugation / rotation of a 3-polynomial tensor) */
-void orc_gen_ksk(void *h, u64 g, u32 *out) {
-    orc_t *o = (orc_t *)h;
-    int n = o->n, tot = o->n_q + o->n_p, next = o->n_ks + o->n_p;
-    u32 *s = (u32 *)malloc(sizeof(u32) * (size_t)tot * n);
-    orc_secret_ntt(h, s);
-    int *ids = (int *)malloc(sizeof(int) * next);
-    for (int i = 0; i < next; i++) ids[i] = i < o->n_ks ? i : o->n_q + (i - o->n_ks);
-    /* s' on Q limbs 0..n_ks-1 */
-    u32 *sp = (u32 *)malloc(sizeof(u32) * (size_t)o->n_ks * n);
-    for (int i = 0; i < o->n_ks; i++) {
+/* source secret s' of the key of tag g on Q limbs 0..nrows-1 (NTT form): s^2 (g == 0), s(X^g) (g < 2N), or
+ * s(X^g')^2 for the tag g = 4N + g' (the conjugation / rotation of a 3-polynomial tensor).
+ * s: the secret on every limb (orc_secret_ntt) */
+static void key_source(const orc_t *o, const u32 *s, u64 g, int nrows, u32 *sp) {
+    int n = o->n;
+    for (int i = 0; i < nrows; i++) {
         u32 q = o->mod[i];
         if (g == 0) {
             for (int k = 0; k < n; k++) sp[(size_t)i * n + k] = mulm(s[(size_t)i * n + k], s[(size_t)i * n + k], q);
@@ -572,28 +566,70 @@ void orc_gen_ksk(void *h, u64 g, u32 *out) {
             automorph_limb(o, i, g, s + (size_t)i * n, sp + (size_t)i * n);
         }
     }
+}
+
+/* one digit's key (b | a) on the `next` rows of global prime ids[x]: a uniform from stream_a (counter = global
+ * prime * N + k), e (CBD) from stream_e, b = e - a s, plus (P mod q) s' on the digit's own rows lo..hi-1 where
+ * P = the first np special primes.  sp: s' on Q rows (row x = prime x) */
+static void ksk_digit(const orc_t *o, const u32 *s, const u32 *sp, const int *ids, int next, int lo, int hi, int np,
+                      u64 stream_a, u64 stream_e, u32 *b, u32 *a) {
+    int n = o->n;
     int *e = (int *)malloc(sizeof(int) * n);
     u32 *eN = (u32 *)malloc(sizeof(u32) * (size_t)next * n);
-    for (int j = 0; j < o->dnum; j++) {
-        u32 *b = out + (size_t)j * 2 * next * n, *a = b + (size_t)next * n;
-        cbd_poly(o, STREAM(5, g, j), e);
-        small_to_ntt(o, e, ids, next, eN);
-        for (int x = 0; x < next; x++) {
-            int li = ids[x];
-            u32 q = o->mod[li];
-            u32 pmod = 1; /* P mod q */
-            for (int k = 0; k < o->n_p; k++) pmod = mulm(pmod, o->mod[o->n_q + k] % q, q);
-            int in_digit = (x < o->n_ks) && (x / o->alpha == j);
-            for (int k = 0; k < n; k++) {
-                u32 av = (u32)(prng(o->key, STREAM(4, g, j), (u64)li * n + k) % q);
-                u32 v = subm(eN[(size_t)x * n + k], mulm(av, s[(size_t)li * n + k], q), q);
-                if (in_digit) v = addm(v, mulm(pmod, sp[(size_t)x * n + k], q), q);
-                a[(size_t)x * n + k] = av;
-                b[(size_t)x * n + k] = v;
-            }
+    cbd_poly(o, stream_e, e);
+    small_to_ntt(o, e, ids, next, eN);
+    for (int x = 0; x < next; x++) {
+        int li = ids[x];
+        u32 q = o->mod[li];
+        u32 pmod = 1; /* P mod q */
+        for (int k = 0; k < np; k++) pmod = mulm(pmod, o->mod[o->n_q + k] % q, q);
+        int in_digit = x >= lo && x < hi;
+        for (int k = 0; k < n; k++) {
+            u32 av = (u32)(prng(o->key, stream_a, (u64)li * n + k) % q);
+            u32 v = subm(eN[(size_t)x * n + k], mulm(av, s[(size_t)li * n + k], q), q);
+            if (in_digit) v = addm(v, mulm(pmod, sp[(size_t)x * n + k], q), q);
+            a[(size_t)x * n + k] = av;
+            b[(size_t)x * n + k] = v;
         }
     }
-    free(s); free(ids); free(sp); free(e); free(eN);
+    free(e); free(eN);
+}
+
+/* key-switching key for s' -> s (s' of tag g: key_source), dnum digits over Q limbs 0..n_ks-1 and all of P */
+void orc_gen_ksk(void *h, u64 g, u32 *out) {
+    orc_t *o = (orc_t *)h;
+    int n = o->n, tot = o->n_q + o->n_p, next = o->n_ks + o->n_p;
+    u32 *s = (u32 *)malloc(sizeof(u32) * (size_t)tot * n);
+    orc_secret_ntt(h, s);
+    int *ids = (int *)malloc(sizeof(int) * next);
+    for (int i = 0; i < next; i++) ids[i] = i < o->n_ks ? i : o->n_q + (i - o->n_ks);
+    u32 *sp = (u32 *)malloc(sizeof(u32) * (size_t)o->n_ks * n);
+    key_source(o, s, g, o->n_ks, sp);
+    for (int j = 0; j < o->dnum; j++) {
+        u32 *b = out + (size_t)j * 2 * next * n, *a = b + (size_t)next * n;
+        int lo = j * o->alpha, hi = lo + o->alpha < o->n_ks ? lo + o->alpha : o->n_ks;
+        ksk_digit(o, s, sp, ids, next, lo, hi, o->n_p, STREAM(4, g, j), STREAM(5, g, j), b, a);
+    }
+    free(s); free(ids); free(sp);
+}
+
+/* the reduced-basis key of a level of nl < alpha limbs (engine.hip ksk_at): one digit over
+ * Q_l P_l, P_l = the first np = nl + 1 special primes; out [2][nl + np][N], rows = Q limbs 0..nl-1 then
+ * special primes 0..np-1; a from STREAM(10, g, level), e from STREAM(11, g, level),
+ * b = e - a s + (P_l mod q_t) s' on the nl Q rows.  Returns 0, or -1 when the level has no reduced basis */
+int orc_gen_ksk_low(void *h, u64 g, int level, u32 *out) {
+    orc_t *o = (orc_t *)h;
+    if (level < 0 || level > o->L || NL(o, level) >= o->alpha) return -1;
+    int n = o->n, tot = o->n_q + o->n_p, nl = NL(o, level), np = nl + 1, next = nl + np;
+    u32 *s = (u32 *)malloc(sizeof(u32) * (size_t)tot * n);
+    orc_secret_ntt(h, s);
+    int *ids = (int *)malloc(sizeof(int) * next);
+    for (int i = 0; i < next; i++) ids[i] = i < nl ? i : o->n_q + (i - nl);
+    u32 *sp = (u32 *)malloc(sizeof(u32) * (size_t)nl * n);
+    key_source(o, s, g, nl, sp);
+    ksk_digit(o, s, sp, ids, next, 0, nl, np, STREAM(10, g, level), STREAM(11, g, level), out, out + (size_t)next * n);
+    free(s); free(ids); free(sp);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -635,15 +671,7 @@ void orc_rescale(void *h, int level, int npoly, const u32 *in, u32 *out) {
 /* estimate, mu_i = floor(2^61 / q_i); sum_i y_i qhat_i - u Q is the   */
 /* centred representative of the digit (up to rare boundary ties).     */
 /* ------------------------------------------------------------------ */
-static u32 overflow_count(const u32 *y, size_t stride, int h, const u32 *primes) {
-    u64 f = 0;
-    for (int i = 0; i < h; i++) {
-        u64 mu = (1ull << 61) / primes[i];
-        f += ((u64)y[(size_t)i * stride] * mu) >> 29;
-    }
-    return (u32)((f + (1ull << 31)) >> 32);
-}
-/* the same for every coefficient k < n, the mu_i hoisted and the coefficients in parallel */
+/* for every coefficient k < n, the mu_i hoisted and the coefficients in parallel */
 static void overflow_counts(const u32 *y, int n, int h, const u32 *primes, u32 *ucnt) {
     u64 mu[64];
     for (int i = 0; i < h; i++) mu[i] = (1ull << 61) / primes[i];
@@ -656,78 +684,72 @@ static void overflow_counts(const u32 *y, int n, int h, const u32 *primes, u32 *
 }
 
 /* ------------------------------------------------------------------ */
-/* hybrid key switching (DESIGN.md §3.6)                               */
-/* d: (l+2) limbs NTT form; out: 2 x (l+2) limbs NTT form              */
+/* the three steps every key switch here is made of.   */
+/* An extended basis is ne rows: Q limbs 0..nl-1, then np special       */
+/* primes; gid[x] = the global prime of row x.                          */
 /* ------------------------------------------------------------------ */
-void orc_keyswitch(void *h, int level, const u32 *d, const u32 *ksk, u32 *out) {
-    orc_t *o = (orc_t *)h;
-    int n = o->n, nl = NL(o, level), np = o->n_p, next_key = o->n_ks + o->n_p;
-    int ne = nl + np; /* extended basis: Q limbs 0..nl-1, then P */
-    int *gid = (int *)malloc(sizeof(int) * ne);  /* global prime index */
-    int *kid = (int *)malloc(sizeof(int) * ne);  /* key limb index */
+/* ModUp of the digit of Q limbs lo..hi-1: d = the polynomial (NTT form), coef = the same in coefficient form;
+ * ext [ne][N] (NTT form) = the digit's own rows copied, every other row the centred conversion of the digit */
+static void modup_digit(const orc_t *o, const u32 *d, const u32 *coef, int lo, int hi, const int *gid, int ne, u32 *ext) {
+    int n = o->n;
+    /* y_i = coef_i * (qhat_i^-1 mod q_i), qhat_i = prod_{k in digit, k != i} q_k */
+    u32 *y = (u32 *)malloc(sizeof(u32) * (size_t)(hi - lo) * n);
+#pragma omp parallel for schedule(static)
+    for (int i = lo; i < hi; i++) {
+        u32 q = o->mod[i], qh = 1;
+        for (int k = lo; k < hi; k++) if (k != i) qh = mulm(qh, o->mod[k] % q, q);
+        u32 qhi = invm(qh, q), qhip = shoup_pre32(qhi, q);
+        for (int k = 0; k < n; k++) y[(size_t)(i - lo) * n + k] = smul(coef[(size_t)i * n + k], qhi, qhip, q);
+    }
+    u32 *ucnt = (u32 *)malloc(sizeof(u32) * n);
+    overflow_counts(y, n, hi - lo, o->mod + lo, ucnt);
+#pragma omp parallel for schedule(static)
     for (int x = 0; x < ne; x++) {
-        gid[x] = x < nl ? x : o->n_q + (x - nl);
-        kid[x] = x < nl ? x : o->n_ks + (x - nl);
-    }
-    u32 *acc = (u32 *)calloc((size_t)2 * ne * n, sizeof(u32));
-    u32 *ext = (u32 *)malloc(sizeof(u32) * (size_t)ne * n);
-    u32 *coef = (u32 *)malloc(sizeof(u32) * (size_t)nl * n);
-    memcpy(coef, d, sizeof(u32) * (size_t)nl * n);
-#pragma omp parallel for schedule(static)
-    for (int i = 0; i < nl; i++) intt_limb(o, i, coef + (size_t)i * n);
-    int ndig = (nl + o->alpha - 1) / o->alpha;
-    for (int j = 0; j < ndig; j++) {
-        int lo = j * o->alpha, hi = lo + o->alpha < nl ? lo + o->alpha : nl;
-        /* y_i = coef_i * (qhat_i^-1 mod q_i), qhat_i = prod_{k in digit, k != i} q_k */
-        u32 *y = (u32 *)malloc(sizeof(u32) * (size_t)(hi - lo) * n);
-#pragma omp parallel for schedule(static)
+        u32 *dst = ext + (size_t)x * n;
+        if (x >= lo && x < hi) { memcpy(dst, d + (size_t)x * n, sizeof(u32) * n); continue; }
+        u32 t = o->mod[gid[x]];
+        u32 *qh_t = (u32 *)malloc(sizeof(u32) * (hi - lo));
         for (int i = lo; i < hi; i++) {
-            u32 q = o->mod[i], qh = 1;
-            for (int k = lo; k < hi; k++) if (k != i) qh = mulm(qh, o->mod[k] % q, q);
-            u32 qhi = invm(qh, q), qhip = shoup_pre32(qhi, q);
-            for (int k = 0; k < n; k++) y[(size_t)(i - lo) * n + k] = smul(coef[(size_t)i * n + k], qhi, qhip, q);
+            u32 v = 1;
+            for (int k = lo; k < hi; k++) if (k != i) v = mulm(v, o->mod[k] % t, t);
+            qh_t[i - lo] = v;
         }
-        u32 *ucnt = (u32 *)malloc(sizeof(u32) * n);
-        overflow_counts(y, n, hi - lo, o->mod + lo, ucnt);
-#pragma omp parallel for schedule(static)
-        for (int x = 0; x < ne; x++) {
-            u32 *dst = ext + (size_t)x * n;
-            if (x >= lo && x < hi) { memcpy(dst, d + (size_t)x * n, sizeof(u32) * n); continue; }
-            u32 t = o->mod[gid[x]];
-            u32 *qh_t = (u32 *)malloc(sizeof(u32) * (hi - lo));
-            for (int i = lo; i < hi; i++) {
-                u32 v = 1;
-                for (int k = lo; k < hi; k++) if (k != i) v = mulm(v, o->mod[k] % t, t);
-                qh_t[i - lo] = v;
-            }
-            u32 negQ = 1; /* -Q_j mod t */
-            for (int k = lo; k < hi; k++) negQ = mulm(negQ, o->mod[k] % t, t);
-            negQ = negQ ? t - negQ : 0;
-            barrett_t bt = bq_make(t);
-            for (int k = 0; k < n; k++) {
-                u128 s = (u64)ucnt[k] * negQ;
-                for (int i = lo; i < hi; i++) s += (u64)y[(size_t)(i - lo) * n + k] * qh_t[i - lo];
-                dst[k] = bred128(s, &bt);
-            }
-            free(qh_t);
-            ntt_limb(o, gid[x], dst);
+        u32 negQ = 1; /* -Q_j mod t */
+        for (int k = lo; k < hi; k++) negQ = mulm(negQ, o->mod[k] % t, t);
+        negQ = negQ ? t - negQ : 0;
+        barrett_t bt = bq_make(t);
+        for (int k = 0; k < n; k++) {
+            u128 s = (u64)ucnt[k] * negQ;
+            for (int i = lo; i < hi; i++) s += (u64)y[(size_t)(i - lo) * n + k] * qh_t[i - lo];
+            dst[k] = bred128(s, &bt);
         }
-        free(y); free(ucnt);
-        const u32 *kb = ksk + (size_t)j * 2 * next_key * n, *ka = kb + (size_t)next_key * n;
+        free(qh_t);
+        ntt_limb(o, gid[x], dst);
+    }
+    free(y); free(ucnt);
+}
+
+/* acc ([2][ne][N]: the b part, then the a part) += ext * key, row x against key row kid[x] of kb / ka.
+ * Every sum is reduced to [0, q), so the order in which digits or sources are added does not show */
+static void key_inner_acc(const orc_t *o, const u32 *ext, const int *gid, const int *kid, int ne, const u32 *kb, const u32 *ka, u32 *acc) {
+    int n = o->n;
 #pragma omp parallel for schedule(static)
-        for (int x = 0; x < ne; x++) {
-            u32 t = o->mod[gid[x]];
-            barrett_t bt = bq_make(t);
-            for (int k = 0; k < n; k++) {
-                u32 e = ext[(size_t)x * n + k];
-                acc[(size_t)x * n + k] = bred64((u64)acc[(size_t)x * n + k] + (u64)e * kb[(size_t)kid[x] * n + k], &bt);
-                acc[(size_t)(ne + x) * n + k] = bred64((u64)acc[(size_t)(ne + x) * n + k] + (u64)e * ka[(size_t)kid[x] * n + k], &bt);
-            }
+    for (int x = 0; x < ne; x++) {
+        u32 t = o->mod[gid[x]];
+        barrett_t bt = bq_make(t);
+        for (int k = 0; k < n; k++) {
+            u32 e = ext[(size_t)x * n + k];
+            acc[(size_t)x * n + k] = bred64((u64)acc[(size_t)x * n + k] + (u64)e * kb[(size_t)kid[x] * n + k], &bt);
+            acc[(size_t)(ne + x) * n + k] = bred64((u64)acc[(size_t)(ne + x) * n + k] + (u64)e * ka[(size_t)kid[x] * n + k], &bt);
         }
     }
-    /* ModDown by P */
+}
+
+/* ModDown of acc ([2][nl + np][N]) by P = the first np special primes, centred: out [2][nl][N] */
+static void moddown(const orc_t *o, const u32 *acc, int nl, int np, u32 *out) {
+    int n = o->n, ne = nl + np;
     for (int p = 0; p < 2; p++) {
-        u32 *a = acc + (size_t)p * ne * n;
+        const u32 *a = acc + (size_t)p * ne * n;
         u32 *yp = (u32 *)malloc(sizeof(u32) * (size_t)np * n);
 #pragma omp parallel for schedule(static)
         for (int k2 = 0; k2 < np; k2++) {
@@ -769,7 +791,73 @@ void orc_keyswitch(void *h, int level, const u32 *d, const u32 *ksk, u32 *out) {
         }
         free(yp); free(ucnt);
     }
+}
+
+/* ------------------------------------------------------------------ */
+/* hybrid key switching (DESIGN.md §3.6)                               */
+/* d: (l+2) limbs NTT form; out: 2 x (l+2) limbs NTT form              */
+/* ------------------------------------------------------------------ */
+void orc_keyswitch(void *h, int level, const u32 *d, const u32 *ksk, u32 *out) {
+    orc_t *o = (orc_t *)h;
+    int n = o->n, nl = NL(o, level), np = o->n_p, next_key = o->n_ks + o->n_p;
+    int ne = nl + np; /* extended basis: Q limbs 0..nl-1, then P */
+    int *gid = (int *)malloc(sizeof(int) * ne);  /* global prime index */
+    int *kid = (int *)malloc(sizeof(int) * ne);  /* key limb index */
+    for (int x = 0; x < ne; x++) {
+        gid[x] = x < nl ? x : o->n_q + (x - nl);
+        kid[x] = x < nl ? x : o->n_ks + (x - nl);
+    }
+    u32 *acc = (u32 *)calloc((size_t)2 * ne * n, sizeof(u32));
+    u32 *ext = (u32 *)malloc(sizeof(u32) * (size_t)ne * n);
+    u32 *coef = (u32 *)malloc(sizeof(u32) * (size_t)nl * n);
+    memcpy(coef, d, sizeof(u32) * (size_t)nl * n);
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < nl; i++) intt_limb(o, i, coef + (size_t)i * n);
+    int ndig = (nl + o->alpha - 1) / o->alpha;
+    for (int j = 0; j < ndig; j++) {
+        int lo = j * o->alpha, hi = lo + o->alpha < nl ? lo + o->alpha : nl;
+        modup_digit(o, d, coef, lo, hi, gid, ne, ext);
+        const u32 *kb = ksk + (size_t)j * 2 * next_key * n, *ka = kb + (size_t)next_key * n;
+        key_inner_acc(o, ext, gid, kid, ne, kb, ka, acc);
+    }
+    moddown(o, acc, nl, np, out);
     free(gid); free(kid); free(acc); free(ext); free(coef);
+}
+
+/* one digit of all nl Q limbs over Q P', P' = the first np special primes: nsrc polynomials d [nsrc][nl][N],
+ * each with its own key [nsrc][2][nl + np][N]; their inner products are summed in Q P' BEFORE the one
+ * ModDown (out [2][nl][N]), as the engine sums the two sources of a deferred tensor's conjugation
+ * (engine.hip galois_lazy): two separately rounded ModDowns would differ by one here and there */
+static void keyswitch_one_digit(const orc_t *o, int nl, int np, int nsrc, const u32 *d, const u32 *ksk, u32 *out) {
+    int n = o->n, ne = nl + np;
+    int *gid = (int *)malloc(sizeof(int) * ne);
+    for (int x = 0; x < ne; x++) gid[x] = x < nl ? x : o->n_q + (x - nl);
+    u32 *acc = (u32 *)calloc((size_t)2 * ne * n, sizeof(u32));
+    u32 *ext = (u32 *)malloc(sizeof(u32) * (size_t)ne * n);
+    u32 *coef = (u32 *)malloc(sizeof(u32) * (size_t)nl * n);
+    int *kid = (int *)malloc(sizeof(int) * ne);
+    for (int x = 0; x < ne; x++) kid[x] = x;
+    for (int s = 0; s < nsrc; s++) {
+        const u32 *ds = d + (size_t)s * nl * n;
+        memcpy(coef, ds, sizeof(u32) * (size_t)nl * n);
+#pragma omp parallel for schedule(static)
+        for (int i = 0; i < nl; i++) intt_limb(o, i, coef + (size_t)i * n);
+        modup_digit(o, ds, coef, 0, nl, gid, ne, ext);
+        const u32 *kb = ksk + (size_t)s * 2 * ne * n, *ka = kb + (size_t)ne * n;
+        key_inner_acc(o, ext, gid, kid, ne, kb, ka, acc);
+    }
+    moddown(o, acc, nl, np, out);
+    free(gid); free(kid); free(acc); free(ext); free(coef);
+}
+
+/* the reduced-basis key switch at a level of nl < alpha limbs: one digit over Q_l P_l with
+ * P_l = the first nl + 1 special primes and orc_gen_ksk_low's keys; nsrc = 1, or 2 (summed before the
+ * ModDown).  Returns 0, or -1 when the level has no reduced basis */
+int orc_keyswitch_low(void *h, int level, int nsrc, const u32 *d, const u32 *ksk, u32 *out) {
+    orc_t *o = (orc_t *)h;
+    if (level < 0 || level > o->L || NL(o, level) >= o->alpha || nsrc < 1 || nsrc > 2) return -1;
+    keyswitch_one_digit(o, NL(o, level), NL(o, level) + 1, nsrc, d, ksk, out);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -820,88 +908,7 @@ void orc_rescale2(void *h, int level, int npoly, const u32 *in, u32 *out) {
 /* out [2][2][N] = key-switched (c0', c1') (c0 not added).              */
 /* ------------------------------------------------------------------ */
 void orc_keyswitch_d2s(void *h, int np, const u32 *d, const u32 *ksk, u32 *out) {
-    orc_t *o = (orc_t *)h;
-    int n = o->n, nq = 2, ne = nq + np;
-    int gid[64];
-    for (int x = 0; x < ne; x++) gid[x] = x < nq ? x : o->n_q + (x - nq);
-    u32 *coef = (u32 *)malloc(sizeof(u32) * (size_t)nq * n);
-    memcpy(coef, d, sizeof(u32) * (size_t)nq * n);
-    for (int i = 0; i < nq; i++) intt_limb(o, i, coef + (size_t)i * n);
-    u32 *y = (u32 *)malloc(sizeof(u32) * (size_t)nq * n);
-    for (int i = 0; i < nq; i++) {
-        u32 q = o->mod[i], qh = o->mod[1 - i] % q, qhi = invm(qh, q);
-        for (int k = 0; k < n; k++) y[(size_t)i * n + k] = mulm(coef[(size_t)i * n + k], qhi, q);
-    }
-    u32 *ucnt = (u32 *)malloc(sizeof(u32) * n);
-    for (int k = 0; k < n; k++) ucnt[k] = overflow_count(y + k, n, nq, o->mod);
-    u32 *ext = (u32 *)malloc(sizeof(u32) * (size_t)ne * n);
-    for (int x = 0; x < ne; x++) {
-        u32 *dst = ext + (size_t)x * n;
-        if (x < nq) { memcpy(dst, d + (size_t)x * n, sizeof(u32) * n); continue; }
-        u32 t = o->mod[gid[x]];
-        u32 qh0 = o->mod[1] % t, qh1 = o->mod[0] % t;
-        u32 negQ = mulm(o->mod[0] % t, o->mod[1] % t, t);
-        negQ = negQ ? t - negQ : 0;
-        barrett_t bt = bq_make(t);
-        for (int k = 0; k < n; k++) {
-            u128 s = (u64)ucnt[k] * negQ;
-            s += (u64)y[k] * qh0;
-            s += (u64)y[(size_t)n + k] * qh1;
-            dst[k] = bred128(s, &bt);
-        }
-        ntt_limb(o, gid[x], dst);
-    }
-    u32 *acc = (u32 *)calloc((size_t)2 * ne * n, sizeof(u32));
-    const u32 *kb = ksk, *ka = ksk + (size_t)ne * n;
-    for (int x = 0; x < ne; x++) {
-        u32 t = o->mod[gid[x]];
-        for (int k = 0; k < n; k++) {
-            u32 e = ext[(size_t)x * n + k];
-            acc[(size_t)x * n + k] = mulm(e, kb[(size_t)x * n + k], t);
-            acc[(size_t)(ne + x) * n + k] = mulm(e, ka[(size_t)x * n + k], t);
-        }
-    }
-    /* ModDown by P' onto (q0, q1) */
-    for (int p = 0; p < 2; p++) {
-        u32 *a = acc + (size_t)p * ne * n;
-        u32 *yp = (u32 *)malloc(sizeof(u32) * (size_t)np * n);
-        for (int k2 = 0; k2 < np; k2++) {
-            int g = o->n_q + k2;
-            u32 q = o->mod[g], ph = 1;
-            for (int m = 0; m < np; m++) if (m != k2) ph = mulm(ph, o->mod[o->n_q + m] % q, q);
-            u32 phi = invm(ph, q);
-            memcpy(yp + (size_t)k2 * n, a + (size_t)(nq + k2) * n, sizeof(u32) * n);
-            intt_limb(o, g, yp + (size_t)k2 * n);
-            for (int k = 0; k < n; k++) yp[(size_t)k2 * n + k] = mulm(yp[(size_t)k2 * n + k], phi, q);
-        }
-        u32 *uc = (u32 *)malloc(sizeof(u32) * n);
-        overflow_counts(yp, n, np, o->mod + o->n_q, uc);
-        for (int t = 0; t < nq; t++) {
-            u32 q = o->mod[t], pinv = 1;
-            u32 ph_t[16];
-            for (int k2 = 0; k2 < np; k2++) {
-                u32 v = 1;
-                for (int m = 0; m < np; m++) if (m != k2) v = mulm(v, o->mod[o->n_q + m] % q, q);
-                ph_t[k2] = v;
-                pinv = mulm(pinv, o->mod[o->n_q + k2] % q, q);
-            }
-            u32 negP = pinv ? q - pinv : 0;
-            pinv = invm(pinv, q);
-            barrett_t bt = bq_make(q);
-            u32 *conv = (u32 *)malloc(sizeof(u32) * n);
-            for (int k = 0; k < n; k++) {
-                u128 s = (u64)uc[k] * negP;
-                for (int k2 = 0; k2 < np; k2++) s += (u64)yp[(size_t)k2 * n + k] * ph_t[k2];
-                conv[k] = bred128(s, &bt);
-            }
-            ntt_limb(o, t, conv);
-            u32 *dst = out + (size_t)p * nq * n + (size_t)t * n;
-            for (int k = 0; k < n; k++) dst[k] = mulm(subm(a[(size_t)t * n + k], conv[k], q), pinv, q);
-            free(conv);
-        }
-        free(yp); free(uc);
-    }
-    free(coef); free(y); free(ucnt); free(ext); free(acc);
+    keyswitch_one_digit((const orc_t *)h, 2, np, 1, d, ksk, out);
 }
 
 /* ------------------------------------------------------------------ */

@@ -3,7 +3,8 @@
  * oracle/ckks_oracle.c once, with the buffer shapes oracle/ckks_cpu.py passes, so that a
  * build under -fsanitize=address,undefined (tests/test_oracle_sanitize.py) checks the
  * oracle's memory accesses and integer arithmetic on the plain chain (N = 2^13, L = 4) and
- * on the bootstrappable chain (L1 = 5, 13 double-prime levels).
+ * on the bootstrappable chain (L1 = 5, 13 double-prime levels; alpha = 7, so its levels 0..4 also
+ * run the reduced-basis keys and key switch).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -28,6 +29,8 @@ void orc_secret(void *h, int *s_out);
 void orc_secret_ntt(void *h, u32 *out);
 void orc_gen_pk(void *h, u32 *out);
 void orc_gen_ksk(void *h, u64 g, u32 *out);
+int orc_gen_ksk_low(void *h, u64 g, int level, u32 *out);
+int orc_keyswitch_low(void *h, int level, int nsrc, const u32 *d, const u32 *ksk, u32 *out);
 void orc_rescale(void *h, int level, int npoly, const u32 *in, u32 *out);
 void orc_keyswitch(void *h, int level, const u32 *d, const u32 *ksk, u32 *out);
 void orc_rescale2(void *h, int level, int npoly, const u32 *in, u32 *out);
@@ -120,6 +123,14 @@ static void exercise(chain_t *c) {
         u32 *a = rand_poly(c, 2, nl), *b = rand_poly(c, 2, nl);
         u32 *o3 = xalloc((size_t)3 * nl * n), *o2 = xalloc((size_t)2 * nl * n);
         orc_keyswitch(c->h, l, a + (size_t)nl * n, ksk, o2);
+        if (nl < c->alpha) {  /* a reduced level: its own key, one source, then two summed before the ModDown */
+            u32 *klow = xalloc((size_t)2 * 2 * (2 * nl + 1) * n);
+            if (orc_gen_ksk_low(c->h, 0, l, klow) || orc_gen_ksk_low(c->h, 5, l, klow + (size_t)2 * (2 * nl + 1) * n)) exit(3);
+            if (orc_keyswitch_low(c->h, l, 1, a, klow, o2) || orc_keyswitch_low(c->h, l, 2, a, klow, o2)) exit(3);
+            free(klow);
+        } else if (orc_gen_ksk_low(c->h, 0, l, o2) != -1 || orc_keyswitch_low(c->h, l, 1, a, ksk, o2) != -1) {
+            exit(3);  /* an unreduced level is refused, nothing written */
+        }
         orc_tensor(c->h, l, a, b, o3);
         orc_automorph(c->h, l, 5, 2, a, o2);
         u32 *cs = xalloc(nl);
