@@ -3076,6 +3076,42 @@ public:
         p.encx[key] = {d, (size_t)nl * hp_.n};
         return d;
     }
+    // the temporaries of one call (rot_pt_sum, the renorm): scratch rows and owned ciphertexts go back to the pool
+    // on the way out, by return or by throw.  Fixed capacity: a call allocates nothing for it
+    struct Guard {
+        static constexpr int kCap = 8;
+        Engine& e;
+        std::pair<u32*, size_t> rows[kCap];
+        Ct cts[kCap];
+        int nr = 0, nc = 0;
+        explicit Guard(Engine& eng) : e(eng) {}
+        Guard(const Guard&) = delete;
+        [[noreturn]] static void full() { throw std::runtime_error("Guard: more temporaries than it holds"); }
+        u32* get(size_t r) {
+            if (nr == kCap) full();
+            rows[nr] = {e.tmp(r), r};
+            return rows[nr++].first;
+        }
+        void row(u32* p, size_t r) {  // rows taken elsewhere (a ModUp's output)
+            if (nr == kCap) e.untmp(p, r), full();
+            rows[nr++] = {p, r};
+        }
+        void own(const Ct& c) {
+            if (nc == kCap) e.release(c), full();
+            cts[nc++] = c;
+        }
+        void disown(const Ct& c) {  // the call succeeded: c leaves with the caller
+            for (int x = 0; x < nc; ++x)
+                if (cts[x].data == c.data) {
+                    cts[x] = cts[--nc];
+                    return;
+                }
+        }
+        ~Guard() {
+            for (int x = 0; x < nr; ++x) e.untmp(rows[x].first, rows[x].second);
+            for (int x = 0; x < nc; ++x) e.release(cts[x]);
+        }
+    };
     // out[j] = sum_i pts[j n + i] (.) rotate(c, steps[i]), double-hoisted (aesfhe_rot_pt_sum):
     // c1 is ModUp'ed ONCE, k_rot_mask_mac forms every used rotation's key inner product through its
     // automorphism, multiplies it by the term's mask and sums in Q*P -- one ModDown per output, under the
@@ -3090,23 +3126,9 @@ public:
         if (c_in.nb != 1) throw std::runtime_error("rot_pt_sum: a single ciphertext (stacks are refused)");
         if (vis_npoly(c_in) != 2) throw std::runtime_error("rot_pt_sum: expects a 2-polynomial ciphertext");
         if (c_in.level - c_in.pend < 1) throw std::runtime_error("not enough level to multiply by a plaintext (level 0)");
-        // every temporary and, until the call succeeds, every output goes back to the pool on the way out
-        struct Guard {
-            Engine& e;
-            std::vector<std::pair<u32*, size_t>> rows;
-            std::vector<Ct> cts;
-            u32* get(size_t r) {
-                u32* p = e.tmp(r);
-                rows.push_back({p, r});
-                return p;
-            }
-            ~Guard() {
-                for (auto& x : rows) e.untmp(x.first, x.second);
-                for (const Ct& c : cts) e.release(c);
-            }
-        } G{*this, {}, {}};
+        Guard G(*this);
         Ct c = normalize(c_in);
-        if (c.data != c_in.data) G.cts.push_back(c);
+        if (c.data != c_in.data) G.own(c);
         const int l = c.level, nl = hp_.nl(l), np = np_at(l), ne = nl + np, N = hp_.n;
         const KsBasis& B = kb(l);
         const long sc = slot_count();
@@ -3131,13 +3153,13 @@ public:
             if (fills[j]) a.fill[j] = pt_fill_at(pt(fills[j]), l, np), ++nfill;
         if (nrot) {
             u32* ext = modup(a.c1, l, 1, 0);
-            G.rows.push_back({ext, (size_t)ext_rows(l)});
+            G.row(ext, (size_t)ext_rows(l));
             a.ext = ext;
         }
         std::vector<Ct> out(n_out);
         for (int j = 0; j < n_out; ++j) {
             out[j] = alloc_ct(l, 2);
-            G.cts.push_back(out[j]);
+            G.own(out[j]);
             if (rot_out[j]) {
                 a.out0[j] = G.get(nl), a.out1[j] = G.get(nl), a.outp[j] = G.get(2 * (size_t)ne);
             } else {  // no rotated term: the Q-side sums are the result
@@ -3158,16 +3180,11 @@ public:
         if (!headroom(l, 1, 1.0))
             for (int j = 0; j < n_out; ++j) {
                 Ct r = rescale(out[j]);
-                G.cts.push_back(r);
+                G.own(r);
                 out[j] = r;
             }
         // success: the outputs leave the guard (the rescaled ones' sources stay in it)
-        for (const Ct& o : out)
-            for (size_t x = 0; x < G.cts.size(); ++x)
-                if (G.cts[x].data == o.data) {
-                    G.cts.erase(G.cts.begin() + x);
-                    break;
-                }
+        for (const Ct& o : out) G.disown(o);
         return out;
     }
     Ct rotate(const Ct& c, int steps) {
@@ -3250,326 +3267,373 @@ public:
         return d_s2_;
     }
 
-    // secret-key Zeta16 renorm of a state pair (REF/pipeline.py:65-69, REF/state_encoder.py:17-38),
-    // entirely on the device: raw decryption of both tensors on 2..4 limbs, mixed-radix CRT,
-    // the 16 state slots evaluated directly, snap to the nearest zeta16 power, closed-form
-    // re-encoding (every other slot 1) and fresh encryption -- no host round trip
-    //
-    // states > 1 is the slot-packed layout: state b of the
-    // batch holds byte i in slot i * stride + b, so every slot with (j mod stride) < states is
-    // snapped and the rest are reset to 1.  The whole slot vector is decoded and re-encoded
-    // with a device fp64 FFT (launch_fft2); states == 1 keeps the 16-slot direct evaluation.
-    //
-    // level >= 0 re-encrypts at min(level, fresh) instead of the fresh level:
-    // callers that know what the next step needs save the limbs
-    void renorm_pair(aesfhe_handle hh, aesfhe_handle hl, aesfhe_handle* oh, aesfhe_handle* ol) { renorm_states(hh, hl, 1, oh, ol); }
-    // period > 0: the periodic layout (slot j == slot j mod period, state_encoder.SlotLayout):
-    // period 16 decodes / re-encodes its 16 slots directly (5^i positions), other periods snap
-    // every slot (states = slot_count / 16)
-    //
-    // unpack = n > 0: hh is a packed state (hi | lo halves of every 2n-slot block, the
-    // pipeline's packed XOR stage) and hl must be hh; oh / ol get its hi / lo halves as
-    // n-periodic states.  single: hh == hl, one output (ol untouched) with every slot snapped.
-    // single with packed_period = 32 (the packed XOR stage's hi | lo form, period 2 x 16): the
-    // 32 slots are decoded / re-encoded directly (decode32 / encode32, no FFT); unpack = 16 likewise
-    // hc (packed / single renorms): the renorm of hh + conj(hc) -- a conjugate-split LUT's S1 + conj(S2)
-    //  renormalised without its conjugation key switch: both are decrypted in the
-    // one raw-decryption launch and conj(m2) is the automorphism X -> X^-1 of the NTT-form m2, added
-    // on the CRT limbs before the codec.  Inputs that do not share (level, owed rescales, shape) are
-    // summed homomorphically first (same result).
-    // hcl: the lo channel's partner of a pair renorm (hl + conj(hcl)), hc then the hi channel's.
-    // pack_out (pair, period 16): ONE output, the snapped hi | lo pair in the packed period-32 form
-    // (StateEncoder.pack's layout) -- the decode's two 16-slot channels are the 32 packed slots in
-    // order, so the encode is the packed renorm's (no mask products, no level for the pack).
-    void renorm_states(aesfhe_handle hh, aesfhe_handle hl, int states, aesfhe_handle* oh, aesfhe_handle* ol, int level = -1,
-                       int period = 0, int unpack = 0, bool single = false, int packed_period = 0, aesfhe_handle hc = 0,
-                       aesfhe_handle hcl = 0, bool pack_out = false, const int* slot_perm = nullptr) {
+    // ------------------------------------------------------------------ secret-key Zeta16 renorm
+    // (REF/pipeline.py:65-69, REF/state_encoder.py:17-38), entirely on the device: raw decryption of the
+    // inputs on 2..4 limbs, mixed-radix CRT, the state slots evaluated, each snapped to the nearest zeta16
+    // power, the message re-encoded and freshly encrypted -- no host round trip.  renorm(spec): renorm_check
+    // validates, renorm_plan picks the codec and the re-encryption once, the phases switch on the plan.
+    struct RenormSpec {
+        // Pair:   a (hi, lo) state pair in, the snapped pair out.
+        // Unpack: ONE packed state in (the hi | lo halves of every 2 period-slot block, the pipeline's packed
+        //         XOR stage), its hi / lo halves out as period-periodic states.
+        // Single: one ciphertext in, one out, every slot snapped.
+        enum class Shape { Pair, Unpack, Single };
+        Shape shape = Shape::Pair;
+        aesfhe_handle in[2] = {0, 0};  // Pair: hi, lo.  Unpack / Single: in[0] alone
+        // conjugate partners, one per input or none: the renorm of in[w] + conj(conj[w]) -- a conjugate-split LUT's
+        // S1 + conj(S2) without its conjugation key switch: both are decrypted raw and conj(m2),
+        // the automorphism X -> X^-1 of the NTT-form m2, is added on the CRT limbs before the codec.  Partners that
+        // do not share (level, owed rescales, shape) with their input are summed homomorphically first (same result)
+        aesfhe_handle conj[2] = {0, 0};
+        // Pair in the reference layout (period 0) only: the slot-packed states per ciphertext (SURVEY.md §8(f)1,
+        // DESIGN.md §3.9) -- state b holds byte i in slot i * stride + b, every slot with (j mod stride) < states is
+        // snapped, the rest reset to 1.  1: the 16 state slots evaluated directly; more: a device fp64 FFT
+        int states = 1;
+        // Pair:   the layout period (slot j == slot j mod period, state_encoder.SlotLayout); 0: the reference
+        //         layout.  16 decodes / re-encodes its 16 slots directly (5^i positions), other periods snap
+        //         every slot.
+        // Unpack: the half period n of the packed input = the period of each output; 16 decodes the 32 packed
+        //         slots directly.
+        // Single: a hint, the period of the packed message when known; 32 (the packed XOR stage's hi | lo
+        //         form, 2 x 16) decodes / re-encodes the 32 slots directly, anything else snaps every slot.
+        int period = 0;
+        // re-encrypt at min(level, fresh) instead of the fresh level (< 0): callers that know what the next
+        // step needs save the limbs
+        int level = -1;
+        // Pair, period 16: ONE output, the snapped hi | lo pair in the packed period-32 form
+        // (StateEncoder.pack's layout) -- the decode's two 16-slot channels are the 32 packed slots in order,
+        // so the encode is the packed renorm's (no mask products, no level for the pack)
+        bool pack_out = false;
+        // Pair with period 16, Unpack with period 16: 16 entries, output slot i takes input slot perm[i] -- a
+        // byte permutation such as ShiftRows folded into the renorm: the decode reads each output slot's value
+        // through the permuted root table, the encode writes slot i (no rotation, no level)
+        const int32_t* perm = nullptr;
+
+        static RenormSpec pair(aesfhe_handle hi, aesfhe_handle lo, int level) {
+            RenormSpec sp;
+            return sp.in[0] = hi, sp.in[1] = lo, sp.level = level, sp;
+        }
+        static RenormSpec unpack(aesfhe_handle packed, int period, int level) {
+            // period 0 has always been the reference-layout pair renorm of (packed, packed)
+            RenormSpec sp = pair(packed, period ? 0 : packed, level);
+            if (period) sp.shape = Shape::Unpack, sp.period = period;
+            return sp;
+        }
+        static RenormSpec single(aesfhe_handle c, int level) {
+            RenormSpec sp = pair(c, 0, level);
+            return sp.shape = Shape::Single, sp;
+        }
+        RenormSpec& with_states(int n) { return states = n, *this; }
+        RenormSpec& with_period(int p) { return period = p, *this; }
+        RenormSpec& with_conj(aesfhe_handle c0, aesfhe_handle c1 = 0) { return conj[0] = c0, conj[1] = c1, *this; }
+        RenormSpec& with_perm(const int32_t* p) { return perm = p, *this; }
+        RenormSpec& with_pack(bool on) { return pack_out = on, *this; }
+    };
+    // Sparse32 / Sparse16: the sparse decryption (round 6, AESFHE_SPARSE_DEC, default on with the pool) of the packed
+    // period-32 single / the periodic pair: only the D subring coefficients the snapped message can have are decoded
+    // (launch_renorm_sparse: block sums of c0 + c1 s, a D-point inverse transform, the CRT, the slots, the snap and the
+    // message's NTT table in TWO launches) -- three launches for the whole renorm with the pooled re-encryption instead
+    // of six.  Direct32 / Direct16: the 32 / 2 x 16 slots evaluated from the full raw decryption.  Fft: every slot.
+    enum class Codec { Sparse32, Sparse16, Direct32, Direct16, Fft };
+    struct RenormPlan {
+        Codec codec = Codec::Fft;
+        int P = 1;                           // members of a stacked input (stacks: Fft, their own encryptions)
+        int n_in = 2, n_out = 2, n_dec = 2;  // channels the codec reads, outputs, ciphertexts decrypted per member
+        int f = 0;                           // level of the outputs
+        bool per16 = false;                  // a period-16 pair
+        int snap = 1;                        // Fft: slots snapped per 16-slot row
+        int unpack = 0;                      // Fft: k_snap_slots gathers both outputs from channel 0
+        bool fold = false, sum_first = false;  // partners: decrypted and folded on the CRT limbs / summed first
+        // the re-encryption from this stream's pool of zero encryptions (zero_enc) where the snapped message
+        // is sparse; ld: log2 D of its NTT table (6: 32 slots of one channel, 5: 16 slots of each of two)
+        bool pooled = false;
+        int ld = 0;
+    };
+    // the decryption operands of up to two inputs
+    struct DecIn {
+        DecRaw dr;
+        int kd[2] = {0, 0};
+        CrtConsts cc[2];
+        double isc[2] = {1.0, 1.0};
+        bool need_s2 = false;
+    };
+
+    // every validation, before any allocation or launch
+    void renorm_check(const RenormSpec& sp) {
+        using Shape = RenormSpec::Shape;
         if (!d_pk_) throw std::runtime_error("keys not generated");
-        // slot_perm (pair, period 16): output slot i takes input slot slot_perm[i] -- a byte
-        // permutation such as ShiftRows folded into the renorm: the decode reads each output slot's
-        // value through the permuted root table, the encode writes slot i (no rotation, no level)
-        if (slot_perm) {  // a period-16 pair, or the unpacking renorm of one packed period-16 pair
-            const bool pair16 = !unpack && !single && period == 16, unpack16 = unpack == 16 && !single;
-            if (!(pair16 || unpack16) || ct(hh).nb > 1 || ct(hl).nb > 1)
-                throw std::runtime_error("renorm: a slot permutation needs a single period-16 state pair");
+        const bool one = sp.shape != Shape::Pair;
+        const Ct &hi = ct(sp.in[0]), &lo = ct(sp.in[one ? 0 : 1]);
+        const bool stacked = hi.nb > 1 || lo.nb > 1;
+        if (sp.perm) {
+            const bool pair16 = sp.shape == Shape::Pair && sp.period == 16, unpack16 = sp.shape == Shape::Unpack && sp.period == 16;
+            if (!(pair16 || unpack16) || stacked) throw std::runtime_error("renorm: a slot permutation needs a single period-16 state pair");
             for (int i = 0; i < 16; ++i)
-                if (slot_perm[i] < 0 || slot_perm[i] > 15) throw std::runtime_error("renorm: slot permutation entries must lie in [0, 16)");
-            // checked before any temporary is taken or launch issued
+                if (sp.perm[i] < 0 || sp.perm[i] > 15) throw std::runtime_error("renorm: slot permutation entries must lie in [0, 16)");
             if (unpack16 && !direct32_) throw std::runtime_error("renorm: a slot permutation needs the direct period-32 codec");
         }
-        if (pack_out && (unpack || single || period != 16 || ct(hh).nb > 1 || ct(hl).nb > 1))
-            throw std::runtime_error("renorm: the packed output needs a single period-16 state pair");
-        if (hc || hcl) {
-            const bool one = unpack || single;
-            if (one ? (hl != hh || hcl) : (!hc || !hcl)) throw std::runtime_error("renorm: conjugate partners: one per input channel");
+        if (sp.pack_out && (one || sp.period != 16 || stacked)) throw std::runtime_error("renorm: the packed output needs a single period-16 state pair");
+        if ((sp.conj[0] || sp.conj[1]) && (one ? sp.conj[1] != 0 : (!sp.conj[0] || !sp.conj[1])))
+            throw std::runtime_error("renorm: conjugate partners: one per input channel");
+        if (sp.shape == Shape::Unpack && (sp.period & (sp.period - 1) || sp.period < 16 || 2 * sp.period > slot_count()))
+            throw std::runtime_error("renorm: bad packed period");
+        if (sp.shape == Shape::Pair && sp.period > 0 && (sp.period & (sp.period - 1) || sp.period < 16 || sp.period > slot_count()))
+            throw std::runtime_error("renorm: bad period");
+        if (sp.shape == Shape::Pair && sp.period <= 0 && (sp.states < 1 || sp.states > slot_count() / 16))
+            throw std::runtime_error("renorm: states per ciphertext must be in [1, slot_count / 16]");
+        if (stacked && lo.nb != hi.nb) throw std::runtime_error("renorm: hi and lo stacks of different sizes");
+    }
+    RenormPlan renorm_plan(const RenormSpec& sp) {
+        using Shape = RenormSpec::Shape;
+        RenormPlan pl;
+        const bool one = sp.shape != Shape::Pair, single = sp.shape == Shape::Single;
+        const int stride = slot_count() / 16;
+        pl.P = ct(sp.in[0]).nb;
+        pl.per16 = !one && sp.period == 16;
+        const int states = one ? stride : sp.period > 0 ? (pl.per16 ? 1 : stride) : sp.states;
+        pl.f = sp.level < 0 ? hp_.fresh : std::min(sp.level, hp_.fresh);  // never above a fresh encryption
+        // Unpack / Single read ONE ciphertext: it is decrypted once and the codec runs on one input channel; a
+        // folded partner is decrypted as the second channel and added onto the first
+        pl.n_in = one ? 1 : 2;
+        pl.n_out = (single || sp.pack_out) ? 1 : 2;
+        if (sp.conj[0]) {
             auto same = [&](const Ct& a, const Ct& b) {
                 return a.nb == 1 && b.nb == 1 && a.level == b.level && a.pend == b.pend && vis_npoly(a) == vis_npoly(b) && a.npoly == b.npoly &&
                        a.lazy == b.lazy && !a.zero && !b.zero;
             };
-            if (!same(ct(hh), ct(hc)) || (!one && !same(ct(hl), ct(hcl)))) {
-                auto summed = [&](aesfhe_handle a, aesfhe_handle b) {
-                    Ct cj = conjugate(ct(b));
-                    Ct sm = add_sub(ct(a), cj, false);
-                    release(cj);
-                    return put_ct(sm);
-                };
-                const aesfhe_handle th = summed(hh, hc), tl = one ? th : summed(hl, hcl);
-                try {
-                    renorm_states(th, tl, states, oh, ol, level, period, unpack, single, packed_period, 0, 0, pack_out, slot_perm);
-                } catch (...) {
-                    free_handle(th);
-                    if (tl != th) free_handle(tl);
-                    throw;
-                }
-                free_handle(th);
-                if (tl != th) free_handle(tl);
-                return;
-            }
+            pl.fold = same(ct(sp.in[0]), ct(sp.conj[0])) && (one || same(ct(sp.in[1]), ct(sp.conj[1])));
+            pl.sum_first = !pl.fold;
         }
-        if (unpack || single) {
-            if (hl != hh) throw std::runtime_error("renorm: a packed / single renorm reads one ciphertext");
-            if (unpack && (unpack & (unpack - 1) || unpack < 16 || 2 * unpack > slot_count()))
-                throw std::runtime_error("renorm: bad packed period");
-            period = 0;
-            states = slot_count() / 16;  // every slot snapped (FFT codec)
+        pl.n_dec = (pl.fold && one) ? 2 : pl.n_in;
+        pl.unpack = sp.shape == Shape::Unpack ? sp.period : 0;
+        pl.snap = (pl.P > 1 && pl.per16) ? stride : states;
+        if (pl.P > 1) return pl;
+        const bool small = pool_k_ > 0 && hp_.nl(pl.f) <= kRenormMaxLimbs;
+        const bool d32 = direct32_ && (single ? sp.period == 32 : sp.shape == Shape::Unpack && sp.period == 16);
+        const bool sparse = sparse_dec_ && small && !pl.fold && !sp.perm;
+        if (sparse && d32 && single) pl.codec = Codec::Sparse32, pl.ld = 6;
+        else if (sparse && pl.per16 && !sp.pack_out) pl.codec = Codec::Sparse16, pl.ld = 5;
+        else if (d32) pl.codec = Codec::Direct32, pl.ld = single ? 6 : 5;
+        else if (states == 1) pl.codec = Codec::Direct16, pl.ld = sp.pack_out ? 6 : 5;
+        pl.pooled = small && pl.codec != Codec::Fft && (pl.codec != Codec::Direct16 || sp.pack_out || pl.per16);
+        if (!pl.pooled) pl.ld = 0;
+        return pl;
+    }
+    // the slot tables and codec buffers, made on the first renorm
+    void renorm_tables(bool fft) {
+        if (fft) ensure_slot_pos();
+        if (slots_.e[1] != 0) return;
+        const int s = slot_count(), stride = s / 16;
+        const u64 two_n = 2ull * hp_.n;
+        u64 e = 1;
+        for (int j = 0; j < s; ++j) {
+            if (j % stride == 0) slots_.e[j / stride] = (u32)e;
+            if (j < 16) slots_p_.e[j] = (u32)e;
+            if (j < 32) slots32_.e[j] = (u32)e;
+            e = e * 5 % two_n;
         }
-        if (period > 0) {
-            if (period & (period - 1) || period < 16 || period > slot_count()) throw std::runtime_error("renorm: bad period");
-            states = period == 16 ? 1 : slot_count() / 16;
+        for (int k = 0; k < kStreams; ++k) {
+            d_codec_[k] = (double*)dev_alloc(2 * 64 * 2);  // two accumulators acc[64], or acc + w (AESFHE_SNAP_ENCODE=0)
+            // zeroed on the stream the codec launches run on, ordered before the first decode
+            // (hipMemset on the null stream does not order a hipStreamNonBlocking stream); from
+            // then on each snapping encode zeroes the other accumulator (kernels.h launch_decode16 / 32)
+            HIP_OK(hipMemsetAsync(d_codec_[k], 0, 2 * 64 * sizeof(double), S()));
+            HIP_OK(hipStreamSynchronize(S()));
+            d_nib_[k] = (int*)dev_alloc(32);
         }
-        const bool per16 = period == 16;
-        if (level > hp_.fresh) level = hp_.fresh;  // never above a fresh encryption
-        const int n = hp_.n, s = slot_count(), stride = s / 16;
-        if (states < 1 || states > stride)
-            throw std::runtime_error("renorm: states per ciphertext must be in [1, slot_count / 16]");
-        if (states > 1 || ct(hh).nb > 1) ensure_slot_pos();
-        if (slots_.e[1] == 0) {
-            const u64 two_n = 2ull * n;
-            u64 e = 1;
-            for (int j = 0; j < s; ++j) {
-                if (j % stride == 0) slots_.e[j / stride] = (u32)e;
-                if (j < 16) slots_p_.e[j] = (u32)e;
-                if (j < 32) slots32_.e[j] = (u32)e;
-                e = e * 5 % two_n;
-            }
-            for (int k = 0; k < kStreams; ++k) {
-                d_codec_[k] = (double*)dev_alloc(2 * 64 * 2);  // two accumulators acc[64], or acc + w (AESFHE_SNAP_ENCODE=0)
-                // zeroed on the stream the codec launches run on, ordered before the first decode
-                // (hipMemset on the null stream does not order a hipStreamNonBlocking stream); from
-                // then on each snapping encode zeroes the other accumulator (kernels.h launch_decode16 / 32)
-                HIP_OK(hipMemsetAsync(d_codec_[k], 0, 2 * 64 * sizeof(double), S()));
-                HIP_OK(hipStreamSynchronize(S()));
-                d_nib_[k] = (int*)dev_alloc(32);
-            }
+    }
+    // channel w of d: src in NTT form with its CRT limbs (2..4, rescaled until 4 are enough), constants and
+    // inverse scale; a copy the renorm made is G's
+    void renorm_input(const Ct& src, int w, DecIn& d, Guard& G) {
+        Ct c = ensure_ntt(src);
+        if (c.data != src.data) G.own(c);
+        int kd = crt_limbs(c);
+        if (!kd) {
+            const Ct nc = normalize(c, true);
+            if (nc.data != c.data) G.own(nc);
+            c = nc;
+            kd = crt_limbs(c);
         }
-        const int P = ct(hh).nb;
-        if (P > 1 || ct(hl).nb > 1) {
-            if (ct(hl).nb != P) throw std::runtime_error("renorm: hi and lo stacks of different sizes");
-            renorm_stacked(hh, hl, period == 16 ? stride : states, oh, ol, level, unpack, single);
-            return;
-        }
-        u32* x = tmp(8);  // [2][4][N]
-        int kd[2];
-        CrtConsts cc[2];
-        double isc[2];
-        const aesfhe_handle in[2] = {hh, (hc && (unpack || single)) ? hc : hl};
-        // unpack / single read ONE ciphertext: it is decrypted once and the codec runs on one input
-        // channel (k_snap_slots' unpack gathers both outputs from channel 0; single has one output);
-        // a conjugate partner is decrypted as the second channel and folded into the first
-        const int n_in = (unpack || single) ? 1 : 2, n_out = (single || pack_out) ? 1 : 2, n_dec = (hc && n_in == 1) ? 2 : n_in;
-        kd[1] = 0;
-        // raw decryption of the inputs: ONE launch forms c0 + c1 s (+ c2 s^2) on the CRT limbs of
-        // both, one inverse NTT when their limb counts agree
-        DecRaw dr;
-        Ct dc[2];
-        bool down[2] = {false, false};
-        bool need_s2 = false;
-        for (int w = 0; w < n_dec; ++w) {
-            Ct c = ensure_ntt(ct(in[w]));
-            bool own = c.data != ct(in[w]).data;
-            kd[w] = crt_limbs(c);
-            if (!kd[w]) {
-                Ct nc = normalize(c, true);
-                if (own) release(c);
-                c = nc, own = nc.data != ct(in[w]).data;
-                kd[w] = crt_limbs(c);
-            }
-            dc[w] = c, down[w] = own;
-            dr.ct[w] = c.data, dr.npoly[w] = c.npoly, dr.nlc[w] = hp_.nl(c.level), dr.kd[w] = kd[w];
-            need_s2 = need_s2 || c.npoly == 3;
-            cc[w] = crt_consts(kd[w]);
-            isc[w] = 1.0 / (c.level >= 0 ? raw_scale(c.level, c.pend) : 1.0);
-            cnt_[C_DEC]++;
-        }
-        // the sparse decryption (round 6, AESFHE_SPARSE_DEC, default on with the pool): the packed period-32
-        // renorm and the periodic pair renorm decode only the D subring coefficients the snapped message can
-        // have (launch_renorm_sparse: block sums of c0 + c1 s, a D-point inverse transform, the CRT, the
-        // slots, the snap and the message's NTT table in TWO launches), then the pooled re-encryption: three
-        // launches for the whole renorm instead of six (dec_raw, the INTT's two passes, decode, table, combine)
-        {
-            const int fs = level < 0 ? hp_.fresh : level;
-            const bool one = direct32_ && single && packed_period == 32 && n_in == 1 && n_out == 1;
-            const bool two = states == 1 && per16 && !pack_out && !unpack && !single && n_in == 2 && n_out == 2;
-            if (sparse_dec_ && pool_k_ > 0 && !hc && !slot_perm && hp_.nl(fs) <= kRenormMaxLimbs && (one || two)) {
-                SparseDec sd;
-                for (int w = 0; w < n_in; ++w) sd.kd[w] = kd[w], sd.cc[w] = cc[w];
-                u32* W = renorm_w();
-                launch_renorm_sparse(S(), T_, W, renorm_b(), dr, n_in, sd, slots32_, slots_p_, hp_.delta[fs], hp_.nl(fs), gtab(one ? 64 : 32), d_s_,
-                                     need_s2 ? s_sq4() : d_s_);
-                for (int w = 0; w < n_dec; ++w)
-                    if (down[w]) release(dc[w]);
-                RenormOut ro;
-                Ct outs[2];
-                for (int c = 0; c < n_out; ++c) {
-                    outs[c] = alloc_ct(fs, 2);
-                    ro.pool[c] = zero_enc(fs);
-                    ro.out[c] = outs[c].data;
-                }
-                launch_renorm_combine(S(), T_, ro, n_out, W, hp_.nl(fs), one ? 6 : 5);
-                retire_pools();
-                cnt_[C_ENC] += n_out;
-                *oh = put_ct(outs[0]);
-                if (n_out == 2) *ol = put_ct(outs[1]);
-                untmp(x, 8);
-                return;
-            }
-        }
-        launch_dec_raw(S(), T_, x, dr, n_dec, d_s_, need_s2 ? s_sq4() : d_s_);
-        if (hc && n_in == 1) {
-            if (kd[1] != kd[0] || isc[1] != isc[0]) throw std::runtime_error("renorm: conjugate partner at another scale");
-            u32* cj = tmp(kd[0]);
-            launch_automorph(S(), T_, cj, x + (size_t)4 * n, conj_galois(), kd[0]);
-            launch_add(S(), T_, x, x, cj, kd[0], kd[0], qmap());
-            untmp(cj, kd[0]);
-            cnt_[C_CONJ]++;
-        } else if (hc) {  // pair: the partners of both channels in a second raw decryption
-            DecRaw d2;
-            Ct pc[2];
-            bool pown[2] = {false, false}, ps2 = false;
-            const aesfhe_handle ph[2] = {hc, hcl};
+        d.dr.ct[w] = c.data, d.dr.npoly[w] = pm(c), d.dr.nlc[w] = hp_.nl(c.level), d.dr.kd[w] = kd;
+        d.dr.ms[w] = (size_t)pm(c) * hp_.nl(c.level) * hp_.n;
+        d.need_s2 = d.need_s2 || pm(c) == 3;
+        d.kd[w] = kd, d.cc[w] = crt_consts(kd);
+        d.isc[w] = 1.0 / (c.level >= 0 ? raw_scale(c.level, c.pend) : 1.0);
+    }
+    // x[channel][4][N]: c0 + c1 s (+ c2 s^2) of every input on its CRT limbs, in ONE launch
+    void renorm_dec_raw(u32* x, const DecIn& d, int nch) { launch_dec_raw(S(), T_, x, d.dr, nch, d_s_, d.need_s2 ? s_sq4() : d_s_); }
+    // x += conj(xc) on kd limbs: the partner's raw decryption through X -> X^-1, NTT form
+    void renorm_fold(u32* x, const u32* xc, u32* cj, int kd) {
+        launch_automorph(S(), T_, cj, xc, conj_galois(), kd);
+        launch_add(S(), T_, x, x, cj, kd, kd, qmap());
+        cnt_[C_CONJ]++;
+    }
+    // the raw decryption of in[] (and the folded partners) as coefficients: x [n_in P][4][N]
+    u32* renorm_decrypt(const RenormSpec& sp, const RenormPlan& pl, const DecIn& d, Guard& G) {
+        const int n = hp_.n, chin = pl.n_in * pl.P;
+        const int* kd = d.kd;
+        u32* x = G.get((size_t)4 * std::max(2, pl.n_dec * pl.P));
+        renorm_dec_raw(x, d, pl.n_dec);
+        if (pl.fold && pl.n_in == 1) {
+            renorm_fold(x, x + (size_t)4 * n, G.get(kd[0]), kd[0]);
+        } else if (pl.fold) {  // pair: the partners of both channels in a second raw decryption
+            DecIn d2;
             for (int w = 0; w < 2; ++w) {
-                Ct c = ensure_ntt(ct(ph[w]));
-                bool own = c.data != ct(ph[w]).data;
-                if (!crt_limbs(c)) {
-                    Ct nc = normalize(c, true);
-                    if (own) release(c);
-                    c = nc, own = nc.data != ct(ph[w]).data;
-                }
-                if (crt_limbs(c) != kd[w] || 1.0 / (c.level >= 0 ? raw_scale(c.level, c.pend) : 1.0) != isc[w])
-                    throw std::runtime_error("renorm: conjugate partner at another scale");
-                pc[w] = c, pown[w] = own;
-                d2.ct[w] = c.data, d2.npoly[w] = c.npoly, d2.nlc[w] = hp_.nl(c.level), d2.kd[w] = kd[w];
-                ps2 = ps2 || c.npoly == 3;
+                renorm_input(ct(sp.conj[w]), w, d2, G);
+                if (d2.kd[w] != kd[w] || d2.isc[w] != d.isc[w]) throw std::runtime_error("renorm: conjugate partner at another scale");
             }
-            u32* xc = tmp(8);
-            launch_dec_raw(S(), T_, xc, d2, 2, d_s_, ps2 ? s_sq4() : d_s_);
-            u32* cj = tmp(std::max(kd[0], kd[1]));
-            for (int w = 0; w < 2; ++w) {
-                launch_automorph(S(), T_, cj, xc + (size_t)w * 4 * n, conj_galois(), kd[w]);
-                launch_add(S(), T_, x + (size_t)w * 4 * n, x + (size_t)w * 4 * n, cj, kd[w], kd[w], qmap());
-                cnt_[C_CONJ]++;
-            }
-            untmp(cj, std::max(kd[0], kd[1]));
-            untmp(xc, 8);
-            for (int w = 0; w < 2; ++w)
-                if (pown[w]) release(pc[w]);
+            u32* xc = G.get(8);
+            renorm_dec_raw(xc, d2, 2);
+            u32* cj = G.get(std::max(kd[0], kd[1]));
+            for (int w = 0; w < 2; ++w) renorm_fold(x + (size_t)w * 4 * n, xc + (size_t)w * 4 * n, cj, kd[w]);
         }
-        if (n_in == 2 && kd[0] == kd[1]) {
-            intt(x, x, 2 * kd[0], RowMap{kd[0], 4, 4, 0, 0}, qmap());
-        } else {
-            for (int w = 0; w < n_in; ++w) intt(x + (size_t)w * 4 * n, kd[w], kd[w], qmap());
+        // one inverse NTT when the inputs' limb counts agree
+        if (chin > 1 && (pl.n_in == 1 || kd[0] == kd[1])) return intt(x, x, chin * kd[0], RowMap{kd[0], 4, 4, 0, 0}, qmap()), x;
+        for (int w = 0; w < pl.n_in; ++w) {
+            u32* xw = x + (size_t)w * pl.P * 4 * n;
+            if (pl.P > 1) intt(xw, xw, pl.P * kd[w], RowMap{kd[w], 4, 4, 0, 0}, qmap());
+            else intt(xw, kd[w], kd[w], qmap());
         }
-        for (int w = 0; w < n_dec; ++w)
-            if (down[w]) release(dc[w]);
-        const int f = level < 0 ? hp_.fresh : level, nq = hp_.nl(f) + 1;
-        const double enc_scale = hp_.delta[f] * (double)hp_.mod[hp_.nl(f)];
-        const bool direct32 = direct32_ && ((unpack == 16) || (single && packed_period == 32));
-        // the re-encryption from this stream's pool of zero encryptions (zero_enc) where the snapped
-        // message is sparse: the direct period-32 / period-16 codecs (pooled_ok)
-        const bool pooled = pool_k_ > 0 && hp_.nl(f) <= kRenormMaxLimbs && (direct32 || (states == 1 && (pack_out || per16)));
-        u32* m = pooled ? nullptr : tmp(2 * (size_t)nq);
-        u32* W = pooled ? renorm_w() : nullptr;
-        int ld = 0;  // log2 D of the pooled message
+        return x;
+    }
+    // the sparse decryption straight to the snapped message's NTT table W
+    void renorm_sparse(const RenormPlan& pl, const DecIn& d, u32* W) {
+        SparseDec sd;
+        for (int w = 0; w < pl.n_in; ++w) sd.kd[w] = d.kd[w], sd.cc[w] = d.cc[w];
+        const u32* s2 = d.need_s2 ? s_sq4() : d_s_;
+        launch_renorm_sparse(S(), T_, W, renorm_b(), d.dr, pl.n_in, sd, slots32_, slots_p_, hp_.delta[pl.f], hp_.nl(pl.f), gtab(1 << pl.ld), d_s_, s2);
+    }
+    // the direct codecs: the 32 (Direct32) or 2 x 16 (Direct16) slots decoded one by one and snapped, the
+    // message written as its NTT table W (pooled) or its coefficients m
+    void renorm_direct(const RenormSpec& sp, const RenormPlan& pl, const u32* x, const DecIn& d, u32* W, u32* m) {
+        const int nl = hp_.nl(pl.f), nq = nl + 1;
+        const double enc_scale = hp_.delta[pl.f] * (double)hp_.mod[nl];
         // the snap inside the encode (AESFHE_SNAP_ENCODE, default on): the two accumulators of this
         // stream alternate -- this renorm decodes into one, its encode snaps from it and zeroes the other
         double* acc = d_codec_[t_sidx] + (snap_encode_ ? 64 * codec_flip_[t_sidx] : 0);
         double* zacc = snap_encode_ ? d_codec_[t_sidx] + 64 * (1 - codec_flip_[t_sidx]) : nullptr;
         double* wv = snap_encode_ ? acc : d_codec_[t_sidx] + 64;
-        if (slot_perm && unpack && !direct32) throw std::runtime_error("renorm: a slot permutation needs the direct period-32 codec");
-        // the message's NTT table instead of its coefficients (pooled): 32 slots of one channel (D = 64),
-        // or 16 periodic slots of each of two channels (D = 32)
-        auto wtab = [&](bool one32, const Slot16& s16) {
-            if (one32) launch_renorm_wtab32(S(), T_, W, wv, zacc, slots32_, hp_.delta[f], hp_.nl(f), gtab(64)), ld = 6;
-            else launch_renorm_wtab16(S(), T_, W, wv, zacc, s16, hp_.delta[f], hp_.nl(f), gtab(32)), ld = 5;
+        // the message's NTT table instead of its coefficients: 32 slots of one channel (D = 64), or 16
+        // periodic slots of each of two channels (D = 32)
+        auto wtab = [&]() {
+            if (pl.ld == 6) launch_renorm_wtab32(S(), T_, W, wv, zacc, slots32_, hp_.delta[pl.f], nl, gtab(64));
+            else launch_renorm_wtab16(S(), T_, W, wv, zacc, slots_p_, hp_.delta[pl.f], nl, gtab(32));
         };
-        if (direct32) {
+        if (pl.codec == Codec::Direct32) {
             // the 32 slots of the packed period-32 state: one direct decode, the snap as 2 x 16, and
-            // either the two 16-periodic halves (unpack) or the 32-periodic whole (single); a slot
+            // either the two 16-periodic halves (Unpack) or the 32-periodic whole (Single); a slot
             // permutation applies within each 16-slot half (hi, lo)
             Slot32 sp32 = slots32_;
-            if (slot_perm)
-                for (int j = 0; j < 32; ++j) sp32.e[j] = slots32_.e[16 * (j / 16) + slot_perm[j % 16]];
-            launch_decode32(S(), T_, x, kd[0], cc[0], sp32, isc[0], acc);
+            if (sp.perm)
+                for (int j = 0; j < 32; ++j) sp32.e[j] = slots32_.e[16 * (j / 16) + sp.perm[j % 16]];
+            launch_decode32(S(), T_, x, d.kd[0], d.cc[0], sp32, d.isc[0], acc);
             if (!snap_encode_) launch_snap16(S(), acc, wv, d_nib_[t_sidx]);
-            if (pooled) wtab(!unpack, slots_p_);
-            else if (unpack) launch_encode16(S(), T_, m, wv, slots_p_, enc_scale, nq, true, zacc);
+            if (pl.pooled) wtab();
+            else if (pl.unpack) launch_encode16(S(), T_, m, wv, slots_p_, enc_scale, nq, true, zacc);
             else launch_encode32(S(), T_, m, wv, slots32_, enc_scale, nq, zacc);
-            if (snap_encode_) codec_flip_[t_sidx] ^= 1;
-        } else if (states == 1) {
-            const Slot16& sl = per16 ? slots_p_ : slots_;
-            Slot16 sp = sl;
-            if (slot_perm)
-                for (int i = 0; i < 16; ++i) sp.e[i] = sl.e[slot_perm[i]];
-            launch_decode16(S(), T_, x, kd, cc, sp, isc, acc);
-            if (!snap_encode_) launch_snap16(S(), acc, wv, d_nib_[t_sidx]);
-            if (pooled) wtab(pack_out, sl);
-            else if (pack_out) launch_encode32(S(), T_, m, wv, slots32_, enc_scale, nq, zacc);  // acc[c][i] = packed slot 16 c + i
-            else launch_encode16(S(), T_, m, wv, sl, enc_scale, nq, per16, zacc);
-            if (snap_encode_) codec_flip_[t_sidx] ^= 1;
         } else {
-            double*& zbuf = d_fft_[t_sidx];
-            if (!zbuf) zbuf = (double*)dev_alloc((size_t)2 * 2 * 2 * 2 * n);  // 2 buffers x [2][N] complex double
-            double* z = zbuf;
-            double* w = zbuf + (size_t)2 * 2 * n;
-            if (n_in == 1) cc[1] = cc[0], isc[1] = isc[0];
-            launch_decode_twist(S(), T_, x, kd, cc, isc, z, n_in);
-            launch_fft2(S(), T_, z, 1, n_in);
-            launch_snap_slots(S(), T_, z, w, d_slot_pos_, states, unpack, n_out);
-            launch_fft2(S(), T_, w, -1, n_out);
-            launch_encode_untwist(S(), T_, m, w, enc_scale, nq, n_out);
+            const Slot16& sl = pl.per16 ? slots_p_ : slots_;
+            Slot16 sp16 = sl;
+            if (sp.perm)
+                for (int i = 0; i < 16; ++i) sp16.e[i] = sl.e[sp.perm[i]];
+            launch_decode16(S(), T_, x, d.kd, d.cc, sp16, d.isc, acc);
+            if (!snap_encode_) launch_snap16(S(), acc, wv, d_nib_[t_sidx]);
+            if (pl.pooled) wtab();  // pooled: a period-16 pair (sl is slots_p_)
+            else if (sp.pack_out) launch_encode32(S(), T_, m, wv, slots32_, enc_scale, nq, zacc);  // acc[c][i] = packed slot 16 c + i
+            else launch_encode16(S(), T_, m, wv, sl, enc_scale, nq, pl.per16, zacc);
         }
-        if (pooled) {
-            // out_c = a pooled encryption of zero at level f + the message's NTT (one launch for both)
-            RenormOut ro;
-            Ct outs[2];
-            for (int c = 0; c < n_out; ++c) {
-                outs[c] = alloc_ct(f, 2);
-                ro.pool[c] = zero_enc(f);
-                ro.out[c] = outs[c].data;
-            }
-            launch_renorm_combine(S(), T_, ro, n_out, W, hp_.nl(f), ld);
-            retire_pools();
-            cnt_[C_ENC] += n_out;
-            *oh = put_ct(outs[0]);
-            if (n_out == 2) *ol = put_ct(outs[1]);
-            untmp(x, 8);
+        if (snap_encode_) codec_flip_[t_sidx] ^= 1;
+    }
+    // the FFT codec (stacks §3.16): the n_in P channels of x decoded into z, every kept slot
+    // snapped into the n_out P channels of w, w re-encoded as the coefficient-form messages m
+    void renorm_fft(const RenormPlan& pl, const u32* x, DecIn& d, double* z, double* w, u32* m) {
+        const int chin = pl.n_in * pl.P, chout = pl.n_out * pl.P, nl = hp_.nl(pl.f);
+        if (pl.n_in == 1) d.kd[1] = d.kd[0], d.cc[1] = d.cc[0], d.isc[1] = d.isc[0];
+        launch_decode_twist(S(), T_, x, d.kd, d.cc, d.isc, z, chin, pl.P);
+        launch_fft2(S(), T_, z, 1, chin);
+        launch_snap_slots(S(), T_, z, w, d_slot_pos_, pl.snap, pl.unpack, chout, pl.P);
+        launch_fft2(S(), T_, w, -1, chout);
+        launch_encode_untwist(S(), T_, m, w, hp_.delta[pl.f] * (double)hp_.mod[nl], nl + 1, chout);
+    }
+    // out_c = a pooled encryption of zero at level f + the message's NTT table (one launch for both)
+    void renorm_emit_pooled(const RenormPlan& pl, const u32* W, aesfhe_handle* oh, aesfhe_handle* ol) {
+        Guard G(*this);
+        RenormOut ro;
+        Ct outs[2];
+        for (int c = 0; c < pl.n_out; ++c) {
+            outs[c] = alloc_ct(pl.f, 2);
+            G.own(outs[c]);
+            ro.pool[c] = zero_enc(pl.f);
+            ro.out[c] = outs[c].data;
+        }
+        launch_renorm_combine(S(), T_, ro, pl.n_out, W, hp_.nl(pl.f), pl.ld);
+        retire_pools();
+        cnt_[C_ENC] += pl.n_out;
+        G.nc = 0;  // the outputs leave with the caller
+        *oh = put_ct(outs[0]);
+        if (pl.n_out == 2) *ol = put_ct(outs[1]);
+    }
+    // every re-encryption in one set of launches, the coefficient-form messages added to e0; the outputs of
+    // stacks are stacks again (hi = members [0, P), lo = [P, 2P) of the encryption)
+    void renorm_emit_encrypted(const RenormPlan& pl, const u32* m, aesfhe_handle* oh, aesfhe_handle* ol) {
+        Ct enc = encrypt_many(m, pl.n_out * pl.P, (size_t)(hp_.nl(pl.f) + 1) * hp_.n, pl.f, true);
+        if (pl.n_out == 1) {
+            if (pl.P == 1) enc.nb = 1;
+            *oh = put_ct(enc);
             return;
         }
-        // both re-encryptions in one set of launches, the coefficient-form message added to e0
-        Ct enc = encrypt_many(m, n_out, (size_t)nq * n, f, true);
-        if (n_out == 1) {
-            enc.nb = 1;
-            *oh = put_ct(enc);
-        } else {
-            Ct parts[2];
+        Guard G(*this);
+        G.own(enc);
+        Ct parts[2];
+        if (pl.P == 1) {
             const int idx[2] = {0, 1};
             unstack(enc, parts, idx);
-            release(enc);
-            *oh = put_ct(parts[0]);
-            *ol = put_ct(parts[1]);
+        } else {
+            parts[0] = members_of(enc, 0, pl.P);
+            parts[1] = members_of(enc, pl.P, pl.P);
         }
-        untmp(m, 2 * (size_t)nq);
-        untmp(x, 8);
+        *oh = put_ct(parts[0]);
+        *ol = put_ct(parts[1]);
+    }
+    void renorm(const RenormSpec& sp, aesfhe_handle* oh, aesfhe_handle* ol) {
+        renorm_check(sp);
+        const RenormPlan pl = renorm_plan(sp);
+        renorm_tables(pl.snap > 1 || pl.P > 1);
+        Guard G(*this);
+        Ct in[2] = {ct(sp.in[0]), ct(sp.in[pl.n_in - 1])};
+        for (int w = 0; pl.sum_first && w < pl.n_in; ++w) {
+            const Ct cj = conjugate(ct(sp.conj[w]));
+            G.own(cj);
+            G.own(in[w] = add_sub(in[w], cj, false));
+        }
+        DecIn d;
+        d.dr.members = pl.P;
+        for (int w = 0; w < pl.n_dec; ++w) {
+            renorm_input(w < pl.n_in ? in[w] : ct(sp.conj[0]), w, d, G);
+            cnt_[C_DEC] += pl.P;
+        }
+        if (pl.n_dec > pl.n_in && (d.kd[1] != d.kd[0] || d.isc[1] != d.isc[0])) throw std::runtime_error("renorm: conjugate partner at another scale");
+        u32* W = pl.pooled ? renorm_w() : nullptr;
+        if (pl.codec == Codec::Sparse32 || pl.codec == Codec::Sparse16) {
+            renorm_sparse(pl, d, W);
+            return renorm_emit_pooled(pl, W, oh, ol);
+        }
+        const u32* x = renorm_decrypt(sp, pl, d, G);
+        u32* m = pl.pooled ? nullptr : G.get((size_t)(pl.P > 1 ? pl.n_out * pl.P : 2) * (hp_.nl(pl.f) + 1));
+        if (pl.codec != Codec::Fft) {
+            renorm_direct(sp, pl, x, d, W, m);
+        } else if (pl.P > 1) {
+            // fp64 codec buffers: a complex double is 4 words, so a channel of N values is 4 rows
+            u32* zb = G.get((size_t)4 * pl.n_in * pl.P);
+            u32* wb = G.get((size_t)4 * pl.n_out * pl.P);
+            renorm_fft(pl, x, d, (double*)zb, (double*)wb, m);
+        } else {
+            double*& zbuf = d_fft_[t_sidx];
+            if (!zbuf) zbuf = (double*)dev_alloc((size_t)2 * 2 * 2 * 2 * hp_.n);  // 2 buffers x [2][N] complex double
+            renorm_fft(pl, x, d, zbuf, zbuf + (size_t)2 * 2 * hp_.n, m);
+        }
+        if (pl.pooled) renorm_emit_pooled(pl, W, oh, ol);
+        else renorm_emit_encrypted(pl, m, oh, ol);
     }
 
     // ---- pooled zero encryptions for the renorm (AESFHE_RENORM_POOL = K per refill, default 16; 0: every
@@ -3654,79 +3718,6 @@ public:
         for (int j = 0; j < s; ++j) pos[j] = (u32)((e - 1) / 2), e = e * 5 % two_n;
         d_slot_pos_ = dev_alloc(s);
         HIP_OK(hipMemcpy(d_slot_pos_, pos.data(), sizeof(u32) * s, hipMemcpyHostToDevice));
-    }
-    // the renorm of P stacked state pairs (multi-pair batches): every member's
-    // channels in ONE set of launches -- one raw decryption, one inverse NTT, the fp64 FFT codec
-    // over all n_in P channels (states = the slots snapped per 16-slot row, as renorm_states), one
-    // encryption of all n_out P messages -- and the outputs as stacks again (hi = members
-    // [0, P), lo = [P, 2P) of the encryption).  Same snapped values as P single renorms.
-    void renorm_stacked(aesfhe_handle hh, aesfhe_handle hl, int states, aesfhe_handle* oh, aesfhe_handle* ol, int level, int unpack,
-                        bool single) {
-        const int n = hp_.n, P = ct(hh).nb;
-        const int n_in = (unpack || single) ? 1 : 2, n_out = single ? 1 : 2;
-        int kd[2] = {0, 0};
-        CrtConsts cc[2];
-        double isc[2] = {1.0, 1.0};
-        DecRaw dr;
-        dr.members = P;
-        Ct dc[2];
-        bool down[2] = {false, false}, need_s2 = false;
-        const aesfhe_handle in[2] = {hh, hl};
-        for (int w = 0; w < n_in; ++w) {
-            Ct c = ensure_ntt(ct(in[w]));
-            bool own = c.data != ct(in[w]).data;
-            kd[w] = crt_limbs(c);
-            if (!kd[w]) {
-                Ct nc = normalize(c, true);
-                if (own) release(c);
-                c = nc, own = nc.data != ct(in[w]).data;
-                kd[w] = crt_limbs(c);
-            }
-            dc[w] = c, down[w] = own;
-            dr.ct[w] = c.data, dr.npoly[w] = pm(c), dr.nlc[w] = hp_.nl(c.level), dr.kd[w] = kd[w];
-            dr.ms[w] = (size_t)pm(c) * hp_.nl(c.level) * n;
-            need_s2 = need_s2 || pm(c) == 3;
-            cc[w] = crt_consts(kd[w]);
-            isc[w] = 1.0 / (c.level >= 0 ? raw_scale(c.level, c.pend) : 1.0);
-            cnt_[C_DEC] += P;
-        }
-        if (n_in == 1) kd[1] = kd[0], cc[1] = cc[0], isc[1] = isc[0];
-        const int chin = n_in * P, chout = n_out * P;
-        u32* x = tmp((size_t)4 * chin);  // [channel][4][N]
-        launch_dec_raw(S(), T_, x, dr, n_in, d_s_, need_s2 ? s_sq4() : d_s_);
-        if (kd[0] == kd[1] || n_in == 1) {
-            intt(x, x, chin * kd[0], RowMap{kd[0], 4, 4, 0, 0}, qmap());
-        } else {
-            for (int w = 0; w < n_in; ++w) intt(x + (size_t)w * P * 4 * n, x + (size_t)w * P * 4 * n, P * kd[w], RowMap{kd[w], 4, 4, 0, 0}, qmap());
-        }
-        for (int w = 0; w < n_in; ++w)
-            if (down[w]) release(dc[w]);
-        ensure_slot_pos();
-        const int f = level < 0 ? hp_.fresh : level, nq = hp_.nl(f) + 1;
-        const double enc_scale = hp_.delta[f] * (double)hp_.mod[hp_.nl(f)];
-        // fp64 codec buffers: a complex double is 4 words, so a channel of N values is 4 rows
-        u32* zb = tmp((size_t)4 * chin);
-        u32* wb = tmp((size_t)4 * chout);
-        double* z = (double*)zb;
-        double* wv = (double*)wb;
-        launch_decode_twist(S(), T_, x, kd, cc, isc, z, chin, P);
-        launch_fft2(S(), T_, z, 1, chin);
-        launch_snap_slots(S(), T_, z, wv, d_slot_pos_, states, unpack, chout, P);
-        launch_fft2(S(), T_, wv, -1, chout);
-        u32* m = tmp((size_t)chout * nq);
-        launch_encode_untwist(S(), T_, m, wv, enc_scale, nq, chout);
-        untmp(zb, (size_t)4 * chin);
-        untmp(wb, (size_t)4 * chout);
-        untmp(x, (size_t)4 * chin);
-        Ct enc = encrypt_many(m, chout, (size_t)nq * n, f, true);
-        untmp(m, (size_t)chout * nq);
-        if (n_out == 1) {
-            *oh = put_ct(enc);
-            return;
-        }
-        *oh = put_ct(members_of(enc, 0, P));
-        *ol = put_ct(members_of(enc, P, P));
-        release(enc);
     }
 
     // ------------------------------------------------------------------ bootstrapping
@@ -5983,75 +5974,82 @@ int aesfhe_boot_info(aesfhe_ctx* ctx, double* out) {
     e.boot_info(out);
     API_END
 }
+using RenormSpec = Engine::RenormSpec;
+static const int32_t* perm_of(const int32_t* perm16, const char* who) {
+    if (!perm16) throw std::runtime_error(std::string(who) + ": no permutation");
+    return perm16;
+}
+static void both_or_none(aesfhe_handle a, aesfhe_handle b, const char* who) {
+    if ((a != 0) != (b != 0)) throw std::runtime_error(std::string(who) + ": give both conjugate partners or none");
+}
+static void packed_period(int period) {
+    if (period < 16 || (period & (period - 1))) throw std::runtime_error("renorm_packed: period must be a power of two >= 16");
+}
 int aesfhe_renorm_pair(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, aesfhe_handle* out_hi, aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_pair(hi, lo, out_hi, out_lo);
+    API_BEGIN ctx->eng->renorm(RenormSpec::pair(hi, lo, -1), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_periodic(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, int period, int level, aesfhe_handle* out_hi,
                            aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(hi, lo, 1, out_hi, out_lo, level, period);
+    API_BEGIN ctx->eng->renorm(RenormSpec::pair(hi, lo, level).with_period(period), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_unpack(aesfhe_ctx* ctx, aesfhe_handle packed, int period, int level, aesfhe_handle* out_hi, aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(packed, packed, 1, out_hi, out_lo, level, 0, period);
+    API_BEGIN ctx->eng->renorm(RenormSpec::unpack(packed, period, level), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_unpack_perm(aesfhe_ctx* ctx, aesfhe_handle packed, aesfhe_handle packed_conj, const int32_t* perm16, int period, int level,
                               aesfhe_handle* out_hi, aesfhe_handle* out_lo) {
-    API_BEGIN if (!perm16) throw std::runtime_error("renorm_unpack_perm: no permutation");
-    int p[16];
-    for (int i = 0; i < 16; ++i) p[i] = perm16[i];
-    ctx->eng->renorm_states(packed, packed, 1, out_hi, out_lo, level, 0, period, false, 0, packed_conj, 0, false, p);
+    API_BEGIN const int32_t* p = perm_of(perm16, "renorm_unpack_perm");
+    ctx->eng->renorm(RenormSpec::unpack(packed, period, level).with_conj(packed_conj).with_perm(p), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_periodic_perm(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, aesfhe_handle hi_conj, aesfhe_handle lo_conj,
                                 const int32_t* perm16, int pack_out, int period, int level, aesfhe_handle* out_hi, aesfhe_handle* out_lo) {
-    API_BEGIN if ((hi_conj != 0) != (lo_conj != 0)) throw std::runtime_error("renorm_periodic_perm: give both conjugate partners or none");
-    if (!perm16) throw std::runtime_error("renorm_periodic_perm: no permutation");
-    int p[16];
-    for (int i = 0; i < 16; ++i) p[i] = perm16[i];
-    ctx->eng->renorm_states(hi, lo, 1, out_hi, pack_out ? nullptr : out_lo, level, period, 0, false, 0, hi_conj, lo_conj, pack_out != 0, p);
+    API_BEGIN both_or_none(hi_conj, lo_conj, "renorm_periodic_perm");
+    const int32_t* p = perm_of(perm16, "renorm_periodic_perm");
+    ctx->eng->renorm(RenormSpec::pair(hi, lo, level).with_period(period).with_conj(hi_conj, lo_conj).with_perm(p).with_pack(pack_out != 0), out_hi,
+                     pack_out ? nullptr : out_lo);
     API_END
 }
 int aesfhe_renorm_pack(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, aesfhe_handle hi_conj, aesfhe_handle lo_conj, int period, int level,
                        aesfhe_handle* out) {
-    API_BEGIN if ((hi_conj != 0) != (lo_conj != 0)) throw std::runtime_error("renorm_pack: give both conjugate partners or none");
-    ctx->eng->renorm_states(hi, lo, 1, out, nullptr, level, period, 0, false, 0, hi_conj, lo_conj, true);
+    API_BEGIN both_or_none(hi_conj, lo_conj, "renorm_pack");
+    ctx->eng->renorm(RenormSpec::pair(hi, lo, level).with_period(period).with_conj(hi_conj, lo_conj).with_pack(true), out, nullptr);
     API_END
 }
 int aesfhe_renorm_periodic_conj(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, aesfhe_handle hi_conj, aesfhe_handle lo_conj, int period,
                                 int level, aesfhe_handle* out_hi, aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(hi, lo, 1, out_hi, out_lo, level, period, 0, false, 0, hi_conj, lo_conj);
+    API_BEGIN ctx->eng->renorm(RenormSpec::pair(hi, lo, level).with_period(period).with_conj(hi_conj, lo_conj), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_packed_conj(aesfhe_ctx* ctx, aesfhe_handle c, aesfhe_handle c_conj, int period, int level, aesfhe_handle* out) {
-    API_BEGIN if (period < 16 || (period & (period - 1))) throw std::runtime_error("renorm_packed: period must be a power of two >= 16");
-    ctx->eng->renorm_states(c, c, 1, out, nullptr, level, 0, 0, true, period, c_conj);
+    API_BEGIN packed_period(period);
+    ctx->eng->renorm(RenormSpec::single(c, level).with_period(period).with_conj(c_conj), out, nullptr);
     API_END
 }
 int aesfhe_renorm_unpack_conj(aesfhe_ctx* ctx, aesfhe_handle packed, aesfhe_handle packed_conj, int period, int level, aesfhe_handle* out_hi,
                               aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(packed, packed, 1, out_hi, out_lo, level, 0, period, false, 0, packed_conj);
+    API_BEGIN ctx->eng->renorm(RenormSpec::unpack(packed, period, level).with_conj(packed_conj), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_single(aesfhe_ctx* ctx, aesfhe_handle c, int level, aesfhe_handle* out) {
-    API_BEGIN ctx->eng->renorm_states(c, c, 1, out, nullptr, level, 0, 0, true);
+    API_BEGIN ctx->eng->renorm(RenormSpec::single(c, level), out, nullptr);
     API_END
 }
 int aesfhe_renorm_packed(aesfhe_ctx* ctx, aesfhe_handle c, int period, int level, aesfhe_handle* out) {
-    API_BEGIN
-    if (period < 16 || (period & (period - 1))) throw std::runtime_error("renorm_packed: period must be a power of two >= 16");
-    ctx->eng->renorm_states(c, c, 1, out, nullptr, level, 0, 0, true, period);
+    API_BEGIN packed_period(period);
+    ctx->eng->renorm(RenormSpec::single(c, level).with_period(period), out, nullptr);
     API_END
 }
 int aesfhe_renorm_states(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, int states, aesfhe_handle* out_hi,
                          aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(hi, lo, states, out_hi, out_lo);
+    API_BEGIN ctx->eng->renorm(RenormSpec::pair(hi, lo, -1).with_states(states), out_hi, out_lo);
     API_END
 }
 int aesfhe_renorm_at(aesfhe_ctx* ctx, aesfhe_handle hi, aesfhe_handle lo, int states, int level, aesfhe_handle* out_hi,
                      aesfhe_handle* out_lo) {
-    API_BEGIN ctx->eng->renorm_states(hi, lo, states, out_hi, out_lo, level);
+    API_BEGIN ctx->eng->renorm(RenormSpec::pair(hi, lo, level).with_states(states), out_hi, out_lo);
     API_END
 }
 int aesfhe_export(aesfhe_ctx* ctx, aesfhe_handle c, uint32_t* out, uint64_t words) {

@@ -1,5 +1,5 @@
 """The secret-key renorm of s1 + conj(s2) with the conjugation folded into its decryption
-(aesfhe_renorm_packed_conj / aesfhe_renorm_unpack_conj, engine.hip renorm_states' conjugate
+(aesfhe_renorm_packed_conj / aesfhe_renorm_unpack_conj, engine.hip RenormSpec::conj, the renorm's conjugate
 partner; utils.ConjSum): a conjugate-split LUT's output renormalised without its conjugation key
 switch.  Neither input alone decodes to the state (each carries a garbage half that cancels only in
 s1 + conj(s2)); the folded renorm must give the states of renorm(add(s1, conjugate(s2))), on the
