@@ -154,6 +154,13 @@ struct Lut {
     double pub_mag = 0.0;       // sum_t max_b |D[t][b]|
 };
 
+// the value decode's coefficient tables: [2][kValueRows][16] complex double on the device
+constexpr int kValueRows = 9;  // E_0..E_8 per nibble; row 0 (the constant) is Python's
+struct ValueTab {
+    std::pair<u32*, size_t> tab{nullptr, 0};
+    double mag_t = 0.0, mag_r = 0.0;  // sum over T's / R's channels of max_b |E_p[b]|
+};
+
 struct Pt {
     std::vector<double> re, im;
     bool constant = false;
@@ -313,6 +320,12 @@ public:
             for (auto& e : il->second.cst) give_back(e.second.first, e.second.second);
             if (il->second.pub.first) give_back(il->second.pub.first, il->second.pub.second);
             luts_.erase(il);
+            return;
+        }
+        auto iv = vtabs_.find(h);
+        if (iv != vtabs_.end()) {
+            give_back(iv->second.tab.first, iv->second.tab.second);
+            vtabs_.erase(iv);
             return;
         }
         auto ip = pts_.find(h);
@@ -1775,6 +1788,166 @@ public:
         const int nl = hp_.nl(level);
         const size_t rows = L.pub_rows.size() * (size_t)nl;
         u32* m = public_encode(L, nullptr, d_nib, hp_.ptscale[level], nl);
+        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
+        if (e == hipSuccess) e = hipStreamSynchronize(S());
+        untmp(m, rows);
+        HIP_OK(e);
+        *scale = hp_.ptscale[level];
+    }
+
+    // ------------------------------------------------------------------ public XOR fused with the value decode
+    // The two 9 x 16 tables E_p[b] of a byte's nibbles (hi pre-scaled by 16 gain, lo by gain; made by Python) as
+    // one device table [2][9][16] complex double: uploaded once, waiting for its copy once as lut_public_table does.
+    aesfhe_handle value_create(const double* re, const double* im) {
+        if (!re || !im) throw std::runtime_error("xor_value_create: missing table");
+        ValueTab V;
+        std::vector<double> h((size_t)2 * kValueRows * 16 * 2);
+        for (int half = 0; half < 2; ++half)
+            for (int p = 0; p < kValueRows; ++p) {
+                double top = 0.0;
+                for (int b = 0; b < 16; ++b) {
+                    const size_t c = ((size_t)half * kValueRows + p) * 16 + b;
+                    if (!std::isfinite(re[c]) || !std::isfinite(im[c])) throw std::runtime_error("xor_value_create: table entry not finite");
+                    h[2 * c] = re[c], h[2 * c + 1] = im[c];
+                    top = std::max(top, std::hypot(re[c], im[c]));
+                }
+                if (p >= 1 && p < kValueRows - 1) V.mag_t += top;
+                if (p == kValueRows - 1) V.mag_r += top;
+            }
+        ensure_slot_pos();
+        const size_t words = (2 * h.size() + (size_t)hp_.n - 1) / hp_.n * hp_.n;
+        u32* d = alloc_words(words);
+        HIP_OK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, S()));
+        HIP_OK(hipStreamSynchronize(S()));  // cached for every stream; host vector dies here
+        V.tab = {d, words};
+        const aesfhe_handle hd = next_++;
+        vtabs_.emplace(hd, V);
+        return hd;
+    }
+    const ValueTab& vtab(aesfhe_handle h) const {
+        auto it = vtabs_.find(h);
+        if (it == vtabs_.end()) throw std::runtime_error("invalid value table handle");
+        return it->second;
+    }
+    void free_value(aesfhe_handle h) {
+        if (!vtabs_.count(h)) throw std::runtime_error("aesfhe_xor_value_free: not a value table handle");
+        free_handle(h);
+    }
+    // both public nibble arrays checked and copied into this stream's staging buffers, hi then lo (stage_nibbles)
+    const uint8_t* stage_nibbles2(const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots) {
+        const int s = slot_count();
+        if (!nib_hi || !nib_lo || n_slots != s)
+            throw std::runtime_error("xor_value_public: one nibble per slot (n_slots must equal slot_count)");
+        std::vector<uint8_t>& h = h_val_nib_[t_sidx];
+        h.resize((size_t)2 * s);
+        for (int half = 0; half < 2; ++half) {
+            const uint8_t* nib = half ? nib_lo : nib_hi;
+            for (int j = 0; j < s; ++j) {
+                if (nib[j] >= 16) throw std::runtime_error("xor_value_public: nibble out of range (>= 16) at slot " + std::to_string(j));
+                h[(size_t)half * s + j] = nib[j];
+            }
+        }
+        if (!d_val_nib_[t_sidx]) d_val_nib_[t_sidx] = (uint8_t*)dev_alloc(((size_t)2 * s + 3) / 4);
+        HIP_OK(hipMemcpyAsync(d_val_nib_[t_sidx], h.data(), (size_t)2 * s, hipMemcpyHostToDevice, S()));
+        return d_val_nib_[t_sidx];
+    }
+    // the 16 per-slot coefficient plaintexts, channel t = half * 8 + (p - 1) holding E_p of nibble array `half`
+    // (p = 1..8), encoded at `scale` on nl limbs by the codec public_encode uses.  Returns 16 x nl rows (tmp)
+    u32* value_encode(const ValueTab& V, const uint8_t* d_nib, double scale, int nl) {
+        ValueSlotArgs ch;
+        for (int t = 0; t < kValueCh; ++t) ch.half[t] = t / 8, ch.row[t] = (t / 8) * kValueRows + (t % 8) + 1;
+        u32* wb = tmp((size_t)4 * kValueCh);  // [16][N] complex double: 4 rows per channel
+        u32* m = nullptr;
+        try {
+            m = tmp((size_t)kValueCh * nl);
+            launch_value_slots(S(), T_, (double*)wb, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, d_nib, d_slot_pos_);
+            launch_fft2(S(), T_, (double*)wb, -1, kValueCh);
+            launch_encode_untwist(S(), T_, m, (const double*)wb, scale, nl, kValueCh);
+            ntt(m, kValueCh * nl, nl, qmap());
+        } catch (...) {
+            untmp(wb, (size_t)4 * kValueCh);
+            if (m) untmp(m, (size_t)kValueCh * nl);
+            throw;
+        }
+        untmp(wb, (size_t)4 * kValueCh);
+        return m;
+    }
+    // T = sum_{p = 1..7} E_p[nib_hi] (.) hi^p + E_p[nib_lo] (.) lo^p and R = E_8[nib_hi] (.) hi^8 + E_8[nib_lo] (.) lo^8:
+    // A_hi / A_lo are indexed by the power p (entry 0 unused), the operands canonical and dropped exactly to their
+    // common lowest logical level l as lut_eval_public's, ONE k_value_public_mac launch for both sums; each output
+    // owes its rescale (applied here when the raw scale has no headroom)
+    void xor_value_public(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi,
+                          const uint8_t* nib_lo, int n_slots, Ct* oT, Ct* oR) {
+        const ValueTab& V = vtab(hv);
+        if (!A_hi || !A_lo) throw std::runtime_error("xor_value_public: missing element handles");
+        aesfhe_handle A[kValueCh];
+        int l = 1 << 30;
+        for (int t = 0; t < kValueCh; ++t) {
+            A[t] = (t / 8 ? A_lo : A_hi)[(t % 8) + 1];
+            if (!A[t]) throw std::runtime_error("xor_value_public: missing element handle of a used row");
+            const Ct& c = ct(A[t]);
+            if (c.nb != 1) throw std::runtime_error("xor_value_public: stacked operands are not supported (single ciphertexts only)");
+            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("xor_value_public: nonzero 2-polynomial ciphertexts");
+            l = std::min(l, c.level - c.pend);
+        }
+        if (l < 1) throw std::runtime_error("not enough level for the public value decode (level 0)");
+        const uint8_t* d_nib = stage_nibbles2(nib_hi, nib_lo, n_slots);
+        const int nl = hp_.nl(l);
+        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
+        u32* m = nullptr;
+        Ct out[2];
+        try {
+            ValueMacArgs a;
+            for (int t = 0; t < kValueCh; ++t) {
+                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
+                const Ct& c = ct(A[t]);
+                Ct x = c;
+                if (pm(c) != 2 || c.pend || !c.ntt) {
+                    x = normalize(c, true);
+                    if (x.data != c.data) own.push_back(x);
+                }
+                if (x.level != l) {
+                    const u32* before = x.data;
+                    x = level_down(x, l);
+                    if (x.data != before && x.data != c.data) own.push_back(x);
+                }
+                a.a[t] = x.data;
+                a.real[t] = (t % 8) == 7;  // the a^8 terms: R
+                cnt_[C_PTMUL]++;
+            }
+            m = value_encode(V, d_nib, hp_.ptscale[l], nl);
+            for (int k = 0; k < 2; ++k) res.push_back(out[k] = alloc_ct(l, 2));
+            launch_value_public_mac(S(), T_, out[0].data, out[1].data, a, kValueCh, m, nl, qmap());
+            untmp(m, (size_t)kValueCh * nl), m = nullptr;
+            for (int k = 0; k < 2; ++k) {
+                out[k].pend = 1;
+                out[k].lazy = true;
+                if (!headroom(l, 1, k ? V.mag_r : V.mag_t)) {
+                    Ct r = rescale(out[k]);
+                    own.push_back(out[k]);
+                    res[k] = out[k] = r;
+                }
+            }
+        } catch (...) {
+            if (m) untmp(m, (size_t)kValueCh * nl);
+            for (const Ct& x : own) release(x);
+            for (const Ct& x : res) release(x);
+            throw;
+        }
+        for (const Ct& x : own) release(x);
+        cnt_[C_LUT]++;
+        *oT = out[0];
+        *oR = out[1];
+    }
+    // tests: the 16 encoded channel rows (16 x nl(level) x N, NTT form, value_encode's order) and their scale
+    void debug_value_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level, u32* out, double* scale) {
+        const ValueTab& V = vtab(hv);
+        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_xor_value_pt: level out of range (1..max level)");
+        if (!out || !scale) throw std::runtime_error("debug_xor_value_pt: missing output buffers");
+        const uint8_t* d_nib = stage_nibbles2(nib_hi, nib_lo, n_slots);
+        const int nl = hp_.nl(level);
+        const size_t rows = (size_t)kValueCh * nl;
+        u32* m = value_encode(V, d_nib, hp_.ptscale[level], nl);
         hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
         if (e == hipSuccess) e = hipStreamSynchronize(S());
         untmp(m, rows);
@@ -5533,6 +5706,7 @@ private:
     }
     CrtConsts crt_[4] = {};
     std::unordered_map<aesfhe_handle, Lut> luts_;
+    std::unordered_map<aesfhe_handle, ValueTab> vtabs_;
     Slot16 slots_ = {};    // the reference layout's 16 state slots, 5^(i N/32)
     Slot32 slots32_ = {};  // the first 32 slots, 5^j (the packed period-32 form)
     // AESFHE_RENORM_DIRECT32=0: the packed renorms through the FFT codec (A/B runs)
@@ -5544,6 +5718,8 @@ private:
     int* d_nib_[kStreams] = {};
     uint8_t* d_pub_nib_[kStreams] = {};        // lut_eval_public: the public nibbles, one byte per slot
     std::vector<uint8_t> h_pub_nib_[kStreams];  // their host staging copy
+    uint8_t* d_val_nib_[kStreams] = {};        // xor_value_public: both public nibble arrays, hi then lo
+    std::vector<uint8_t> h_val_nib_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;
@@ -5749,6 +5925,31 @@ int aesfhe_debug_public_pt(aesfhe_ctx* ctx, aesfhe_handle lut, const uint8_t* ni
 }
 int aesfhe_lut_free(aesfhe_ctx* ctx, aesfhe_handle lut) {
     API_BEGIN ctx->eng->free_lut(lut);
+    API_END
+}
+int aesfhe_xor_value_create(aesfhe_ctx* ctx, const double* re, const double* im, aesfhe_handle* out) {
+    API_BEGIN
+    if (!out) throw std::runtime_error("xor_value_create: missing output handle");
+    *out = ctx->eng->value_create(re, im);
+    API_END
+}
+int aesfhe_xor_value_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo, const uint8_t* nib_hi,
+                            const uint8_t* nib_lo, int n_slots, aesfhe_handle* out_t, aesfhe_handle* out_r) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out_t || !out_r) throw std::runtime_error("xor_value_public: missing output handles");
+    Ct t, r;
+    e.xor_value_public(table, a_hi, a_lo, nib_hi, nib_lo, n_slots, &t, &r);
+    *out_t = e.put_ct(t);
+    *out_r = e.put_ct(r);
+    API_END
+}
+int aesfhe_debug_xor_value_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level,
+                              uint32_t* out, double* scale) {
+    API_BEGIN ctx->eng->debug_value_pt(table, nib_hi, nib_lo, n_slots, level, out, scale);
+    API_END
+}
+int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table) {
+    API_BEGIN ctx->eng->free_value(table);
     API_END
 }
 int aesfhe_set_enc_nonce(aesfhe_ctx* ctx, uint64_t nonce) {

@@ -609,3 +609,25 @@ struct PubMacArgs {
 };
 void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* out2, const PubMacArgs& a, int n, int nch, const u32* pt,
                            int nl, LimbMap map);
+
+// --- public XOR fused with the value decode ----------------------------
+// val(a ^ b) of a Zeta16 nibble a with b public is sum_p E_p[b] a^p: per-slot plaintext coefficients again, now
+// over the powers of BOTH nibbles of a byte and two public nibble arrays.  launch_value_slots is
+// launch_public_slots with a channel map: channel c takes row row[c] of one table (rows of 16 complex doubles)
+// at the nibble nib[half[c] * N/2 + j] of slot j, in the same output order.
+constexpr int kValueCh = 16;  // 2 x 8 powers: the FFT scratch's channel limit
+struct ValueSlotArgs {
+    int row[kValueCh] = {};
+    int half[kValueCh] = {};  // 0: the first nibble array (hi), 1: the second (lo)
+};
+void launch_value_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
+                        const uint8_t* nib, const u32* slot_pos);
+// outT = sum_{t: !real[t]} a[t] (.) pt[t], outR = sum_{t: real[t]} a[t] (.) pt[t] (2 polys of nl limbs each; pt:
+// channel t of nl limbs, NTT form) in ONE launch over n <= kValueCh ciphertexts, every word read once; neither
+// sum may take more than 15 terms (64-bit sums of 60-bit products)
+struct ValueMacArgs {
+    const u32* a[kValueCh] = {};
+    int real[kValueCh] = {};
+};
+void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32* outR, const ValueMacArgs& a, int n, const u32* pt, int nl,
+                             LimbMap map);

@@ -135,6 +135,23 @@ __global__ void k_lut_public_mac(u32* out1, u32* out2, PubMacArgs a, int n, cons
     out1[idx] = reduce64(acc1, P.q, P.mu, P.r32);
     if (out2) out2[idx] = reduce64(acc2, P.q, P.mu, P.r32);
 }
+// outT = sum_{t: !real_t} a_t (.) pt[t], outR = sum_{t: real_t} a_t (.) pt[t] over n <= kValueCh ciphertexts, channel t of
+// one encoded plaintext buffer per ciphertext (the value decode's T and R, launch_value_public_mac): every ciphertext
+// and plaintext word read once.  64-bit sums with one reduction each: the residues are below 2^30, so the 14 products
+// of T (15 at most, the launcher checks) stay below 15 x 2^60 < 2^64
+__global__ void k_value_public_mac(u32* outT, u32* outR, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc,
+                                   int logn) {
+    EW_PROLOGUE
+    const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
+    u64 accT = 0, accR = 0;
+    for (int t = 0; t < n; ++t) {
+        const u64 prod = (u64)a.a[t][idx] * pt[(size_t)t * chan + pidx];
+        if (a.real[t]) accR += prod;
+        else accT += prod;
+    }
+    outT[idx] = reduce64(accT, P.q, P.mu, P.r32);
+    outR[idx] = reduce64(accR, P.q, P.mu, P.r32);
+}
 __global__ void k_tensor(u32* out, const u32* a, const u32* b, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     // row = m * nl + limb: ciphertext m of a stacked batch ([m][2][nl] in, [m][3][nl] out)
     const int row = blockIdx.y;
@@ -1349,6 +1366,21 @@ __global__ void __launch_bounds__(kBlock) k_public_slots(double2* w, const doubl
     wc[t] = v;
     wc[n - 1 - t] = make_double2(v.x, -v.y);
 }
+// k_public_slots with a channel map (launch_value_slots): channel c takes row ch.row[c] of ONE table at the slot's
+// nibble in nibble array ch.half[c] (two arrays of N/2 bytes, back to back).  The map is a kernel argument: uniform
+// per block, read by the scalar unit
+__global__ void __launch_bounds__(kBlock) k_value_slots(double2* w, const double2* tab, ValueSlotArgs ch, const uint8_t* nib,
+                                                        const u32* slot_pos, int logn) {
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
+    const int n = 1 << logn;
+    if (j >= n / 2) return;
+    const double2 v = tab[16 * ch.row[c] + (nib[(size_t)ch.half[c] * (n / 2) + j] & 15)];
+    const u32 t = slot_pos[j];
+    double2* wc = w + ((size_t)c << logn);
+    wc[t] = v;
+    wc[n - 1 - t] = make_double2(v.x, -v.y);
+}
 
 // ------------------------------------------------------------------------------------
 // fused LUT evaluation: one launch per LUT instead of a tensor + constant + add per term
@@ -2245,4 +2277,28 @@ void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* o
         if (!a.a[t] || a.c1[t] >= nch || a.c2[t] >= nch) throw std::runtime_error("launch_lut_public_mac: bad operand");
     prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + (out2 ? 2 : 1)) + (double)nch * nl), k_lut_public_mac, ew_grid(T.logn, 2 * nl),
                 dim3(kBlock), 0, st, out1, out2, a, n, pt, nl, map, T.pc, T.logn);
+}
+void launch_value_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
+                        const uint8_t* nib, const u32* slot_pos) {
+    if (nch < 1 || nch > kValueCh || !tab || !nib) throw std::runtime_error("launch_value_slots: 1..16 channels");
+    for (int c = 0; c < nch; ++c)
+        if (ch.row[c] < 0 || ch.row[c] >= tab_rows || (ch.half[c] != 0 && ch.half[c] != 1))
+            throw std::runtime_error("launch_value_slots: bad channel map");
+    const double s = (double)(1u << (T.logn - 1));
+    const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
+    prof_launch(KID_ELEMENTWISE, nch * (1.0 * s + 4.0 * s + 32.0 * s), k_value_slots, dim3(gx, nch), dim3(kBlock), 0, st, (double2*)w,
+                (const double2*)tab, ch, nib, slot_pos, T.logn);
+}
+void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32* outR, const ValueMacArgs& a, int n, const u32* pt, int nl,
+                             LimbMap map) {
+    if (n < 1 || n > kValueCh || !outT || !outR || !pt) throw std::runtime_error("launch_value_public_mac: 1..16 ciphertexts");
+    int nr = 0;
+    for (int t = 0; t < n; ++t) {
+        if (!a.a[t]) throw std::runtime_error("launch_value_public_mac: bad operand");
+        nr += a.real[t] != 0;
+    }
+    if (nr > 15 || n - nr > 15) throw std::runtime_error("launch_value_public_mac: at most 15 terms per sum");
+    // reads: n ciphertexts and n plaintext channels; writes: two ciphertexts
+    prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + 2) + (double)n * nl), k_value_public_mac, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st,
+                outT, outR, a, n, pt, nl, map, T.pc, T.logn);
 }

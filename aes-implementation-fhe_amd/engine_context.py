@@ -426,3 +426,10 @@ class EngineContext:
         plaintexts encoded on the device (Engine.lut_eval_public).  Modules test for it
         with getattr(ctx, "lut_eval_public", None)."""
         return self.engine.lut_eval_public(lut1, lut2, a, nibbles)
+
+    def xor_value_public(self, a_hi, a_lo, nib_hi, nib_lo, tab_hi, tab_lo):
+        """(T, R): the public XOR of a byte's two nibbles fused with the decode to its real VALUE, from the powers
+        x^1..x^8 of hi and lo, the two public nibble arrays and the two (9, 16) coefficient tables -- one engine
+        call (Engine.xor_value_public); R + T + conj(T) + constant is the value.  Modules test
+        for it with getattr(ctx, "xor_value_public", None)."""
+        return self.engine.xor_value_public(a_hi, a_lo, nib_hi, nib_lo, tab_hi, tab_lo)

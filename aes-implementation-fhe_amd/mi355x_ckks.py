@@ -50,6 +50,7 @@ EXPORTED = [
     "aesfhe_renorm_packed", "aesfhe_renorm_packed_conj", "aesfhe_renorm_unpack_conj", "aesfhe_renorm_periodic_conj", "aesfhe_renorm_pack", "aesfhe_renorm_periodic_perm", "aesfhe_renorm_unpack_perm",
     "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
     "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine", "aesfhe_export_ksk_at",
+    "aesfhe_xor_value_create", "aesfhe_xor_value_public", "aesfhe_debug_xor_value_pt", "aesfhe_xor_value_free",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -146,6 +147,10 @@ def load_library(path: Optional[Path] = None):
     _bp = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
     sig["aesfhe_lut_eval_public"] = [vp, _H, _H, _Hp, _bp, c_int, _Hp, _Hp]
     sig["aesfhe_debug_public_pt"] = [vp, _H, _bp, c_int, c_int, _up, ctypes.POINTER(c_dbl)]
+    sig["aesfhe_xor_value_create"] = [vp, _dp, _dp, _Hp]
+    sig["aesfhe_xor_value_public"] = [vp, _H, _Hp, _Hp, _bp, _bp, c_int, _Hp, _Hp]
+    sig["aesfhe_debug_xor_value_pt"] = [vp, _H, _bp, _bp, c_int, c_int, _up, ctypes.POINTER(c_dbl)]
+    sig["aesfhe_xor_value_free"] = [vp, _H]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -259,6 +264,12 @@ class LookupTable(_Handle):
     """Coefficient set of a fused LUT evaluation (aesfhe_lut_create)."""
 
     __slots__ = ("n_a", "n_b", "used_rows")
+
+
+class ValueTable(_Handle):
+    """The two 9 x 16 coefficient tables of the public value decode on the device (aesfhe_xor_value_create)."""
+
+    __slots__ = ()
 
 
 class _Key:
@@ -381,6 +392,7 @@ class Engine:
             defer_calls = env.get("AESFHE_DEFER_CALLS", "1") != "0"
         self.defer = bool(defer_calls)
         self._defer_luts = {}
+        self._value_tables = {}  # xor_value_public: table bytes -> ValueTable (uploaded once)
 
     # ------------------------------------------------------------------ concurrency
     def _executor(self):
@@ -1086,6 +1098,61 @@ class Engine:
         h, lut.handle = lut.handle, 0
         if h:
             self._ctx.check(self._lib.aesfhe_lut_free(self._ctx.ptr, h))
+
+    # ------------------------------------------------------------------ public XOR fused with the value decode
+    def _value_table(self, tab_hi, tab_lo) -> ValueTable:
+        """the device copy of a (hi, lo) table pair, uploaded once per pair of table values"""
+        t = np.ascontiguousarray(np.stack([np.asarray(tab_hi, np.complex128), np.asarray(tab_lo, np.complex128)]))
+        if t.shape != (2, 9, 16):
+            raise ValueError(f"xor_value_public: two (9, 16) complex tables, got {t.shape[1:]}")
+        cache, key = self._value_tables, t.tobytes()
+        if key not in cache:
+            h = ctypes.c_uint64()
+            self._ctx.check(self._lib.aesfhe_xor_value_create(self._ctx.ptr, np.ascontiguousarray(t.real), np.ascontiguousarray(t.imag),
+                                                              ctypes.byref(h)))
+            cache[key] = ValueTable(self._ctx, h.value)
+        return cache[key]
+
+    @staticmethod
+    def _power_handles(a):
+        arr = (ctypes.c_uint64 * 9)()
+        for k, ct in (a.items() if isinstance(a, dict) else enumerate(a)):
+            if ct is not None and 1 <= k <= 8:
+                arr[k] = ct.handle
+        return arr
+
+    def xor_value_public(self, a_hi, a_lo, nib_hi, nib_lo, tab_hi, tab_lo):
+        """(T, R) of the public XOR fused with the value decode (aesfhe_xor_value_public):
+        T = sum_{p = 1..7} tab_hi[p, nib_hi] hi^p + tab_lo[p, nib_lo] lo^p,  R = tab_hi[8, nib_hi] hi^8 + tab_lo[8, nib_lo] lo^8
+        per slot, so that R + T + conj(T) + (tab_hi[0] + tab_lo[0]) is the value.  a_hi / a_lo: the powers {p: x^p}
+        for p = 1..8 (dicts or sequences indexed by p); nib_*: contiguous uint8 arrays of slot_count entries < 16;
+        tab_*: (9, 16) complex tables, xor_value_table()[:9] scaled by 16 gain / gain (uploaded once per table pair).
+        Raises RuntimeError with "level" in the message when the powers sit at level 0, with "nibble" for an
+        entry >= 16."""
+        nh, nl_ = self._nibble_array(nib_hi), self._nibble_array(nib_lo)
+        if nh.size != nl_.size:
+            raise ValueError("xor_value_public: the two nibble arrays differ in length")
+        self._ensure_keys()
+        tab = self._value_table(tab_hi, tab_lo)
+        t, r = ctypes.c_uint64(), ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_xor_value_public(self._ctx.ptr, tab.handle, self._power_handles(a_hi), self._power_handles(a_lo),
+                                                          nh, nl_, int(nh.size), ctypes.byref(t), ctypes.byref(r)))
+        return Ciphertext(self._ctx, t.value), Ciphertext(self._ctx, r.value)
+
+    def debug_xor_value_pt(self, nib_hi, nib_lo, tab_hi, tab_lo, level: int):
+        """tests: (rows, scale) -- the 16 coefficient plaintexts xor_value_public multiplies by at `level` as
+        (16, nl(level), N) uint32 in NTT form, channel 8 half + (p - 1) holding row p of the hi (half 0) / lo
+        (half 1) table at that half's nibbles, and their scale"""
+        nh, nl_ = self._nibble_array(nib_hi), self._nibble_array(nib_lo)
+        if nh.size != nl_.size:
+            raise ValueError("debug_xor_value_pt: the two nibble arrays differ in length")
+        self._ensure_keys()
+        tab = self._value_table(tab_hi, tab_lo)
+        out = np.zeros((16, self.nl(level), self.n), np.uint32)
+        scale = ctypes.c_double(0.0)
+        self._ctx.check(self._lib.aesfhe_debug_xor_value_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), int(level), out,
+                                                            ctypes.byref(scale)))
+        return out, scale.value
 
     # ------------------------------------------------------------------ raw access (tests)
     def moduli(self) -> np.ndarray:

@@ -45,6 +45,10 @@ byte_order="transposed": states, round keys, counter blocks, public AES cipherte
 snapshots).  Its pairs are tagged transposed and refused by a plain pipeline (check_layout).  ``fuse_sub_ark``,
 ``fuse_sr_mc`` and ``pairs`` > 1 are not available with it (ValueError).
 
+Real-valued slots (xor_value_lut.py): ``transcipher_values`` / ``to_values`` return ONE ciphertext whose
+state slots hold gain * byte as real numbers (read back by ``encoder.decode_values``) instead of the Zeta16 pair -- the
+last public XOR of counter mode fused with the value decode, no renorm after the keystream.
+
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
 11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
 pairs the server never saw in clear: ``expand_key(*encrypt_key(master))`` derives them homomorphically from ONE
@@ -573,6 +577,39 @@ class AESPipeline:
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
         ct = self.ark.public(*ks, *nib, out_level=self._floor())
         return tag_layout(self.layout, *self._renorm_pair(*ct))
+
+    # ---------------------------------------------------------------- real-valued slots
+    def _value_lut(self, gain: float):
+        from xor_value_lut import XorValueLUT
+        if getattr(self, "_value_luts", None) is None:
+            self._value_luts = {}
+        g = float(gain)
+        if g not in self._value_luts:
+            self._value_luts[g] = XorValueLUT(self.ctx, g)
+        return self._value_luts[g]
+
+    def transcipher_values(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys,
+                           gain: float = 1.0 / 256.0):
+        """AES-CTR transciphering to REAL-VALUED slots: transcipher's inputs, but the result is ONE layout-tagged
+        ciphertext whose state slots hold gain * m as real numbers (in [0, 1) at the default gain; slots that hold
+        no state hold 0) -- what a CKKS program can add, multiply or average, read back by encoder.decode_values.
+        The keystream's last XOR (public AES ciphertext bytes) is fused with the value decode
+        (xor_value_lut.XorValueLUT.apply_public): no XOR4, no renorm and no bootstrap come after the keystream, whose
+        own last renorm (secret-key, or bootstrap + snap with true_fhe) is the last one.  The keystream is NOT
+        dropped first: the output sits utils.XOR_VALUE_DEPTH = 4 levels below the keystream's fresh level (3 on the
+        fresh-level-7 set, 13 on the default 17 / 5 set), and those levels are the caller's to compute with."""
+        self._no_pairs("transcipher_values")
+        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
+        lut = self._value_lut(gain)
+        ks = self.ctr_keystream(nonce12, counter0, round_keys)
+        return tag_layout(self.layout, lut.apply_public(*ks, *nib))[0]
+
+    def to_values(self, ct_hi, ct_lo, gain: float = 1.0 / 256.0):
+        """a clean layout-tagged (hi, lo) pair -- the output of encrypt, decrypt or transcipher -- as ONE ciphertext of
+        gain * byte per state slot (XorValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair)"""
+        self._no_pairs("to_values")
+        check_layout(self.layout, ct_hi, ct_lo)
+        return tag_layout(self.layout, self._value_lut(gain).apply(ct_hi, ct_lo))[0]
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):

@@ -222,6 +222,26 @@ class StateEncoder:
         out = self._order(((hi << 4) | lo).astype(np.uint8))
         return out[0] if self.states == 1 else out
 
+    def values_from_slots(self, slots: np.ndarray) -> np.ndarray:
+        """the pure unpacking of decode_values: a slot vector whose state slots hold one real number per byte
+        (xor_value_lut.XorValueLUT's output) -> the (states, 16) float array in the caller's byte order, (16,) for one
+        state -- _pack's slot order and the encoder's byte order undone, imaginary parts dropped"""
+        slots = np.asarray(slots)
+        if slots.shape != (self.sc,):
+            raise ValueError(f"expected a slot vector of {self.sc} entries, got shape {slots.shape}")
+        v = np.ascontiguousarray(self._take(slots.real.astype(np.float64)))
+        if self.byte_order == "transposed":  # shift_columns.transpose_bytes' map, on floats
+            v = np.ascontiguousarray(np.swapaxes(v.reshape(-1, 4, 4), -1, -2)).reshape(v.shape)
+        return v[0] if self.states == 1 else v
+
+    def decode_values(self, ct) -> np.ndarray:
+        """client side: decrypt a value ciphertext (AESPipeline.transcipher_values / to_values) into the
+        (states, 16) float array of gain * byte, (16,) for one state"""
+        if self.pairs > 1:
+            raise ValueError("decode_values: multi-pair batches (pairs > 1) are not supported")
+        check_layout(self.layout, ct)
+        return self.values_from_slots(self.ctx.decrypt(ct))
+
     # ---------------------------------------------------------------- packed form (DESIGN.md §4c)
     PACK_DEPTH = 1  # pack(): one plaintext product
 

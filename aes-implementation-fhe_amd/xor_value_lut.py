@@ -1,0 +1,106 @@
+"""XorValueLUT: a Zeta16 byte XOR a PUBLIC byte, decoded to its real VALUE.
+
+The pipeline's states are nibble codes: a byte is two 16th roots of unity (hi, lo), which only a decryption can
+read.  A CKKS program that wants to add, multiply or average the bytes needs them as NUMBERS.  With
+zeta = e^(-2 pi i / 16) (utils.ZetaEncoder), a = zeta^k and a public nibble b,
+
+    val(a ^ b) = sum_{p < 16} E_p[b] a^p,       E_p[b] = (1/16) sum_k (k ^ b) zeta^(-p k)      (coeffgen.xor_value_table)
+
+and since E_0 = 7.5, E_8 is real, E_(16-p) = conj(E_p) and a^(16-p) = conj(a^p) on codewords,
+
+    val(a ^ b) = 7.5 + E_8[b] a^8 + T + conj(T),      T = sum_{p = 1..7} E_p[b] a^p.
+
+For a byte the output is gain * (16 val(hi ^ b_hi) + val(lo ^ b_lo)): T summed over both nibbles (14 ciphertext x
+plaintext products), R = the two E_8 terms, the constant gain * 7.5 * 17 and ONE conjugation.  The powers a^1..a^8 of
+hi and lo take depth 3 (7 products each, batched by xor4_lut.joint_bases), the plaintext product one more:
+utils.XOR_VALUE_DEPTH = 4 levels.  With b = 0 everywhere this is the plain decode val(a); slots that hold no state
+(value 1 = zeta^0, nibble 0) come out as 0.
+
+The last XOR of counter mode has a public operand (the AES ciphertext byte), so transciphering ends here instead of
+in an XOR4, a renorm and a separate decode: AESPipeline.transcipher_values.
+"""
+from typing import Any, Dict
+
+import numpy as np
+
+from coeffgen import xor_value_table
+from utils import XOR_VALUE_DEPTH
+from xor4_lut import batched, joint_bases, powers
+
+POWERS = frozenset(range(1, 9))
+
+
+class XorValueLUT:
+    """gain: the real number a byte value v comes out as is gain * v (default 1/256: slots in [0, 1))"""
+
+    DEPTH = XOR_VALUE_DEPTH
+
+    def __init__(self, ctx, gain: float = 1.0 / 256.0):
+        self.ctx = ctx
+        self.sc = ctx.engine.slot_count
+        self.gain = float(gain)
+        E = xor_value_table()[:9]
+        self.tab_hi = np.ascontiguousarray(16.0 * self.gain * E)  # rows E_0..E_8 of the hi nibble, scaled by its weight
+        self.tab_lo = np.ascontiguousarray(self.gain * E)
+        self.const = self.gain * 7.5 * 17.0                      # E_0 of both nibbles
+
+    def _nibbles(self, nibbles) -> np.ndarray:
+        nib = np.ascontiguousarray(nibbles, dtype=np.uint8)
+        if nib.shape != (self.sc,):
+            raise ValueError(f"public nibbles: one uint8 per slot ({self.sc}), got shape {nib.shape}")
+        if nib.size and int(nib.max()) >= 16:
+            raise ValueError("public nibbles must be < 16")
+        return nib
+
+    def _bases(self, hi, lo):
+        """({p: hi^p}, {p: lo^p}) for p = 1..8: the two chains' products of one depth in one multiply_many batch"""
+        ctx = self.ctx
+        if batched(ctx):
+            return joint_bases(ctx, [(hi, POWERS, "pow"), (lo, POWERS, "pow")])
+        return powers(ctx, hi, POWERS), powers(ctx, lo, POWERS)
+
+    def _engine(self, A_hi: Dict[int, Any], A_lo: Dict[int, Any], nib_hi, nib_lo):
+        """(T, R) from ONE engine call (Engine.xor_value_public); None: the context has no such op, or the powers
+        sit too low for it (level)"""
+        ctx = self.ctx
+        ev = getattr(ctx, "xor_value_public", None)
+        if ev is None or not getattr(ctx, "fused_luts", False):
+            return None
+        try:
+            return ev(A_hi, A_lo, nib_hi, nib_lo, self.tab_hi, self.tab_lo)
+        except RuntimeError as e:
+            if "level" in str(e):
+                return None
+            raise
+
+    def _loop(self, A_hi, A_lo, nib_hi, nib_lo):
+        """(T, R) as the product loop over encoded per-slot coefficient vectors (XOR4LUT._public_loop's form):
+        existing calls only, so it runs on any context"""
+        ctx = self.ctx
+        T = R = None
+        for A, tab, nib in ((A_hi, self.tab_hi, nib_hi), (A_lo, self.tab_lo, nib_lo)):
+            for p in range(1, 8):
+                t = ctx.multiply(A[p], ctx.encode(tab[p, nib]))
+                T = t if T is None else ctx.add(T, t)
+            r = ctx.multiply(A[8], ctx.encode(tab[8, nib]))
+            R = r if R is None else ctx.add(R, r)
+        return T, R
+
+    def apply_public(self, hi, lo, nib_hi, nib_lo):
+        """ONE ciphertext whose slots hold gain * (16 (hi ^ nib_hi) + (lo ^ nib_lo)) as real numbers, XOR_VALUE_DEPTH
+        levels below the inputs.  hi / lo: clean Zeta16 ciphertexts (unit magnitude, as a renorm or a fresh
+        encryption leaves them); nib_*: the public nibble of every slot (uint8, slot_count entries;
+        StateEncoder.nibble_slots)."""
+        ctx = self.ctx
+        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
+        A_hi, A_lo = self._bases(hi, lo)
+        out = self._engine(A_hi, A_lo, nib_hi, nib_lo)
+        T, R = out if out is not None else self._loop(A_hi, A_lo, nib_hi, nib_lo)
+        return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)
+
+    def apply(self, hi, lo):
+        """the plain decode gain * (16 hi + lo): apply_public with zero nibbles"""
+        zero = np.zeros(self.sc, np.uint8)
+        return self.apply_public(hi, lo, zero, zero)
+
+    __call__ = apply

@@ -160,6 +160,39 @@ int aesfhe_debug_public_pt(aesfhe_ctx* ctx, aesfhe_handle lut, const uint8_t* ni
  * evaluator's plaintext caches, REF/lut.py:71-94 keeps them per object); fails if `lut` is not
  * a LUT handle.  aesfhe_free also accepts LUT handles; this entry states the intent. */
 int aesfhe_lut_free(aesfhe_ctx* ctx, aesfhe_handle lut);
+/* Public XOR fused with the value decode: from the Zeta16 nibbles hi, lo of an encrypted byte
+ * and PUBLIC nibbles b_hi, b_lo per slot, the real number gain * (16 (hi ^ b_hi) + (lo ^ b_lo)) -- the last XOR
+ * of a counter mode (keystream with the public AES ciphertext) and the step from the nibble code to a CKKS
+ * number in one plaintext-coefficient sum; no reference counterpart (REF decodes by decrypting).  With
+ * zeta = e^(-2 pi i / 16) and a = zeta^k:  val(a ^ b) = sum_{p < 16} E_p[b] a^p,
+ * E_p[b] = (1/16) sum_{k < 16} (k ^ b) zeta^(-p k);  E_0 = 7.5, E_8 real, E_(16-p) = conj(E_p), so on codewords
+ *     val(a ^ b) = 7.5 + E_8[b] a^8 + T + conj(T),   T = sum_{p = 1..7} E_p[b] a^p.
+ * xor_value_create uploads the two 9 x 16 tables (rows E_0..E_8, columns b), hi then lo, row-major re / im
+ * ([2][9][16] each), the hi table pre-scaled by 16 gain and the lo table by gain; row 0 is not read (the caller
+ * adds the constant gain 7.5 17).  The upload waits for its copy once; xor_value_free (or aesfhe_free) releases it.
+ * xor_value_public takes the powers a_hi[p], a_lo[p] = hi^p, lo^p for p = 1..8 (arrays of 9, entry 0 ignored;
+ * single 2-polynomial ciphertexts, stacks are refused, a missing one is an error) and the two nibble arrays
+ * (n_slots = slot_count bytes each, every byte < 16, else an error containing "nibble"; copied before the call
+ * returns), and returns
+ *     out_t = sum_{p = 1..7} E_p[b_hi] hi^p + E_p[b_lo] lo^p     (14 ciphertext x plaintext products)
+ *     out_r = E_8[b_hi] hi^8 + E_8[b_lo] lo^8                     (2 products, real coefficients)
+ * so that out_r + out_t + conj(out_t) + gain 7.5 17 is the value.  The operands are brought to canonical form
+ * and dropped exactly to their common lowest logical level l (l < 1: an error containing "level"); the 16
+ * per-slot coefficient plaintexts are encoded on the device at the level's plaintext scale (the codec of
+ * aesfhe_lut_eval_public, 16 channels at once) and one kernel forms both sums; each output is at level l - 1,
+ * owing its rescale as aesfhe_lut_eval_public's outputs do.  A refused call leaves every handle intact; the
+ * evaluations never synchronise the stream. */
+int aesfhe_xor_value_create(aesfhe_ctx* ctx, const double* re, const double* im, aesfhe_handle* out);
+int aesfhe_xor_value_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo,
+                            const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                            aesfhe_handle* out_t, aesfhe_handle* out_r);
+/* tests only: the 16 coefficient plaintexts aesfhe_xor_value_public multiplies by at `level` (>= 1) -- channel
+ * 8 half + (p - 1) holding E_p (p = 1..8) of the hi (half 0) or lo (half 1) table at that half's nibbles,
+ * nl(level) limbs of N words each, NTT form -- and the scale they were encoded at */
+int aesfhe_debug_xor_value_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level,
+                              uint32_t* out, double* scale);
+/* Releases a value table; fails if `table` is not one.  aesfhe_free also accepts value tables. */
+int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table);
 /* Deferred evaluation switch, default on: API-level ct x ct products
  * leave relinearisation and their rescale to the first consumer that needs a
  * 2-polynomial canonical ciphertext (rotate, conjugate, ct x ct, power basis, bootstrap,
