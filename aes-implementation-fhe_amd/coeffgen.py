@@ -65,20 +65,26 @@ def lut_bivariate(f, scale: float = 1.0) -> np.ndarray:
     return np.fft.ifft2(F) * scale
 
 
-def xor_value_table() -> np.ndarray:
+def xor_value_table(signed: bool = False) -> np.ndarray:
     """E[p, b] = (1/16) Σ_k (k ⊕ b) ζ16^{-pk}: the INTEGER value of a ⊕ b for a Zeta16 nibble a = ζ16^k and a
     public nibble b is Σ_p E[p, b] a^p (xor_value_lut.py).  Closed form, with w = ζ16^{-p}:
     k ⊕ b = k + b - 2 Σ_j 2^j b_j k_j over the bits j; Σ_k k w^k is 120 at p = 0 and 16 / (w - 1) elsewhere;
     Σ_{k: k_j = 1} w^k is 8 at p = 0, 2^(4-j) / (w - 1) where p is an odd multiple of 2^(3-j), and 0 elsewhere.
     Every p > 0 is an odd multiple of exactly one 2^(3-j), j(p) = 3 - v2(p), so
         E[0, b] = 7.5,        E[p, b] = (-1)^(bit j(p) of b) / (ζ16^{-p} - 1)   (p > 0):
-    E[8] = -+1/2 is real, E[16 - p] = conj(E[p]), no entry is zero, max |E[p]| = 1 / (2 sin(π/16)) = 2.563 at p = 1."""
+    E[8] = -+1/2 is real, E[16 - p] = conj(E[p]), no entry is zero, max |E[p]| = 1 / (2 sin(π/16)) = 2.563 at p = 1.
+    signed=True: the table Es of the SIGNED value sval(x) = x - 16 [x >= 8] of a ⊕ b (a two's-complement top nibble,
+    DESIGN.md §3.21).  Only bit 3 changes weight (8 -> -8) and j(p) = 3 exactly for the odd p, so Es is E with the odd
+    rows negated and Es[0] = 7.5 - 8 = -0.5; Es[8] stays real and Es[16 - p] = conj(Es[p])."""
     E = np.full((16, 16), 7.5, np.complex128)
     b = np.arange(16)
     for p in range(1, 16):
         j = 3 - ((p & -p).bit_length() - 1)
         E[p] = (1.0 - 2.0 * ((b >> j) & 1)) / (_zeta(16) ** -p - 1.0)
     E[8] = E[8].real  # ζ16^{-8} = -1 up to an ulp of imaginary part
+    if signed:
+        E[1::2] *= -1.0
+        E[0] -= 8.0
     return E
 
 

@@ -1955,6 +1955,172 @@ public:
         *scale = hp_.ptscale[level];
     }
 
+    // ------------------------------------------------------------------ typed value decode
+    // The value decode is linear in its table, so a real weight per slot scales the decoded value per slot, and a
+    // signed hi nibble (sval(x) = x - 16 [x >= 8]) only negates the hi table's odd rows: both fold into the per-slot
+    // coefficients k_value_slots_typed writes.  G = 1 or 2 weight groups share the ciphertext operands; group g's
+    // weights select byte g of a 16-bit word, and the caller adds group 1 rotated onto group 0.
+    struct TypedStage {
+        const uint8_t* nib = nullptr;    // both nibble arrays, hi then lo
+        const double* wt = nullptr;      // [G][slots]
+        const uint8_t* flags = nullptr;  // [G][slots], null: no slot signed
+        double top[kValueGroups] = {};   // max |w| per group
+    };
+    // nibbles, weights and flags checked and copied into this stream's staging buffer in ONE copy:
+    // [G][s] doubles, then 2 s nibble bytes, then (flags given) G s flag bytes
+    TypedStage stage_typed(const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights, const uint8_t* flags) {
+        const int s = slot_count();
+        if (!nib_hi || !nib_lo || n_slots != s)
+            throw std::runtime_error("xor_value_typed: one nibble per slot (n_slots must equal slot_count)");
+        const size_t nw = (size_t)G * s, o_nib = nw * sizeof(double), o_flag = o_nib + (size_t)2 * s;
+        const size_t bytes = o_flag + (flags ? nw : 0);
+        std::vector<uint8_t>& h = h_val_typed_[t_sidx];
+        h.resize(bytes);
+        TypedStage st;
+        for (int g = 0; g < G; ++g)
+            for (int j = 0; j < s; ++j) {
+                const double w = weights[(size_t)g * s + j];
+                if (!std::isfinite(w))
+                    throw std::runtime_error("xor_value_typed: weight not finite at group " + std::to_string(g) + ", slot " + std::to_string(j));
+                st.top[g] = std::max(st.top[g], std::fabs(w));
+            }
+        std::memcpy(h.data(), weights, o_nib);
+        for (int half = 0; half < 2; ++half) {
+            const uint8_t* nib = half ? nib_lo : nib_hi;
+            for (int j = 0; j < s; ++j) {
+                if (nib[j] >= 16) throw std::runtime_error("xor_value_typed: nibble out of range (>= 16) at slot " + std::to_string(j));
+                h[o_nib + (size_t)half * s + j] = nib[j];
+            }
+        }
+        if (flags) std::memcpy(h.data() + o_flag, flags, nw);
+        // sized for kValueGroups groups with flags: 8 G s + 2 s + G s bytes
+        if (!d_val_typed_[t_sidx]) d_val_typed_[t_sidx] = (uint8_t*)dev_alloc(((size_t)(9 * kValueGroups + 2) * s + 3) / 4);
+        uint8_t* d = d_val_typed_[t_sidx];
+        HIP_OK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, S()));
+        st.wt = (const double*)d;
+        st.nib = d + o_nib;
+        st.flags = flags ? d + o_flag : nullptr;
+        return st;
+    }
+    // value_encode per weight group: G x 16 channels (group g's 16 follow group g - 1's), one codec pass per group
+    // through the same 16-channel FFT scratch.  Returns G x 16 x nl rows (tmp)
+    u32* value_encode_typed(const ValueTab& V, const TypedStage& st, int G, double scale, int nl) {
+        ValueTypedSlotArgs ch;
+        for (int t = 0; t < kValueCh; ++t) {
+            const int half = t / 8, p = (t % 8) + 1;
+            ch.ch.half[t] = half, ch.ch.row[t] = half * kValueRows + p;
+            ch.flip[t] = half == 0 && (p & 1);  // the signed nibble negates the hi table's odd rows
+        }
+        const int s = slot_count();
+        const size_t grp = (size_t)kValueCh * nl;
+        u32* wb = tmp((size_t)4 * kValueCh);  // [16][N] complex double: 4 rows per channel
+        u32* m = nullptr;
+        try {
+            m = tmp((size_t)G * grp);
+            for (int g = 0; g < G; ++g) {
+                u32* mg = m + (size_t)g * grp * hp_.n;
+                launch_value_slots_typed(S(), T_, (double*)wb, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, st.nib,
+                                         st.wt + (size_t)g * s, st.flags ? st.flags + (size_t)g * s : nullptr, d_slot_pos_);
+                launch_fft2(S(), T_, (double*)wb, -1, kValueCh);
+                launch_encode_untwist(S(), T_, mg, (const double*)wb, scale, nl, kValueCh);
+                ntt(mg, kValueCh * nl, nl, qmap());
+            }
+        } catch (...) {
+            untmp(wb, (size_t)4 * kValueCh);
+            if (m) untmp(m, (size_t)G * grp);
+            throw;
+        }
+        untmp(wb, (size_t)4 * kValueCh);
+        return m;
+    }
+    // xor_value_public with per-slot weights and flags for G groups: oT[g], oR[g] are group g's T and R (the same
+    // operands, normalisation, level drop and owed rescale), all formed by ONE k_value_typed_mac launch
+    void xor_value_typed(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                         int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT, Ct* oR) {
+        const ValueTab& V = vtab(hv);
+        if (G < 1 || G > kValueGroups) throw std::runtime_error("xor_value_typed: n_groups must be 1 or 2");
+        if (!weights) throw std::runtime_error("xor_value_typed: missing weights");
+        if (!A_hi || !A_lo) throw std::runtime_error("xor_value_typed: missing element handles");
+        aesfhe_handle A[kValueCh];
+        int l = 1 << 30;
+        for (int t = 0; t < kValueCh; ++t) {
+            A[t] = (t / 8 ? A_lo : A_hi)[(t % 8) + 1];
+            if (!A[t]) throw std::runtime_error("xor_value_typed: missing element handle of a used row");
+            const Ct& c = ct(A[t]);
+            if (c.nb != 1) throw std::runtime_error("xor_value_typed: stacked operands are not supported (single ciphertexts only)");
+            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("xor_value_typed: nonzero 2-polynomial ciphertexts");
+            l = std::min(l, c.level - c.pend);
+        }
+        if (l < 1) throw std::runtime_error("not enough level for the typed value decode (level 0)");
+        const TypedStage st = stage_typed(nib_hi, nib_lo, n_slots, G, weights, flags);
+        const int nl = hp_.nl(l);
+        const size_t mrows = (size_t)G * kValueCh * nl;
+        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
+        u32* m = nullptr;
+        Ct out[2 * kValueGroups];  // T_0, R_0, T_1, R_1
+        try {
+            ValueMacArgs a;
+            for (int t = 0; t < kValueCh; ++t) {
+                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
+                const Ct& c = ct(A[t]);
+                Ct x = c;
+                if (pm(c) != 2 || c.pend || !c.ntt) {
+                    x = normalize(c, true);
+                    if (x.data != c.data) own.push_back(x);
+                }
+                if (x.level != l) {
+                    const u32* before = x.data;
+                    x = level_down(x, l);
+                    if (x.data != before && x.data != c.data) own.push_back(x);
+                }
+                a.a[t] = x.data;
+                a.real[t] = (t % 8) == 7;  // the a^8 terms: R
+                cnt_[C_PTMUL] += G;
+            }
+            m = value_encode_typed(V, st, G, hp_.ptscale[l], nl);
+            ValueTypedOut o;
+            for (int k = 0; k < 2 * G; ++k) res.push_back(out[k] = alloc_ct(l, 2));
+            for (int g = 0; g < G; ++g) o.t[g] = out[2 * g].data, o.r[g] = out[2 * g + 1].data;
+            launch_value_typed_mac(S(), T_, o, G, a, kValueCh, m, nl, qmap());
+            untmp(m, mrows), m = nullptr;
+            for (int k = 0; k < 2 * G; ++k) {
+                out[k].pend = 1;
+                out[k].lazy = true;
+                if (!headroom(l, 1, (k & 1 ? V.mag_r : V.mag_t) * st.top[k / 2])) {
+                    Ct r = rescale(out[k]);
+                    own.push_back(out[k]);
+                    res[k] = out[k] = r;
+                }
+            }
+        } catch (...) {
+            if (m) untmp(m, mrows);
+            for (const Ct& x : own) release(x);
+            for (const Ct& x : res) release(x);
+            throw;
+        }
+        for (const Ct& x : own) release(x);
+        cnt_[C_LUT]++;
+        for (int g = 0; g < G; ++g) oT[g] = out[2 * g], oR[g] = out[2 * g + 1];
+    }
+    // tests: the G x 16 encoded channel rows (value_encode_typed's order) and their scale
+    void debug_value_typed_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights,
+                              const uint8_t* flags, int level, u32* out, double* scale) {
+        const ValueTab& V = vtab(hv);
+        if (G < 1 || G > kValueGroups) throw std::runtime_error("debug_xor_value_typed_pt: n_groups must be 1 or 2");
+        if (!weights) throw std::runtime_error("debug_xor_value_typed_pt: missing weights");
+        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_xor_value_typed_pt: level out of range (1..max level)");
+        if (!out || !scale) throw std::runtime_error("debug_xor_value_typed_pt: missing output buffers");
+        const TypedStage st = stage_typed(nib_hi, nib_lo, n_slots, G, weights, flags);
+        const int nl = hp_.nl(level);
+        const size_t rows = (size_t)G * kValueCh * nl;
+        u32* m = value_encode_typed(V, st, G, hp_.ptscale[level], nl);
+        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
+        if (e == hipSuccess) e = hipStreamSynchronize(S());
+        untmp(m, rows);
+        HIP_OK(e);
+        *scale = hp_.ptscale[level];
+    }
+
     // ------------------------------------------------------------------ key switching
     // returns (c0', c1') with c0' + c1' s = d s' (+ add0/add1 folded in); d NTT, level l
     // ModUp: coefficient form of d, every digit converted to all other limbs of Q*P in one
@@ -5720,6 +5886,8 @@ private:
     std::vector<uint8_t> h_pub_nib_[kStreams];  // their host staging copy
     uint8_t* d_val_nib_[kStreams] = {};        // xor_value_public: both public nibble arrays, hi then lo
     std::vector<uint8_t> h_val_nib_[kStreams];  // their host staging copy
+    uint8_t* d_val_typed_[kStreams] = {};        // xor_value_typed: weights, both nibble arrays, flags (stage_typed)
+    std::vector<uint8_t> h_val_typed_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;
@@ -5946,6 +6114,21 @@ int aesfhe_xor_value_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_h
 int aesfhe_debug_xor_value_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level,
                               uint32_t* out, double* scale) {
     API_BEGIN ctx->eng->debug_value_pt(table, nib_hi, nib_lo, n_slots, level, out, scale);
+    API_END
+}
+int aesfhe_xor_value_typed(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo, const uint8_t* nib_hi,
+                           const uint8_t* nib_lo, int n_slots, int n_groups, const double* weights, const uint8_t* flags, aesfhe_handle* out_t,
+                           aesfhe_handle* out_r) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out_t || !out_r) throw std::runtime_error("xor_value_typed: missing output handles");
+    Ct t[kValueGroups], r[kValueGroups];
+    e.xor_value_typed(table, a_hi, a_lo, nib_hi, nib_lo, n_slots, n_groups, weights, flags, t, r);
+    for (int g = 0; g < n_groups; ++g) out_t[g] = e.put_ct(t[g]), out_r[g] = e.put_ct(r[g]);
+    API_END
+}
+int aesfhe_debug_xor_value_typed_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int n_groups,
+                                    const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale) {
+    API_BEGIN ctx->eng->debug_value_typed_pt(table, nib_hi, nib_lo, n_slots, n_groups, weights, flags, level, out, scale);
     API_END
 }
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table) {

@@ -631,3 +631,25 @@ struct ValueMacArgs {
 };
 void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32* outR, const ValueMacArgs& a, int n, const u32* pt, int nl,
                              LimbMap map);
+
+// --- typed value decode: per-slot weights and a signed hi nibble ----------------
+// launch_value_slots with a real weight wt[j] per slot and, where flags[j] & 1, the signed-nibble table on the
+// channels marked flip[c] (the odd rows of the hi half: sval(x) = x - 16 [x >= 8] negates exactly those rows):
+// w[c][slot j] = (flags[j] & 1 && flip[c] ? -1 : 1) * wt[j] * tab[row[c]][nib].  flags may be null (no slot signed).
+struct ValueTypedSlotArgs {
+    ValueSlotArgs ch;
+    int flip[kValueCh] = {};
+};
+void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueTypedSlotArgs& ch,
+                              int nch, const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos);
+// launch_value_public_mac for G = 1 or 2 weight groups in ONE launch: outT[g] / outR[g] = the two sums over the
+// same n ciphertexts against group g's channels pt[(g * kValueCh + t) * nl ...]; every ciphertext word is read once
+// and used for all groups (n ciphertext and n G plaintext words per element, 2 G 64-bit sums); the 15-term limit
+// per sum is launch_value_public_mac's
+constexpr int kValueGroups = 2;
+struct ValueTypedOut {
+    u32* t[kValueGroups] = {};
+    u32* r[kValueGroups] = {};
+};
+void launch_value_typed_mac(hipStream_t st, const DevTables& T, const ValueTypedOut& out, int groups, const ValueMacArgs& a, int n,
+                            const u32* pt, int nl, LimbMap map);

@@ -152,6 +152,30 @@ __global__ void k_value_public_mac(u32* outT, u32* outR, ValueMacArgs a, int n, 
     outT[idx] = reduce64(accT, P.q, P.mu, P.r32);
     outR[idx] = reduce64(accR, P.q, P.mu, P.r32);
 }
+// k_value_public_mac for G weight groups (launch_value_typed_mac): group g's plaintext channels follow group g - 1's
+// (kValueCh channels each).  Each ciphertext word is loaded once and multiplied into all G groups; G is a template
+// argument, so the group loop unrolls and the 2 G sums stay in registers.  The 2^64 bound is per sum, as above
+template <int G>
+__global__ void k_value_typed_mac(ValueTypedOut o, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc, int logn) {
+    EW_PROLOGUE
+    const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
+    u64 accT[G] = {}, accR[G] = {};
+    for (int t = 0; t < n; ++t) {
+        const u64 c = a.a[t][idx];
+        const int real = a.real[t];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const u64 prod = c * pt[(size_t)(g * kValueCh + t) * chan + pidx];
+            if (real) accR[g] += prod;
+            else accT[g] += prod;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        o.t[g][idx] = reduce64(accT[g], P.q, P.mu, P.r32);
+        o.r[g][idx] = reduce64(accR[g], P.q, P.mu, P.r32);
+    }
+}
 __global__ void k_tensor(u32* out, const u32* a, const u32* b, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     // row = m * nl + limb: ciphertext m of a stacked batch ([m][2][nl] in, [m][3][nl] out)
     const int row = blockIdx.y;
@@ -1381,6 +1405,23 @@ __global__ void __launch_bounds__(kBlock) k_value_slots(double2* w, const double
     wc[t] = v;
     wc[n - 1 - t] = make_double2(v.x, -v.y);
 }
+// k_value_slots with a per-slot real weight and the signed-nibble sign (launch_value_slots_typed): one lane per slot,
+// weight, flag and nibble read coalesced; the sign is a select, not a branch
+__global__ void __launch_bounds__(kBlock) k_value_slots_typed(double2* w, const double2* tab, ValueTypedSlotArgs a, const uint8_t* nib,
+                                                              const double* wt, const uint8_t* flags, const u32* slot_pos, int logn) {
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
+    const int n = 1 << logn;
+    if (j >= n / 2) return;
+    const double2 e = tab[16 * a.ch.row[c] + (nib[(size_t)a.ch.half[c] * (n / 2) + j] & 15)];
+    const bool neg = a.flip[c] && flags && (flags[j] & 1);
+    const double s = neg ? -wt[j] : wt[j];
+    const double2 v = make_double2(e.x * s, e.y * s);
+    const u32 t = slot_pos[j];
+    double2* wc = w + ((size_t)c << logn);
+    wc[t] = v;
+    wc[n - 1 - t] = make_double2(v.x, -v.y);
+}
 
 // ------------------------------------------------------------------------------------
 // fused LUT evaluation: one launch per LUT instead of a tensor + constant + add per term
@@ -2301,4 +2342,37 @@ void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32*
     // reads: n ciphertexts and n plaintext channels; writes: two ciphertexts
     prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + 2) + (double)n * nl), k_value_public_mac, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st,
                 outT, outR, a, n, pt, nl, map, T.pc, T.logn);
+}
+void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueTypedSlotArgs& ch,
+                              int nch, const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos) {
+    if (nch < 1 || nch > kValueCh || !tab || !nib || !wt) throw std::runtime_error("launch_value_slots_typed: 1..16 channels, weights");
+    for (int c = 0; c < nch; ++c)
+        if (ch.ch.row[c] < 0 || ch.ch.row[c] >= tab_rows || (ch.ch.half[c] != 0 && ch.ch.half[c] != 1))
+            throw std::runtime_error("launch_value_slots_typed: bad channel map");
+    const double s = (double)(1u << (T.logn - 1));
+    const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
+    // reads: nibble, flag, weight, slot position; writes: two complex doubles
+    prof_launch(KID_ELEMENTWISE, nch * (2.0 * s + 8.0 * s + 4.0 * s + 32.0 * s), k_value_slots_typed, dim3(gx, nch), dim3(kBlock), 0, st,
+                (double2*)w, (const double2*)tab, ch, nib, wt, flags, slot_pos, T.logn);
+}
+void launch_value_typed_mac(hipStream_t st, const DevTables& T, const ValueTypedOut& out, int groups, const ValueMacArgs& a, int n,
+                            const u32* pt, int nl, LimbMap map) {
+    if (groups < 1 || groups > kValueGroups) throw std::runtime_error("launch_value_typed_mac: 1..2 groups");
+    if (n < 1 || n > kValueCh || !pt) throw std::runtime_error("launch_value_typed_mac: 1..16 ciphertexts");
+    for (int g = 0; g < groups; ++g)
+        if (!out.t[g] || !out.r[g]) throw std::runtime_error("launch_value_typed_mac: missing output");
+    int nr = 0;
+    for (int t = 0; t < n; ++t) {
+        if (!a.a[t]) throw std::runtime_error("launch_value_typed_mac: bad operand");
+        nr += a.real[t] != 0;
+    }
+    if (nr > 15 || n - nr > 15) throw std::runtime_error("launch_value_typed_mac: at most 15 terms per sum");
+    // reads: n ciphertexts and groups x n plaintext channels; writes: 2 x groups ciphertexts
+    const double bytes = 2.0 * nl * (n + 2 * groups) + (double)groups * n * nl;
+    if (groups == 1)
+        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<1>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n, pt, nl, map,
+                    T.pc, T.logn);
+    else
+        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<2>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n, pt, nl, map,
+                    T.pc, T.logn);
 }

@@ -433,3 +433,9 @@ class EngineContext:
         call (Engine.xor_value_public); R + T + conj(T) + constant is the value.  Modules test
         for it with getattr(ctx, "xor_value_public", None)."""
         return self.engine.xor_value_public(a_hi, a_lo, nib_hi, nib_lo, tab_hi, tab_lo)
+
+    def xor_value_typed(self, a_hi, a_lo, nib_hi, nib_lo, weights, flags=None):
+        """[(T_g, R_g)]: xor_value_public with a real weight and a signed-nibble flag per slot, for one or two
+        weight groups over the same powers -- one engine call (Engine.xor_value_typed).  Modules
+        test for it with getattr(ctx, "xor_value_typed", None)."""
+        return self.engine.xor_value_typed(a_hi, a_lo, nib_hi, nib_lo, weights, flags)

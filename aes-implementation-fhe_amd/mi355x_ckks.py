@@ -51,6 +51,7 @@ EXPORTED = [
     "aesfhe_set_low_p", "aesfhe_ks_special_primes", "aesfhe_lut_eval_public", "aesfhe_debug_public_pt",
     "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine", "aesfhe_export_ksk_at",
     "aesfhe_xor_value_create", "aesfhe_xor_value_public", "aesfhe_debug_xor_value_pt", "aesfhe_xor_value_free",
+    "aesfhe_xor_value_typed", "aesfhe_debug_xor_value_typed_pt",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -151,6 +152,8 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_xor_value_public"] = [vp, _H, _Hp, _Hp, _bp, _bp, c_int, _Hp, _Hp]
     sig["aesfhe_debug_xor_value_pt"] = [vp, _H, _bp, _bp, c_int, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_xor_value_free"] = [vp, _H]
+    sig["aesfhe_xor_value_typed"] = [vp, _H, _Hp, _Hp, _bp, _bp, c_int, c_int, vp, vp, _Hp, _Hp]
+    sig["aesfhe_debug_xor_value_typed_pt"] = [vp, _H, _bp, _bp, c_int, c_int, vp, vp, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -236,9 +239,10 @@ class _Handle:
 
 class Ciphertext(_Handle):
     """Device-resident RNS-CKKS ciphertext (opaque handle).  `layout`: the AES slot layout
-    (state_encoder.SlotLayout) the state encoder tagged it with, unset for plain ciphertexts"""
+    (state_encoder.SlotLayout) the state encoder tagged it with, unset for plain ciphertexts; `value_dtype`: the word
+    type a value ciphertext's slots hold (state_encoder.tag_value_dtype)"""
 
-    __slots__ = ("layout",)
+    __slots__ = ("layout", "value_dtype")
 
     @property
     def level(self) -> int:
@@ -1153,6 +1157,58 @@ class Engine:
         self._ctx.check(self._lib.aesfhe_debug_xor_value_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), int(level), out,
                                                             ctypes.byref(scale)))
         return out, scale.value
+
+    def _typed_args(self, nib_hi, nib_lo, weights, flags, what):
+        """(nib_hi, nib_lo, G, weights pointer ((G, slots) float64), flags pointer or None, the arrays kept alive)"""
+        nh, nl_ = self._nibble_array(nib_hi), self._nibble_array(nib_lo)
+        if nh.size != nl_.size:
+            raise ValueError(f"{what}: the two nibble arrays differ in length")
+        if weights is None:  # the engine refuses a null pointer ("missing weights")
+            return nh, nl_, 1, None, None, None
+        w = np.ascontiguousarray(np.atleast_2d(np.asarray(weights, np.float64)))
+        if w.ndim != 2 or w.shape[1] != nh.size:
+            raise ValueError(f"{what}: weights must be (groups, {nh.size}), got {w.shape}")
+        f = None
+        if flags is not None:
+            f = np.ascontiguousarray(np.atleast_2d(np.asarray(flags, np.uint8)))
+            if f.shape != w.shape:
+                raise ValueError(f"{what}: flags must have the weights' shape {w.shape}, got {f.shape}")
+        return nh, nl_, int(w.shape[0]), w.ctypes.data_as(ctypes.c_void_p), (f.ctypes.data_as(ctypes.c_void_p) if f is not None else None), (w, f)
+
+    def xor_value_typed(self, a_hi, a_lo, nib_hi, nib_lo, weights, flags=None):
+        """[(T_g, R_g)] of the typed value decode (aesfhe_xor_value_typed): xor_value_public on the
+        unit tables (16 E, E) with a real weight per slot and, where flags & 1, a SIGNED hi nibble, for G = 1 or 2
+        weight groups over the same powers -- R_g + T_g + conj(T_g) + w_g (16 c + 7.5), c = -0.5 on flagged slots and
+        7.5 elsewhere, is group g's value.  weights: (G, slot_count) or (slot_count,) float64, finite; flags: the
+        same shape of uint8, or None.  Errors as xor_value_public's, plus "n_groups", "weight not finite"."""
+        nh, nl_, G, w, fp, _keep = self._typed_args(nib_hi, nib_lo, weights, flags, "xor_value_typed")
+        self._ensure_keys()
+        E = self._unit_value_tables()
+        tab = self._value_table(*E)
+        n_out = max(1, min(G, 2))
+        t, r = (ctypes.c_uint64 * n_out)(), (ctypes.c_uint64 * n_out)()
+        self._ctx.check(self._lib.aesfhe_xor_value_typed(self._ctx.ptr, tab.handle, self._power_handles(a_hi), self._power_handles(a_lo),
+                                                         nh, nl_, int(nh.size), G, w, fp, t, r))
+        return [(Ciphertext(self._ctx, t[g]), Ciphertext(self._ctx, r[g])) for g in range(G)]
+
+    def debug_xor_value_typed_pt(self, nib_hi, nib_lo, weights, flags, level: int):
+        """tests: (rows, scale) -- the G x 16 coefficient plaintexts xor_value_typed multiplies by at `level` as
+        (G, 16, nl(level), N) uint32 in NTT form (debug_xor_value_pt's channel order per group), and their scale"""
+        nh, nl_, G, w, fp, _keep = self._typed_args(nib_hi, nib_lo, weights, flags, "debug_xor_value_typed_pt")
+        self._ensure_keys()
+        tab = self._value_table(*self._unit_value_tables())
+        out = np.zeros((max(1, min(G, 2)), 16, self.nl(level), self.n), np.uint32)
+        scale = ctypes.c_double(0.0)
+        self._ctx.check(self._lib.aesfhe_debug_xor_value_typed_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), G, w, fp, int(level),
+                                                                  out, ctypes.byref(scale)))
+        return out, scale.value
+
+    @staticmethod
+    def _unit_value_tables():
+        """the unit tables the typed decode is created with: 16 E for the hi nibble, E for the lo one"""
+        from coeffgen import xor_value_table
+        E = xor_value_table()[:9]
+        return np.ascontiguousarray(16.0 * E), np.ascontiguousarray(E)
 
     # ------------------------------------------------------------------ raw access (tests)
     def moduli(self) -> np.ndarray:

@@ -47,7 +47,9 @@ snapshots).  Its pairs are tagged transposed and refused by a plain pipeline (ch
 
 Real-valued slots (xor_value_lut.py): ``transcipher_values`` / ``to_values`` return ONE ciphertext whose
 state slots hold gain * byte as real numbers (read back by ``encoder.decode_values``) instead of the Zeta16 pair -- the
-last public XOR of counter mode fused with the value decode, no renorm after the keystream.
+last public XOR of counter mode fused with the value decode, no renorm after the keystream.  ``dtype`` / ``gain`` /
+``offset`` read the bytes as int8 / uint8 or 16-bit words of either sign and byte order, with per-word
+gains and offsets, for no further level.
 
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
 11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
@@ -69,7 +71,7 @@ from key_expansion import EncryptedRoundKeys, KeyExpansion
 from inv_shiftrows import InvShiftRows
 from mixcol_final import MixColFinal
 from shift_rows import ShiftRows
-from state_encoder import StateEncoder, check_layout, tag_layout
+from state_encoder import StateEncoder, check_layout, tag_layout, tag_value_dtype
 from shift_rows import shift_rows_bytes
 from shiftrows_mixcolumns import ShiftRowsMixColumnsFusedEnc
 from sub_bytes_ark import SubBytesARK
@@ -588,8 +590,18 @@ class AESPipeline:
             self._value_luts[g] = XorValueLUT(self.ctx, g)
         return self._value_luts[g]
 
+    def _typed_lut(self, dtype, gain, offset):
+        """None: today's path (unsigned bytes times one scalar gain, no offset: XorValueLUT, unchanged); else the
+        TypedValueLUT of the value spec in this pipeline's layout and byte order"""
+        from state_encoder import value_dtype
+        w = value_dtype(dtype)[0]  # ValueError for anything but the six types
+        if dtype == "u1" and (gain is None or np.ndim(gain) == 0) and np.ndim(offset) == 0 and float(offset) == 0.0:
+            return None
+        from xor_value_lut import TypedValueLUT
+        return TypedValueLUT(self.ctx, self.encoder.value_slots((dtype, 256.0 ** -w if gain is None else gain, offset)))
+
     def transcipher_values(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys,
-                           gain: float = 1.0 / 256.0):
+                           gain=None, dtype: str = "u1", offset=0.0):
         """AES-CTR transciphering to REAL-VALUED slots: transcipher's inputs, but the result is ONE layout-tagged
         ciphertext whose state slots hold gain * m as real numbers (in [0, 1) at the default gain; slots that hold
         no state hold 0) -- what a CKKS program can add, multiply or average, read back by encoder.decode_values.
@@ -597,19 +609,30 @@ class AESPipeline:
         (xor_value_lut.XorValueLUT.apply_public): no XOR4, no renorm and no bootstrap come after the keystream, whose
         own last renorm (secret-key, or bootstrap + snap with true_fhe) is the last one.  The keystream is NOT
         dropped first: the output sits utils.XOR_VALUE_DEPTH = 4 levels below the keystream's fresh level (3 on the
-        fresh-level-7 set, 13 on the default 17 / 5 set), and those levels are the caller's to compute with."""
+        fresh-level-7 set, 13 on the default 17 / 5 set), and those levels are the caller's to compute with.
+
+        Typed numbers, for no further level: dtype "u1" / "i1" (bytes) or "<u2" / ">u2" / "<i2" /
+        ">i2" (16-bit words, w = 2 bytes, either byte order); gain and offset scalars or arrays broadcastable to
+        (16 // w,) or (states, 16 // w) (gain None: 256^-w).  The slot of each word's first byte holds
+        gain * q + offset, q the integer the message bytes spell in `dtype`; every other slot holds 0.
+        decode_values returns (states, 16 // w).  dtype "u1" with a scalar gain and no offset is the path above,
+        unchanged; any other dtype (32-bit words would add no precision over 16) raises ValueError."""
         self._no_pairs("transcipher_values")
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
-        lut = self._value_lut(gain)
+        typed = self._typed_lut(dtype, gain, offset)
+        lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
-        return tag_layout(self.layout, lut.apply_public(*ks, *nib))[0]
+        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
 
-    def to_values(self, ct_hi, ct_lo, gain: float = 1.0 / 256.0):
+    def to_values(self, ct_hi, ct_lo, gain=None, dtype: str = "u1", offset=0.0):
         """a clean layout-tagged (hi, lo) pair -- the output of encrypt, decrypt or transcipher -- as ONE ciphertext of
-        gain * byte per state slot (XorValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair)"""
+        gain * byte per state slot (XorValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair); dtype, gain and
+        offset as transcipher_values'"""
         self._no_pairs("to_values")
         check_layout(self.layout, ct_hi, ct_lo)
-        return tag_layout(self.layout, self._value_lut(gain).apply(ct_hi, ct_lo))[0]
+        typed = self._typed_lut(dtype, gain, offset)
+        lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
+        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):

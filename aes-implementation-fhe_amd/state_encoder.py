@@ -120,6 +120,43 @@ def _describe(lay: SlotLayout) -> str:
     return f"{'periodic' if lay.periodic else 'reference'} (states={lay.states}{order})"
 
 
+# the value decode's word types: name -> (bytes per word, signed, little-endian)
+VALUE_DTYPES = {"u1": (1, False, True), "i1": (1, True, True), "<u2": (2, False, True), ">u2": (2, False, False),
+                "<i2": (2, True, True), ">i2": (2, True, False)}
+
+
+def value_dtype(dtype):
+    """(width, signed, little) of a value dtype; ValueError for anything else.  32-bit words are refused on
+    purpose: a word's error is its top byte's error times 256^(w - 1), so a 16-bit word is already good to ~13
+    bits only and wider words would add no precision"""
+    if dtype not in VALUE_DTYPES:
+        raise ValueError(f"value dtype must be one of {sorted(VALUE_DTYPES)}, got {dtype!r} (words wider than 16 bits would add "
+                         "no precision over 16: the top byte's error times 256^(w - 1) dominates)")
+    return VALUE_DTYPES[dtype]
+
+
+class ValueSlots:
+    """StateEncoder.value_slots' result: weights / flags (G, slots) for the G = width groups, the per-slot
+    constant (group constants rotated onto the word slot, plus the offset), and the rotation distance that
+    brings group 1 onto group 0 (0 for 8-bit types)"""
+
+    def __init__(self, dtype, weights, flags, const, distance):
+        self.dtype, self.weights, self.flags, self.const, self.distance = dtype, weights, flags, const, distance
+
+    @property
+    def groups(self) -> int:
+        return self.weights.shape[0]
+
+
+def tag_value_dtype(dtype, ct):
+    """mark a value ciphertext with the dtype its slots hold (decode_values' default); returns it"""
+    try:
+        ct.value_dtype = dtype
+    except AttributeError:  # a context whose ciphertexts carry no tag
+        pass
+    return ct
+
+
 class StateEncoder:
     """pairs > 1: a multi-pair batch -- `pairs` independent ciphertext pairs,
     each holding `states` states in this layout, carried as ONE stacked hi and ONE stacked lo
@@ -222,25 +259,85 @@ class StateEncoder:
         out = self._order(((hi << 4) | lo).astype(np.uint8))
         return out[0] if self.states == 1 else out
 
-    def values_from_slots(self, slots: np.ndarray) -> np.ndarray:
-        """the pure unpacking of decode_values: a slot vector whose state slots hold one real number per byte
-        (xor_value_lut.XorValueLUT's output) -> the (states, 16) float array in the caller's byte order, (16,) for one
-        state -- _pack's slot order and the encoder's byte order undone, imaginary parts dropped"""
+    def _float_slots(self, per_byte: np.ndarray) -> np.ndarray:
+        """(states, 16) floats in the caller's byte order -> the slot vector with each number in its byte's slot
+        and 0 in every slot that holds no state (nibble_slots' placement, on floats)"""
+        v = np.asarray(per_byte, np.float64).reshape(self.states, 16)
+        if self.byte_order == "transposed":  # shift_columns.transpose_bytes' map, on floats
+            v = np.swapaxes(v.reshape(-1, 4, 4), -1, -2).reshape(v.shape)
+        grid = np.zeros((16, self.stride), np.float64)
+        grid[:, :self.states] = v.T
+        return np.ascontiguousarray(self.layout.tile(grid.reshape(-1)))
+
+    @property
+    def word_distance(self) -> int:
+        """the slot distance between bytes 2k and 2k + 1 of a block in this layout and byte order: the rotation
+        that brings a 16-bit word's second byte onto its first (unit in the plain order, 4 unit transposed)"""
+        at = self._order(np.arange(16, dtype=np.uint8)[None, :])[0].astype(np.int64)  # an involution: where byte i sits
+        d = {int(at[2 * k + 1] - at[2 * k]) for k in range(8)}
+        assert len(d) == 1 and min(d) > 0
+        return d.pop() * self.stride
+
+    def value_slots(self, spec) -> "ValueSlots":
+        """spec = (dtype, gain, offset): the per-slot weights, flags and constant with which the value decode
+        (xor_value_lut.TypedValueLUT) leaves gain * q + offset in the slot of each word's first
+        byte, q the integer the word's bytes spell in `dtype`, and 0 in every other slot.  dtype: one of
+        VALUE_DTYPES; gain, offset: scalars or arrays broadcastable to (16 // w,) or (states, 16 // w), w the
+        word's width in bytes (gain None: 256^-w).  Group g weighs byte g of every word by gain * 256^(its
+        significance); the top byte of a signed type carries flag 1 (signed hi nibble)."""
+        dtype, gain, offset = spec
+        w, signed, little = value_dtype(dtype)
+        nw = 16 // w
+        try:
+            g = np.broadcast_to(np.asarray(256.0 ** -w if gain is None else gain, np.float64), (self.states, nw))
+            off = np.broadcast_to(np.asarray(offset, np.float64), (self.states, nw))
+        except ValueError:
+            raise ValueError(f"value_slots: gain and offset must broadcast to ({nw},) or ({self.states}, {nw}) for dtype {dtype!r}") from None
+        if not (np.all(np.isfinite(g)) and np.all(np.isfinite(off))):
+            raise ValueError("value_slots: gain and offset must be finite")
+        weights, flags = np.zeros((w, self.sc)), np.zeros((w, self.sc), np.uint8)
+        const = np.zeros(self.sc)
+        first = np.zeros((self.states, 16))
+        first[:, ::w] = off
+        const += self._float_slots(first)  # the offset sits with the word: the slot of its first byte
+        for j in range(w):  # group j: byte j of every word
+            sig = j if little else w - 1 - j
+            top = signed and sig == w - 1
+            wb, fb = np.zeros((self.states, 16)), np.zeros((self.states, 16))
+            wb[:, j::w] = g * 256.0 ** sig
+            fb[:, j::w] = 1.0 if top else 0.0
+            weights[j] = self._float_slots(wb)
+            flags[j] = self._float_slots(fb).astype(np.uint8)
+            # E_0 of both nibbles: 16 * 7.5 + 7.5, the signed hi nibble's E_0 is -0.5; rotated with its group
+            const += np.roll(weights[j] * (16.0 * (-0.5 if top else 7.5) + 7.5), -j * self.word_distance)
+        return ValueSlots(dtype, weights, flags, const, self.word_distance if w > 1 else 0)
+
+    def values_from_slots(self, slots: np.ndarray, dtype=None) -> np.ndarray:
+        """the pure unpacking of decode_values: a slot vector whose word slots hold one real number per word
+        (xor_value_lut's output) -> the (states, 16 // w) float array in the caller's byte order, (16 // w,) for one
+        state -- _pack's slot order and the encoder's byte order undone, imaginary parts dropped.  dtype None: bytes"""
+        w = value_dtype("u1" if dtype is None else dtype)[0]
         slots = np.asarray(slots)
         if slots.shape != (self.sc,):
             raise ValueError(f"expected a slot vector of {self.sc} entries, got shape {slots.shape}")
         v = np.ascontiguousarray(self._take(slots.real.astype(np.float64)))
         if self.byte_order == "transposed":  # shift_columns.transpose_bytes' map, on floats
             v = np.ascontiguousarray(np.swapaxes(v.reshape(-1, 4, 4), -1, -2)).reshape(v.shape)
+        if w > 1:
+            v = np.ascontiguousarray(v[:, ::w])  # a word sits in the slot of its first byte
         return v[0] if self.states == 1 else v
 
-    def decode_values(self, ct) -> np.ndarray:
+    def decode_values(self, ct, dtype=None) -> np.ndarray:
         """client side: decrypt a value ciphertext (AESPipeline.transcipher_values / to_values) into the
-        (states, 16) float array of gain * byte, (16,) for one state"""
+        (states, 16 // w) float array of gain * q + offset, (16 // w,) for one state.  The ciphertext carries the
+        dtype it was made with (tag_value_dtype): that is the default, and a contradicting `dtype` is refused"""
         if self.pairs > 1:
             raise ValueError("decode_values: multi-pair batches (pairs > 1) are not supported")
         check_layout(self.layout, ct)
-        return self.values_from_slots(self.ctx.decrypt(ct))
+        tag = getattr(ct, "value_dtype", None)
+        if dtype is not None and tag is not None and dtype != tag:
+            raise ValueError(f"decode_values: the ciphertext holds {tag!r} values, asked for {dtype!r}")
+        return self.values_from_slots(self.ctx.decrypt(ct), dtype if dtype is not None else tag)
 
     # ---------------------------------------------------------------- packed form (DESIGN.md §4c)
     PACK_DEPTH = 1  # pack(): one plaintext product

@@ -18,6 +18,8 @@ utils.XOR_VALUE_DEPTH = 4 levels.  With b = 0 everywhere this is the plain decod
 
 The last XOR of counter mode has a public operand (the AES ciphertext byte), so transciphering ends here instead of
 in an XOR4, a renorm and a separate decode: AESPipeline.transcipher_values.
+
+TypedValueLUT is the same sum with per-slot weights, a signed top nibble and 16-bit words.
 """
 from typing import Any, Dict
 
@@ -104,3 +106,86 @@ class XorValueLUT:
         return self.apply_public(hi, lo, zero, zero)
 
     __call__ = apply
+
+
+class TypedValueLUT(XorValueLUT):
+    """The value decode to TYPED numbers: int8 / uint8 bytes or 16-bit words of either sign and
+    byte order, times a per-word gain plus a per-word offset, for no level beyond XorValueLUT's four.
+
+    The decoded value is linear in the table, so a real weight per slot scales it per slot; a signed top nibble
+    is the same table with its odd rows negated (coeffgen.xor_value_table(signed=True)); and with group g's weights
+    non-zero only on byte g of each word, X_0 + rotate(X_1, d) holds the word in the slot of its first byte and 0
+    everywhere else -- no mask.  By linearity that is (R_0 + rot R_1) + V + conj(V) + const with V = T_0 + rot T_1:
+    two rotations (one batched key switch) and one conjugation.
+
+    spec: a state_encoder.ValueSlots (StateEncoder.value_slots((dtype, gain, offset)))."""
+
+    def __init__(self, ctx, spec):
+        super().__init__(ctx, 1.0)  # the unit tables 16 E and E: the weights carry the gain
+        if spec.weights.shape != (spec.groups, self.sc) or spec.flags.shape != spec.weights.shape or spec.const.shape != (self.sc,):
+            raise ValueError(f"value spec: per-slot vectors of {self.sc} entries")
+        if not 1 <= spec.groups <= 2:
+            raise ValueError("value spec: one or two weight groups")
+        self.spec = spec
+        self.weights = np.ascontiguousarray(spec.weights, np.float64)
+        self.flags = np.ascontiguousarray(spec.flags, np.uint8)
+        self.const = np.ascontiguousarray(spec.const, np.float64)  # per slot, unlike XorValueLUT's scalar
+        self.distance = int(spec.distance)
+        E, Es = xor_value_table()[:9], xor_value_table(signed=True)[:9]
+        self._tabs = (16.0 * E, 16.0 * Es, E)  # hi unsigned, hi signed, lo (the fallback's)
+
+    def _engine(self, A_hi, A_lo, nib_hi, nib_lo):
+        """[(T_g, R_g)] from ONE engine call (Engine.xor_value_typed); None as XorValueLUT._engine"""
+        ctx = self.ctx
+        ev = getattr(ctx, "xor_value_typed", None)
+        if ev is None or not getattr(ctx, "fused_luts", False):
+            return None
+        try:
+            return ev(A_hi, A_lo, nib_hi, nib_lo, self.weights, self.flags if self.flags.any() else None)
+        except RuntimeError as e:
+            if "level" in str(e):
+                return None
+            raise
+
+    def _loop(self, A_hi, A_lo, nib_hi, nib_lo):
+        """[(T_g, R_g)] as the product loop, the weights and the sign folded into the encoded coefficient vectors"""
+        ctx = self.ctx
+        hi_u, hi_s, lo = self._tabs
+        out = []
+        for w, f in zip(self.weights, self.flags):
+            signed = (f & 1).astype(bool)
+            T = R = None
+            for A, nib, half in ((A_hi, nib_hi, 0), (A_lo, nib_lo, 1)):
+                for p in range(1, 9):
+                    c = lo[p, nib] if half else np.where(signed, hi_s[p, nib], hi_u[p, nib])
+                    t = ctx.multiply(A[p], ctx.encode(w * c))
+                    if p == 8:
+                        R = t if R is None else ctx.add(R, t)
+                    else:
+                        T = t if T is None else ctx.add(T, t)
+            out.append((T, R))
+        return out
+
+    def _rotate_pairs(self, cts):
+        """[rotate(ct, -distance)]: slot j takes slot j + distance (the word's second byte onto its first), the
+        independent rotations as one batched key switch where the context has it"""
+        ctx = self.ctx
+        multi = getattr(ctx, "rotate_multi", None)
+        if multi is not None:
+            return multi([(c, -self.distance) for c in cts])
+        return [ctx.rotate(c, -self.distance) for c in cts]
+
+    def apply_public(self, hi, lo, nib_hi, nib_lo):
+        """ONE ciphertext whose word slots hold gain * q + offset, q the integer the XORed bytes spell in the spec's
+        dtype, and whose other slots hold 0; XOR_VALUE_DEPTH levels below the inputs"""
+        ctx = self.ctx
+        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
+        A_hi, A_lo = self._bases(hi, lo)
+        out = self._engine(A_hi, A_lo, nib_hi, nib_lo)
+        if out is None:
+            out = self._loop(A_hi, A_lo, nib_hi, nib_lo)
+        T, R = out[0]
+        if len(out) == 2:
+            t1, r1 = self._rotate_pairs(list(out[1]))
+            T, R = ctx.add(T, t1), ctx.add(R, r1)
+        return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)

@@ -191,6 +191,31 @@ int aesfhe_xor_value_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_h
  * nl(level) limbs of N words each, NTT form -- and the scale they were encoded at */
 int aesfhe_debug_xor_value_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level,
                               uint32_t* out, double* scale);
+/* Typed value decode: aesfhe_xor_value_public with a real WEIGHT and a sign FLAG per slot, for
+ * n_groups G = 1 or 2 weight groups over the same operands.  The decoded value is linear in the table, so weight
+ * w(s) on every coefficient of slot s gives w(s) * value; a set flag bit 0 makes the hi nibble SIGNED
+ * (sval(x) = x - 16 [x >= 8]: the hi table's odd rows negated, since only bit 3 changes weight and bit 3 lives in
+ * the odd powers), so 16 sval(hi ^ b_hi) + (lo ^ b_lo) is the two's-complement byte.  `table` is a handle of
+ * aesfhe_xor_value_create made from the UNIT tables (16 E and E); the weights carry the gain.
+ *   weights: G x n_slots doubles, group-major, all finite (else an error containing "weight not finite"; a null
+ *            pointer: "missing weights");  flags: G x n_slots bytes or NULL (no slot signed);
+ *   n_groups outside 1..2: an error containing "n_groups".  Everything aesfhe_xor_value_public refuses is refused
+ *   with the same words; a refused call leaves every handle intact.
+ * Returns G pairs, out_t[g] and out_r[g] (arrays of n_groups handles):
+ *     out_t[g] = sum_{p = 1..7} w_g s_p E_p[b_hi] hi^p + w_g E_p[b_lo] lo^p,   out_r[g] = w_g (E_8[b_hi] hi^8 + E_8[b_lo] lo^8)
+ * with s_p = -1 on odd p of a flagged slot and 1 elsewhere, so that out_r[g] + out_t[g] + conj(out_t[g]) +
+ * w_g (16 c + 7.5) is group g's value (c = -0.5 on a flagged slot, 7.5 elsewhere).  For 16-bit words group g weighs
+ * byte g of each word (0 on every other slot) and the caller adds group 1 rotated by the slot distance of the two
+ * bytes onto group 0: no mask, no extra level.  One codec pass per group encodes the G x 16 coefficient
+ * plaintexts; ONE kernel forms all 2 G sums, reading every ciphertext word once.  Levels, the owed rescale and the
+ * copy-before-return rule are aesfhe_xor_value_public's. */
+int aesfhe_xor_value_typed(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo,
+                           const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int n_groups,
+                           const double* weights, const uint8_t* flags, aesfhe_handle* out_t, aesfhe_handle* out_r);
+/* tests only: the G x 16 coefficient plaintexts aesfhe_xor_value_typed multiplies by at `level` (>= 1) -- group g's
+ * 16 channels (aesfhe_debug_xor_value_pt's order) after group g - 1's -- and the scale they were encoded at */
+int aesfhe_debug_xor_value_typed_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                                    int n_groups, const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale);
 /* Releases a value table; fails if `table` is not one.  aesfhe_free also accepts value tables. */
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table);
 /* Deferred evaluation switch, default on: API-level ct x ct products
