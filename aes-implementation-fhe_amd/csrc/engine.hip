@@ -1662,42 +1662,145 @@ public:
         L.pub_rows = rows;
         L.pub_mag = mag;
     }
-    // the public nibbles checked and copied into this stream's staging buffers (host, then device: the caller's
-    // array is free again when the call returns)
-    const uint8_t* stage_nibbles(const uint8_t* nib, int n_slots) {
-        const int s = slot_count();
-        if (!nib || n_slots != s) throw std::runtime_error("lut_eval_public: one nibble per slot (n_slots must equal slot_count)");
-        std::vector<uint8_t>& h = h_pub_nib_[t_sidx];
-        h.resize(s);
-        for (int j = 0; j < s; ++j) {
-            if (nib[j] >= 16) throw std::runtime_error("lut_eval_public: nibble out of range (>= 16) at slot " + std::to_string(j));
-            h[j] = nib[j];
-        }
-        if (!d_pub_nib_[t_sidx]) d_pub_nib_[t_sidx] = (uint8_t*)dev_alloc(((size_t)s + 3) / 4);
-        HIP_OK(hipMemcpyAsync(d_pub_nib_[t_sidx], h.data(), (size_t)s, hipMemcpyHostToDevice, S()));
-        return d_pub_nib_[t_sidx];
+
+    // ------------------------------------------------------------------ plumbing of the public-operand ops
+    // lut_eval_public (§3.8) and the value decode (§3.20, §3.21) share everything on the host: operand checks,
+    // the operands' canonical form at their common level, the nibble staging, the device codec, one MAC launch,
+    // the owed rescale and the release of the temporaries.  `who` is the entry point's message prefix.
+    static void need_slots(const std::string& who, bool ok) {
+        if (!ok) throw std::runtime_error(who + ": one nibble per slot (n_slots must equal slot_count)");
     }
-    // the per-slot coefficient plaintexts of one or two LUTs' used rows, encoded on the device at `scale` on nl
-    // limbs: k_public_slots -> inverse FFT -> untwist / round / reduce -> forward NTT.  Returns nch x nl rows
-    // (tmp; the caller untmps); the FFT scratch goes back to the pool here
-    u32* public_encode(const Lut& L1, const Lut* L2, const uint8_t* d_nib, double scale, int nl) {
-        const int n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0);
-        u32* wb = tmp((size_t)4 * nch);  // [nch][N] complex double: 4 rows per channel
+    // one nibble per slot checked (< 16) and copied to dst
+    void copy_nibbles(const std::string& who, const uint8_t* nib, uint8_t* dst) const {
+        for (int j = 0, s = slot_count(); j < s; ++j) {
+            if (nib[j] >= 16) throw std::runtime_error(who + ": nibble out of range (>= 16) at slot " + std::to_string(j));
+            dst[j] = nib[j];
+        }
+    }
+    // the n operands checked (single nonzero two-polynomial ciphertexts); returns their common lowest logical
+    // level, at least 1.  `what`: the op's name in the level refusal
+    int public_operands(const std::string& who, const char* what, const aesfhe_handle* A, int n) {
+        int l = 1 << 30;
+        for (int t = 0; t < n; ++t) {
+            if (!A[t]) throw std::runtime_error(who + ": missing element handle of a used row");
+            const Ct& c = ct(A[t]);
+            if (c.nb != 1) throw std::runtime_error(who + ": stacked operands are not supported (single ciphertexts only)");
+            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error(who + ": nonzero 2-polynomial ciphertexts");
+            l = std::min(l, c.level - c.pend);
+        }
+        if (l < 1) throw std::runtime_error(std::string("not enough level for the ") + what + " (level 0)");
+        return l;
+    }
+    // a[t]: operand t canonical (NTT, two polynomials, nothing owed) and dropped exactly to level l; what this had
+    // to allocate joins `own`.  Counts one plaintext product per operand
+    void operands_at(const aesfhe_handle* A, int n, int l, const u32** a, std::vector<Ct>& own) {
+        for (int t = 0; t < n; ++t) {
+            const Ct& c = ct(A[t]);
+            Ct x = c;
+            if (pm(c) != 2 || c.pend || !c.ntt) {
+                x = normalize(c, true);
+                if (x.data != c.data) own.push_back(x);
+            }
+            if (x.level != l) {
+                const u32* before = x.data;
+                x = level_down(x, l);
+                if (x.data != before && x.data != c.data) own.push_back(x);
+            }
+            a[t] = x.data;
+            cnt_[C_PTMUL]++;
+        }
+    }
+    // the device codec of per-slot coefficient plaintexts: for each group g, fill(g, w) launches the caller's slots
+    // kernel into the FFT scratch w ([nch][N] complex double), then inverse FFT -> untwist / round / reduce at
+    // `scale` on nl limbs -> forward NTT into rows [g][nch][nl].  Returns groups x nch x nl rows (tmp; the caller
+    // untmps); the FFT scratch goes back to the pool here
+    template <class Fill>
+    u32* encode_channels(int groups, int nch, double scale, int nl, Fill fill) {
+        const size_t grp = (size_t)nch * nl;
+        u32* wb = tmp((size_t)4 * nch);  // 4 rows per channel
         u32* m = nullptr;
         try {
-            m = tmp((size_t)nch * nl);
-            launch_public_slots(S(), T_, (double*)wb, (const double*)L1.pub.first, n1, L2 ? (const double*)L2->pub.first : nullptr, nch, d_nib,
-                                d_slot_pos_);
-            launch_fft2(S(), T_, (double*)wb, -1, nch);
-            launch_encode_untwist(S(), T_, m, (const double*)wb, scale, nl, nch);
-            ntt(m, nch * nl, nl, qmap());
+            m = tmp(groups * grp);
+            for (int g = 0; g < groups; ++g) {
+                u32* mg = m + g * grp * hp_.n;
+                fill(g, (double*)wb);
+                launch_fft2(S(), T_, (double*)wb, -1, nch);
+                launch_encode_untwist(S(), T_, mg, (const double*)wb, scale, nl, nch);
+                ntt(mg, nch * nl, nl, qmap());
+            }
         } catch (...) {
             untmp(wb, (size_t)4 * nch);
-            if (m) untmp(m, (size_t)nch * nl);
+            if (m) untmp(m, groups * grp);
             throw;
         }
         untmp(wb, (size_t)4 * nch);
         return m;
+    }
+    // what one op holds while it runs: `own` is released when it ends, either way; `res` (the results) and `m` (the
+    // encoded rows, while they live) only when it throws.  A finished op counts as one LUT evaluation
+    struct PubTemps {
+        std::vector<Ct> own, res;
+        u32* m = nullptr;
+        size_t mrows = 0;
+    };
+    template <class Body>
+    void public_op(Body body) {
+        PubTemps s;
+        try {
+            body(s);
+        } catch (...) {
+            if (s.m) untmp(s.m, s.mrows);
+            for (const Ct& x : s.own) release(x);
+            for (const Ct& x : s.res) release(x);
+            throw;
+        }
+        for (const Ct& x : s.own) release(x);
+        cnt_[C_LUT]++;
+    }
+    // a MAC output owes its rescale as mul_pt_sum's; applied here when the raw scale has no headroom for a message
+    // of magnitude `mag` (the raw ciphertext then joins `own`, and `res` follows the rescaled one)
+    void owe_rescale(Ct& out, Ct& res, double mag, std::vector<Ct>& own) {
+        out.pend = 1;
+        out.lazy = true;
+        if (!headroom(out.level, 1, mag)) {
+            Ct r = rescale(out);
+            own.push_back(out);
+            res = out = r;
+        }
+    }
+    // tests: the debug readbacks' argument checks, and `rows` encoded rows (tmp: back to the pool here) copied out
+    // with their scale
+    void debug_args(const std::string& who, int level, const u32* out, const double* scale) const {
+        if (level < 1 || level > hp_.L) throw std::runtime_error(who + ": level out of range (1..max level)");
+        if (!out || !scale) throw std::runtime_error(who + ": missing output buffers");
+    }
+    void read_rows(u32* m, size_t rows, int level, u32* out, double* scale) {
+        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
+        if (e == hipSuccess) e = hipStreamSynchronize(S());
+        untmp(m, rows);
+        HIP_OK(e);
+        *scale = hp_.ptscale[level];
+    }
+
+    // the public nibbles checked and copied into this stream's staging buffers (host, then device: the caller's
+    // array is free again when the call returns)
+    const uint8_t* stage_nibbles(const uint8_t* nib, int n_slots) {
+        const int s = slot_count();
+        need_slots("lut_eval_public", nib && n_slots == s);
+        std::vector<uint8_t>& h = h_pub_nib_[t_sidx];
+        h.resize(s);
+        copy_nibbles("lut_eval_public", nib, h.data());
+        if (!d_pub_nib_[t_sidx]) d_pub_nib_[t_sidx] = (uint8_t*)dev_alloc(((size_t)s + 3) / 4);
+        HIP_OK(hipMemcpyAsync(d_pub_nib_[t_sidx], h.data(), (size_t)s, hipMemcpyHostToDevice, S()));
+        return d_pub_nib_[t_sidx];
+    }
+    // the per-slot coefficient plaintexts of one or two LUTs' used rows (k_public_slots into encode_channels):
+    // nch x nl rows (tmp)
+    u32* public_encode(const Lut& L1, const Lut* L2, const uint8_t* d_nib, double scale, int nl) {
+        const int n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0);
+        return encode_channels(1, nch, scale, nl, [&](int, double* w) {
+            launch_public_slots(S(), T_, w, (const double*)L1.pub.first, n1, L2 ? (const double*)L2->pub.first : nullptr, nch, d_nib, d_slot_pos_);
+        });
     }
     // out_k = sum_p D_k,p[nib] (.) a[p] for lut1 (and lut2): the operands canonical and dropped exactly to their
     // common lowest logical level l, the coefficient plaintexts encoded at ptscale[l], ONE k_lut_public_mac launch
@@ -1715,87 +1818,41 @@ public:
                 if (std::find(rows.begin(), rows.end(), p) == rows.end()) rows.push_back(p);
         const int n = (int)rows.size();
         if (n > kMaxMembers) throw std::runtime_error("lut_eval_public: at most 8 used rows");
-        int l = 1 << 30;
-        for (int p : rows) {
-            if (!A[p]) throw std::runtime_error("lut_eval_public: missing element handle of a used row");
-            const Ct& c = ct(A[p]);
-            if (c.nb != 1) throw std::runtime_error("lut_eval_public: stacked operands are not supported (single ciphertexts only)");
-            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("lut_eval_public: nonzero 2-polynomial ciphertexts");
-            l = std::min(l, c.level - c.pend);
-        }
-        if (l < 1) throw std::runtime_error("not enough level for the public-operand LUT (level 0)");
+        aesfhe_handle used[kMaxMembers];
+        for (int t = 0; t < n; ++t) used[t] = A[rows[t]];
+        const int l = public_operands("lut_eval_public", "public-operand LUT", used, n);
         const uint8_t* d_nib = stage_nibbles(nib, n_slots);
-        const int nl = hp_.nl(l), n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0);
-        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
-        u32* m = nullptr;
+        const int nl = hp_.nl(l), n1 = (int)L1.pub_rows.size(), nch = n1 + (L2 ? (int)L2->pub_rows.size() : 0), no = L2 ? 2 : 1;
         Ct out[2];
-        try {
+        public_op([&](PubTemps& s) {
             PubMacArgs a;
-            for (int t = 0; t < n; ++t) {
-                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
-                const Ct& c = ct(A[rows[t]]);
-                Ct x = c;
-                if (pm(c) != 2 || c.pend || !c.ntt) {
-                    x = normalize(c, true);
-                    if (x.data != c.data) own.push_back(x);
-                }
-                if (x.level != l) {
-                    const u32* before = x.data;
-                    x = level_down(x, l);
-                    if (x.data != before && x.data != c.data) own.push_back(x);
-                }
-                a.a[t] = x.data;
-                auto chan = [&](const std::vector<int>& r, int base) {
-                    auto it = std::find(r.begin(), r.end(), rows[t]);
-                    return it == r.end() ? -1 : base + (int)(it - r.begin());
-                };
-                a.c1[t] = chan(L1.pub_rows, 0);
-                a.c2[t] = L2 ? chan(L2->pub_rows, n1) : -1;
-                cnt_[C_PTMUL]++;
-            }
-            m = public_encode(L1, L2, d_nib, hp_.ptscale[l], nl);
-            const int no = L2 ? 2 : 1;
-            for (int k = 0; k < no; ++k) res.push_back(out[k] = alloc_ct(l, 2));
-            launch_lut_public_mac(S(), T_, out[0].data, L2 ? out[1].data : nullptr, a, n, nch, m, nl, qmap());
-            untmp(m, (size_t)nch * nl), m = nullptr;
-            for (int k = 0; k < no; ++k) {
-                out[k].pend = 1;
-                out[k].lazy = true;
-                if (!headroom(l, 1, k ? L2->pub_mag : L1.pub_mag)) {
-                    Ct r = rescale(out[k]);
-                    own.push_back(out[k]);
-                    res[k] = out[k] = r;
-                }
-            }
-        } catch (...) {
-            if (m) untmp(m, (size_t)nch * nl);
-            for (const Ct& x : own) release(x);
-            for (const Ct& x : res) release(x);
-            throw;
-        }
-        for (const Ct& x : own) release(x);
-        cnt_[C_LUT]++;
+            operands_at(used, n, l, a.a, s.own);
+            auto chan = [&](const std::vector<int>& r, int base, int p) {
+                auto it = std::find(r.begin(), r.end(), p);
+                return it == r.end() ? -1 : base + (int)(it - r.begin());
+            };
+            for (int t = 0; t < n; ++t) a.c1[t] = chan(L1.pub_rows, 0, rows[t]), a.c2[t] = L2 ? chan(L2->pub_rows, n1, rows[t]) : -1;
+            s.mrows = (size_t)nch * nl;
+            s.m = public_encode(L1, L2, d_nib, hp_.ptscale[l], nl);
+            for (int k = 0; k < no; ++k) s.res.push_back(out[k] = alloc_ct(l, 2));
+            launch_lut_public_mac(S(), T_, out[0].data, L2 ? out[1].data : nullptr, a, n, nch, s.m, nl, qmap());
+            untmp(s.m, s.mrows), s.m = nullptr;
+            for (int k = 0; k < no; ++k) owe_rescale(out[k], s.res[k], k ? L2->pub_mag : L1.pub_mag, s.own);
+        });
         *o1 = out[0];
         if (o2 && L2) *o2 = out[1];
     }
     // tests: the encoded coefficient rows of one LUT (used rows x nl(level) x N, NTT form) and their scale
     void debug_public_pt(aesfhe_handle h, const uint8_t* nib, int n_slots, int level, u32* out, double* scale) {
         Lut& L = lut(h);
-        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_public_pt: level out of range (1..max level)");
-        if (!out || !scale) throw std::runtime_error("debug_public_pt: missing output buffers");
+        debug_args("debug_public_pt", level, out, scale);
         lut_public_table(L);
         const uint8_t* d_nib = stage_nibbles(nib, n_slots);
         const int nl = hp_.nl(level);
-        const size_t rows = L.pub_rows.size() * (size_t)nl;
-        u32* m = public_encode(L, nullptr, d_nib, hp_.ptscale[level], nl);
-        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
-        if (e == hipSuccess) e = hipStreamSynchronize(S());
-        untmp(m, rows);
-        HIP_OK(e);
-        *scale = hp_.ptscale[level];
+        read_rows(public_encode(L, nullptr, d_nib, hp_.ptscale[level], nl), L.pub_rows.size() * (size_t)nl, level, out, scale);
     }
 
-    // ------------------------------------------------------------------ public XOR fused with the value decode (DESIGN.md §3.20)
+    // ------------------------------------------------------------------ public XOR fused with the value decode (DESIGN.md §3.20, §3.21)
     // The two 9 x 16 tables E_p[b] of a byte's nibbles (hi pre-scaled by 16 gain, lo by gain; made by Python) as
     // one device table [2][9][16] complex double: uploaded once, waiting for its copy once as lut_public_table does.
     aesfhe_handle value_create(const double* re, const double* im) {
@@ -1833,292 +1890,129 @@ public:
         if (!vtabs_.count(h)) throw std::runtime_error("aesfhe_xor_value_free: not a value table handle");
         free_handle(h);
     }
-    // both public nibble arrays checked and copied into this stream's staging buffers, hi then lo (stage_nibbles)
-    const uint8_t* stage_nibbles2(const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots) {
-        const int s = slot_count();
-        if (!nib_hi || !nib_lo || n_slots != s)
-            throw std::runtime_error("xor_value_public: one nibble per slot (n_slots must equal slot_count)");
-        std::vector<uint8_t>& h = h_val_nib_[t_sidx];
-        h.resize((size_t)2 * s);
-        for (int half = 0; half < 2; ++half) {
-            const uint8_t* nib = half ? nib_lo : nib_hi;
-            for (int j = 0; j < s; ++j) {
-                if (nib[j] >= 16) throw std::runtime_error("xor_value_public: nibble out of range (>= 16) at slot " + std::to_string(j));
-                h[(size_t)half * s + j] = nib[j];
-            }
-        }
-        if (!d_val_nib_[t_sidx]) d_val_nib_[t_sidx] = (uint8_t*)dev_alloc(((size_t)2 * s + 3) / 4);
-        HIP_OK(hipMemcpyAsync(d_val_nib_[t_sidx], h.data(), (size_t)2 * s, hipMemcpyHostToDevice, S()));
-        return d_val_nib_[t_sidx];
-    }
-    // the 16 per-slot coefficient plaintexts, channel t = half * 8 + (p - 1) holding E_p of nibble array `half`
-    // (p = 1..8), encoded at `scale` on nl limbs by the codec public_encode uses.  Returns 16 x nl rows (tmp)
-    u32* value_encode(const ValueTab& V, const uint8_t* d_nib, double scale, int nl) {
-        ValueSlotArgs ch;
-        for (int t = 0; t < kValueCh; ++t) ch.half[t] = t / 8, ch.row[t] = (t / 8) * kValueRows + (t % 8) + 1;
-        u32* wb = tmp((size_t)4 * kValueCh);  // [16][N] complex double: 4 rows per channel
-        u32* m = nullptr;
-        try {
-            m = tmp((size_t)kValueCh * nl);
-            launch_value_slots(S(), T_, (double*)wb, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, d_nib, d_slot_pos_);
-            launch_fft2(S(), T_, (double*)wb, -1, kValueCh);
-            launch_encode_untwist(S(), T_, m, (const double*)wb, scale, nl, kValueCh);
-            ntt(m, kValueCh * nl, nl, qmap());
-        } catch (...) {
-            untmp(wb, (size_t)4 * kValueCh);
-            if (m) untmp(m, (size_t)kValueCh * nl);
-            throw;
-        }
-        untmp(wb, (size_t)4 * kValueCh);
-        return m;
-    }
-    // T = sum_{p = 1..7} E_p[nib_hi] (.) hi^p + E_p[nib_lo] (.) lo^p and R = E_8[nib_hi] (.) hi^8 + E_8[nib_lo] (.) lo^8:
-    // A_hi / A_lo are indexed by the power p (entry 0 unused), the operands canonical and dropped exactly to their
-    // common lowest logical level l as lut_eval_public's, ONE k_value_public_mac launch for both sums; each output
-    // owes its rescale (applied here when the raw scale has no headroom)
-    void xor_value_public(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi,
-                          const uint8_t* nib_lo, int n_slots, Ct* oT, Ct* oR) {
-        const ValueTab& V = vtab(hv);
-        if (!A_hi || !A_lo) throw std::runtime_error("xor_value_public: missing element handles");
-        aesfhe_handle A[kValueCh];
-        int l = 1 << 30;
-        for (int t = 0; t < kValueCh; ++t) {
-            A[t] = (t / 8 ? A_lo : A_hi)[(t % 8) + 1];
-            if (!A[t]) throw std::runtime_error("xor_value_public: missing element handle of a used row");
-            const Ct& c = ct(A[t]);
-            if (c.nb != 1) throw std::runtime_error("xor_value_public: stacked operands are not supported (single ciphertexts only)");
-            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("xor_value_public: nonzero 2-polynomial ciphertexts");
-            l = std::min(l, c.level - c.pend);
-        }
-        if (l < 1) throw std::runtime_error("not enough level for the public value decode (level 0)");
-        const uint8_t* d_nib = stage_nibbles2(nib_hi, nib_lo, n_slots);
-        const int nl = hp_.nl(l);
-        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
-        u32* m = nullptr;
-        Ct out[2];
-        try {
-            ValueMacArgs a;
-            for (int t = 0; t < kValueCh; ++t) {
-                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
-                const Ct& c = ct(A[t]);
-                Ct x = c;
-                if (pm(c) != 2 || c.pend || !c.ntt) {
-                    x = normalize(c, true);
-                    if (x.data != c.data) own.push_back(x);
-                }
-                if (x.level != l) {
-                    const u32* before = x.data;
-                    x = level_down(x, l);
-                    if (x.data != before && x.data != c.data) own.push_back(x);
-                }
-                a.a[t] = x.data;
-                a.real[t] = (t % 8) == 7;  // the a^8 terms: R
-                cnt_[C_PTMUL]++;
-            }
-            m = value_encode(V, d_nib, hp_.ptscale[l], nl);
-            for (int k = 0; k < 2; ++k) res.push_back(out[k] = alloc_ct(l, 2));
-            launch_value_public_mac(S(), T_, out[0].data, out[1].data, a, kValueCh, m, nl, qmap());
-            untmp(m, (size_t)kValueCh * nl), m = nullptr;
-            for (int k = 0; k < 2; ++k) {
-                out[k].pend = 1;
-                out[k].lazy = true;
-                if (!headroom(l, 1, k ? V.mag_r : V.mag_t)) {
-                    Ct r = rescale(out[k]);
-                    own.push_back(out[k]);
-                    res[k] = out[k] = r;
-                }
-            }
-        } catch (...) {
-            if (m) untmp(m, (size_t)kValueCh * nl);
-            for (const Ct& x : own) release(x);
-            for (const Ct& x : res) release(x);
-            throw;
-        }
-        for (const Ct& x : own) release(x);
-        cnt_[C_LUT]++;
-        *oT = out[0];
-        *oR = out[1];
-    }
-    // tests: the 16 encoded channel rows (16 x nl(level) x N, NTT form, value_encode's order) and their scale
-    void debug_value_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level, u32* out, double* scale) {
-        const ValueTab& V = vtab(hv);
-        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_xor_value_pt: level out of range (1..max level)");
-        if (!out || !scale) throw std::runtime_error("debug_xor_value_pt: missing output buffers");
-        const uint8_t* d_nib = stage_nibbles2(nib_hi, nib_lo, n_slots);
-        const int nl = hp_.nl(level);
-        const size_t rows = (size_t)kValueCh * nl;
-        u32* m = value_encode(V, d_nib, hp_.ptscale[level], nl);
-        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
-        if (e == hipSuccess) e = hipStreamSynchronize(S());
-        untmp(m, rows);
-        HIP_OK(e);
-        *scale = hp_.ptscale[level];
-    }
-
-    // ------------------------------------------------------------------ typed value decode
-    // The value decode is linear in its table, so a real weight per slot scales the decoded value per slot, and a
-    // signed hi nibble (sval(x) = x - 16 [x >= 8]) only negates the hi table's odd rows: both fold into the per-slot
-    // coefficients k_value_slots_typed writes.  G = 1 or 2 weight groups share the ciphertext operands; group g's
-    // weights select byte g of a 16-bit word, and the caller adds group 1 rotated onto group 0.
-    struct TypedStage {
+    // ONE path for the plain and the typed decode.  The decode is linear in its table, so a real weight per slot
+    // scales the decoded value per slot, and a signed hi nibble (sval(x) = x - 16 [x >= 8]) only negates the hi
+    // table's odd rows: both fold into the per-slot coefficients k_value_slots_typed writes.  G = 1 or 2 weight
+    // groups share the ciphertext operands; group g's weights select byte g of a 16-bit word, and the caller adds
+    // group 1 rotated onto group 0.  Null weights mean weight 1 on every slot, as null flags mean no slot signed:
+    // xor_value_public is G = 1 with both null (a product by 1.0 is exact, so its rows are the table's own values)
+    struct ValueStage {
         const uint8_t* nib = nullptr;    // both nibble arrays, hi then lo
-        const double* wt = nullptr;      // [G][slots]
+        const double* wt = nullptr;      // [G][slots], null: weight 1
         const uint8_t* flags = nullptr;  // [G][slots], null: no slot signed
         double top[kValueGroups] = {};   // max |w| per group
     };
     // nibbles, weights and flags checked and copied into this stream's staging buffer in ONE copy:
-    // [G][s] doubles, then 2 s nibble bytes, then (flags given) G s flag bytes
-    TypedStage stage_typed(const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights, const uint8_t* flags) {
+    // (weights given) [G][s] doubles, then 2 s nibble bytes, then (flags given) G s flag bytes
+    ValueStage stage_value(const std::string& who, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights,
+                           const uint8_t* flags) {
         const int s = slot_count();
-        if (!nib_hi || !nib_lo || n_slots != s)
-            throw std::runtime_error("xor_value_typed: one nibble per slot (n_slots must equal slot_count)");
-        const size_t nw = (size_t)G * s, o_nib = nw * sizeof(double), o_flag = o_nib + (size_t)2 * s;
+        need_slots(who, nib_hi && nib_lo && n_slots == s);
+        const size_t nw = (size_t)G * s, o_nib = weights ? nw * sizeof(double) : 0, o_flag = o_nib + (size_t)2 * s;
         const size_t bytes = o_flag + (flags ? nw : 0);
-        std::vector<uint8_t>& h = h_val_typed_[t_sidx];
+        std::vector<uint8_t>& h = h_val_[t_sidx];
         h.resize(bytes);
-        TypedStage st;
-        for (int g = 0; g < G; ++g)
-            for (int j = 0; j < s; ++j) {
+        ValueStage st;
+        for (int g = 0; g < G; ++g) {
+            st.top[g] = weights ? 0.0 : 1.0;
+            for (int j = 0; weights && j < s; ++j) {
                 const double w = weights[(size_t)g * s + j];
-                if (!std::isfinite(w))
-                    throw std::runtime_error("xor_value_typed: weight not finite at group " + std::to_string(g) + ", slot " + std::to_string(j));
+                if (!std::isfinite(w)) throw std::runtime_error(who + ": weight not finite at group " + std::to_string(g) + ", slot " + std::to_string(j));
                 st.top[g] = std::max(st.top[g], std::fabs(w));
             }
-        std::memcpy(h.data(), weights, o_nib);
-        for (int half = 0; half < 2; ++half) {
-            const uint8_t* nib = half ? nib_lo : nib_hi;
-            for (int j = 0; j < s; ++j) {
-                if (nib[j] >= 16) throw std::runtime_error("xor_value_typed: nibble out of range (>= 16) at slot " + std::to_string(j));
-                h[o_nib + (size_t)half * s + j] = nib[j];
-            }
         }
+        if (weights) std::memcpy(h.data(), weights, o_nib);
+        copy_nibbles(who, nib_hi, h.data() + o_nib);
+        copy_nibbles(who, nib_lo, h.data() + o_nib + s);
         if (flags) std::memcpy(h.data() + o_flag, flags, nw);
-        // sized for kValueGroups groups with flags: 8 G s + 2 s + G s bytes
-        if (!d_val_typed_[t_sidx]) d_val_typed_[t_sidx] = (uint8_t*)dev_alloc(((size_t)(9 * kValueGroups + 2) * s + 3) / 4);
-        uint8_t* d = d_val_typed_[t_sidx];
+        // sized for kValueGroups groups with weights and flags: 8 G s + 2 s + G s bytes
+        if (!d_val_[t_sidx]) d_val_[t_sidx] = (uint8_t*)dev_alloc(((size_t)(9 * kValueGroups + 2) * s + 3) / 4);
+        uint8_t* d = d_val_[t_sidx];
         HIP_OK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, S()));
-        st.wt = (const double*)d;
+        st.wt = weights ? (const double*)d : nullptr;
         st.nib = d + o_nib;
         st.flags = flags ? d + o_flag : nullptr;
         return st;
     }
-    // value_encode per weight group: G x 16 channels (group g's 16 follow group g - 1's), one codec pass per group
-    // through the same 16-channel FFT scratch.  Returns G x 16 x nl rows (tmp)
-    u32* value_encode_typed(const ValueTab& V, const TypedStage& st, int G, double scale, int nl) {
-        ValueTypedSlotArgs ch;
+    // the G x 16 per-slot coefficient plaintexts: channel t = half * 8 + (p - 1) of group g holds E_p of nibble array
+    // `half` (p = 1..8) times group g's weights, one codec pass per group (encode_channels).  G x 16 x nl rows (tmp)
+    u32* value_encode(const ValueTab& V, const ValueStage& st, int G, double scale, int nl) {
+        ValueSlotArgs ch;
         for (int t = 0; t < kValueCh; ++t) {
             const int half = t / 8, p = (t % 8) + 1;
-            ch.ch.half[t] = half, ch.ch.row[t] = half * kValueRows + p;
+            ch.half[t] = half, ch.row[t] = half * kValueRows + p;
             ch.flip[t] = half == 0 && (p & 1);  // the signed nibble negates the hi table's odd rows
         }
         const int s = slot_count();
-        const size_t grp = (size_t)kValueCh * nl;
-        u32* wb = tmp((size_t)4 * kValueCh);  // [16][N] complex double: 4 rows per channel
-        u32* m = nullptr;
-        try {
-            m = tmp((size_t)G * grp);
-            for (int g = 0; g < G; ++g) {
-                u32* mg = m + (size_t)g * grp * hp_.n;
-                launch_value_slots_typed(S(), T_, (double*)wb, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, st.nib,
-                                         st.wt + (size_t)g * s, st.flags ? st.flags + (size_t)g * s : nullptr, d_slot_pos_);
-                launch_fft2(S(), T_, (double*)wb, -1, kValueCh);
-                launch_encode_untwist(S(), T_, mg, (const double*)wb, scale, nl, kValueCh);
-                ntt(mg, kValueCh * nl, nl, qmap());
-            }
-        } catch (...) {
-            untmp(wb, (size_t)4 * kValueCh);
-            if (m) untmp(m, (size_t)G * grp);
-            throw;
-        }
-        untmp(wb, (size_t)4 * kValueCh);
-        return m;
+        return encode_channels(G, kValueCh, scale, nl, [&](int g, double* w) {
+            launch_value_slots_typed(S(), T_, w, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, st.nib,
+                                     st.wt ? st.wt + (size_t)g * s : nullptr, st.flags ? st.flags + (size_t)g * s : nullptr, d_slot_pos_);
+        });
     }
-    // xor_value_public with per-slot weights and flags for G groups: oT[g], oR[g] are group g's T and R (the same
-    // operands, normalisation, level drop and owed rescale), all formed by ONE k_value_typed_mac launch
-    void xor_value_typed(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi, const uint8_t* nib_lo,
-                         int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT, Ct* oR) {
+    // per group g: oT[g] = sum_{p = 1..7} w_g E_p[nib_hi] (.) hi^p + w_g E_p[nib_lo] (.) lo^p and oR[g] = the two E_8 terms.
+    // A_hi / A_lo are indexed by the power p (entry 0 unused), the operands canonical and dropped exactly to their
+    // common lowest logical level l as lut_eval_public's, ONE k_value_typed_mac launch for all 2 G sums; each output
+    // owes its rescale (applied here when the raw scale has no headroom)
+    void value_decode(const std::string& who, const char* what, aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo,
+                      const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT,
+                      Ct* oR) {
         const ValueTab& V = vtab(hv);
-        if (G < 1 || G > kValueGroups) throw std::runtime_error("xor_value_typed: n_groups must be 1 or 2");
-        if (!weights) throw std::runtime_error("xor_value_typed: missing weights");
-        if (!A_hi || !A_lo) throw std::runtime_error("xor_value_typed: missing element handles");
+        if (!A_hi || !A_lo) throw std::runtime_error(who + ": missing element handles");
         aesfhe_handle A[kValueCh];
-        int l = 1 << 30;
-        for (int t = 0; t < kValueCh; ++t) {
-            A[t] = (t / 8 ? A_lo : A_hi)[(t % 8) + 1];
-            if (!A[t]) throw std::runtime_error("xor_value_typed: missing element handle of a used row");
-            const Ct& c = ct(A[t]);
-            if (c.nb != 1) throw std::runtime_error("xor_value_typed: stacked operands are not supported (single ciphertexts only)");
-            if (vis_npoly(c) != 2 || c.zero) throw std::runtime_error("xor_value_typed: nonzero 2-polynomial ciphertexts");
-            l = std::min(l, c.level - c.pend);
-        }
-        if (l < 1) throw std::runtime_error("not enough level for the typed value decode (level 0)");
-        const TypedStage st = stage_typed(nib_hi, nib_lo, n_slots, G, weights, flags);
+        for (int t = 0; t < kValueCh; ++t) A[t] = (t / 8 ? A_lo : A_hi)[(t % 8) + 1];
+        const int l = public_operands(who, what, A, kValueCh);
+        const ValueStage st = stage_value(who, nib_hi, nib_lo, n_slots, G, weights, flags);
         const int nl = hp_.nl(l);
-        const size_t mrows = (size_t)G * kValueCh * nl;
-        std::vector<Ct> own, res;  // every temporary (and, on the error path, every result) is released
-        u32* m = nullptr;
         Ct out[2 * kValueGroups];  // T_0, R_0, T_1, R_1
-        try {
+        public_op([&](PubTemps& s) {
             ValueMacArgs a;
-            for (int t = 0; t < kValueCh; ++t) {
-                // canonical (NTT, two polynomials, nothing owed), then the exact drop to l
-                const Ct& c = ct(A[t]);
-                Ct x = c;
-                if (pm(c) != 2 || c.pend || !c.ntt) {
-                    x = normalize(c, true);
-                    if (x.data != c.data) own.push_back(x);
-                }
-                if (x.level != l) {
-                    const u32* before = x.data;
-                    x = level_down(x, l);
-                    if (x.data != before && x.data != c.data) own.push_back(x);
-                }
-                a.a[t] = x.data;
-                a.real[t] = (t % 8) == 7;  // the a^8 terms: R
-                cnt_[C_PTMUL] += G;
-            }
-            m = value_encode_typed(V, st, G, hp_.ptscale[l], nl);
+            operands_at(A, kValueCh, l, a.a, s.own);
+            for (int t = 0; t < kValueCh; ++t) a.real[t] = (t % 8) == 7;  // the a^8 terms: R
+            cnt_[C_PTMUL] += (G - 1) * kValueCh;                          // every group multiplies every operand
+            s.mrows = (size_t)G * kValueCh * nl;
+            s.m = value_encode(V, st, G, hp_.ptscale[l], nl);
             ValueTypedOut o;
-            for (int k = 0; k < 2 * G; ++k) res.push_back(out[k] = alloc_ct(l, 2));
+            for (int k = 0; k < 2 * G; ++k) s.res.push_back(out[k] = alloc_ct(l, 2));
             for (int g = 0; g < G; ++g) o.t[g] = out[2 * g].data, o.r[g] = out[2 * g + 1].data;
-            launch_value_typed_mac(S(), T_, o, G, a, kValueCh, m, nl, qmap());
-            untmp(m, mrows), m = nullptr;
-            for (int k = 0; k < 2 * G; ++k) {
-                out[k].pend = 1;
-                out[k].lazy = true;
-                if (!headroom(l, 1, (k & 1 ? V.mag_r : V.mag_t) * st.top[k / 2])) {
-                    Ct r = rescale(out[k]);
-                    own.push_back(out[k]);
-                    res[k] = out[k] = r;
-                }
-            }
-        } catch (...) {
-            if (m) untmp(m, mrows);
-            for (const Ct& x : own) release(x);
-            for (const Ct& x : res) release(x);
-            throw;
-        }
-        for (const Ct& x : own) release(x);
-        cnt_[C_LUT]++;
+            launch_value_typed_mac(S(), T_, o, G, a, kValueCh, s.m, nl, qmap());
+            untmp(s.m, s.mrows), s.m = nullptr;
+            for (int k = 0; k < 2 * G; ++k) owe_rescale(out[k], s.res[k], (k & 1 ? V.mag_r : V.mag_t) * st.top[k / 2], s.own);
+        });
         for (int g = 0; g < G; ++g) oT[g] = out[2 * g], oR[g] = out[2 * g + 1];
     }
-    // tests: the G x 16 encoded channel rows (value_encode_typed's order) and their scale
+    // tests: the G x 16 encoded channel rows (value_encode's order) and their scale; `op`: the decode whose staging
+    // refusals these are
+    void debug_value_rows(const std::string& who, const std::string& op, aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                          int n_slots, int G, const double* weights, const uint8_t* flags, int level, u32* out, double* scale) {
+        const ValueTab& V = vtab(hv);
+        debug_args(who, level, out, scale);
+        const ValueStage st = stage_value(op, nib_hi, nib_lo, n_slots, G, weights, flags);
+        const int nl = hp_.nl(level);
+        read_rows(value_encode(V, st, G, hp_.ptscale[level], nl), (size_t)G * kValueCh * nl, level, out, scale);
+    }
+    // the entry points: the plain decode is one group with unit weights and no flags; only the typed one takes (and
+    // then requires) weights
+    void typed_args(const std::string& who, aesfhe_handle hv, int G, const double* weights) const {
+        vtab(hv);
+        if (G < 1 || G > kValueGroups) throw std::runtime_error(who + ": n_groups must be 1 or 2");
+        if (!weights) throw std::runtime_error(who + ": missing weights");
+    }
+    void xor_value_public(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi,
+                          const uint8_t* nib_lo, int n_slots, Ct* oT, Ct* oR) {
+        value_decode("xor_value_public", "public value decode", hv, A_hi, A_lo, nib_hi, nib_lo, n_slots, 1, nullptr, nullptr, oT, oR);
+    }
+    void debug_value_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int level, u32* out, double* scale) {
+        debug_value_rows("debug_xor_value_pt", "xor_value_public", hv, nib_hi, nib_lo, n_slots, 1, nullptr, nullptr, level, out, scale);
+    }
+    void xor_value_typed(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                         int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT, Ct* oR) {
+        typed_args("xor_value_typed", hv, G, weights);
+        value_decode("xor_value_typed", "typed value decode", hv, A_hi, A_lo, nib_hi, nib_lo, n_slots, G, weights, flags, oT, oR);
+    }
     void debug_value_typed_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights,
                               const uint8_t* flags, int level, u32* out, double* scale) {
-        const ValueTab& V = vtab(hv);
-        if (G < 1 || G > kValueGroups) throw std::runtime_error("debug_xor_value_typed_pt: n_groups must be 1 or 2");
-        if (!weights) throw std::runtime_error("debug_xor_value_typed_pt: missing weights");
-        if (level < 1 || level > hp_.L) throw std::runtime_error("debug_xor_value_typed_pt: level out of range (1..max level)");
-        if (!out || !scale) throw std::runtime_error("debug_xor_value_typed_pt: missing output buffers");
-        const TypedStage st = stage_typed(nib_hi, nib_lo, n_slots, G, weights, flags);
-        const int nl = hp_.nl(level);
-        const size_t rows = (size_t)G * kValueCh * nl;
-        u32* m = value_encode_typed(V, st, G, hp_.ptscale[level], nl);
-        hipError_t e = hipMemcpyAsync(out, m, rows * hp_.n * sizeof(u32), hipMemcpyDeviceToHost, S());
-        if (e == hipSuccess) e = hipStreamSynchronize(S());
-        untmp(m, rows);
-        HIP_OK(e);
-        *scale = hp_.ptscale[level];
+        typed_args("debug_xor_value_typed_pt", hv, G, weights);
+        debug_value_rows("debug_xor_value_typed_pt", "xor_value_typed", hv, nib_hi, nib_lo, n_slots, G, weights, flags, level, out, scale);
     }
 
     // ------------------------------------------------------------------ key switching
@@ -5884,10 +5778,8 @@ private:
     int* d_nib_[kStreams] = {};
     uint8_t* d_pub_nib_[kStreams] = {};        // lut_eval_public: the public nibbles, one byte per slot
     std::vector<uint8_t> h_pub_nib_[kStreams];  // their host staging copy
-    uint8_t* d_val_nib_[kStreams] = {};        // xor_value_public: both public nibble arrays, hi then lo
-    std::vector<uint8_t> h_val_nib_[kStreams];  // their host staging copy
-    uint8_t* d_val_typed_[kStreams] = {};        // xor_value_typed: weights, both nibble arrays, flags (stage_typed)
-    std::vector<uint8_t> h_val_typed_[kStreams];  // their host staging copy
+    uint8_t* d_val_[kStreams] = {};        // the value decode: weights, both nibble arrays, flags (stage_value)
+    std::vector<uint8_t> h_val_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;

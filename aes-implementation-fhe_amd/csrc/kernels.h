@@ -610,43 +610,32 @@ struct PubMacArgs {
 void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* out2, const PubMacArgs& a, int n, int nch, const u32* pt,
                            int nl, LimbMap map);
 
-// --- public XOR fused with the value decode ----------------------------
+// --- public XOR fused with the value decode, plain and typed -----------
 // val(a ^ b) of a Zeta16 nibble a with b public is sum_p E_p[b] a^p: per-slot plaintext coefficients again, now
-// over the powers of BOTH nibbles of a byte and two public nibble arrays.  launch_value_slots is
-// launch_public_slots with a channel map: channel c takes row row[c] of one table (rows of 16 complex doubles)
-// at the nibble nib[half[c] * N/2 + j] of slot j, in the same output order.
+// over the powers of BOTH nibbles of a byte and two public nibble arrays.  launch_value_slots_typed is
+// launch_public_slots with a channel map, a real weight wt[j] per slot and, where flags[j] & 1, the signed-nibble
+// table on the channels marked flip[c] (the odd rows of the hi half: sval(x) = x - 16 [x >= 8] negates exactly
+// those rows): channel c takes row row[c] of one table (rows of 16 complex doubles) at the nibble
+// nib[half[c] * N/2 + j] of slot j,  w[c][slot j] = (flags[j] & 1 && flip[c] ? -1 : 1) * wt[j] * tab[row[c]][nib],
+// in the same output order.  wt may be null (weight 1: the table's own values, bit for bit), flags may be null
+// (no slot signed): the plain decode passes neither.
 constexpr int kValueCh = 16;  // 2 x 8 powers: the FFT scratch's channel limit
 struct ValueSlotArgs {
     int row[kValueCh] = {};
     int half[kValueCh] = {};  // 0: the first nibble array (hi), 1: the second (lo)
+    int flip[kValueCh] = {};
 };
-void launch_value_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
-                        const uint8_t* nib, const u32* slot_pos);
-// outT = sum_{t: !real[t]} a[t] (.) pt[t], outR = sum_{t: real[t]} a[t] (.) pt[t] (2 polys of nl limbs each; pt:
-// channel t of nl limbs, NTT form) in ONE launch over n <= kValueCh ciphertexts, every word read once; neither
-// sum may take more than 15 terms (64-bit sums of 60-bit products)
+void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
+                              const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos);
+// outT[g] = sum_{t: !real[t]} a[t] (.) pt_g[t], outR[g] = sum_{t: real[t]} a[t] (.) pt_g[t] (2 polys of nl limbs each)
+// for G = 1 or 2 weight groups in ONE launch over n <= kValueCh ciphertexts, pt_g[t] = channel g * kValueCh + t of
+// nl limbs, NTT form; every ciphertext word is read once and used for all groups (n ciphertext and n G plaintext
+// words per element, 2 G 64-bit sums); no sum may take more than 15 terms (64-bit sums of 60-bit products)
+constexpr int kValueGroups = 2;
 struct ValueMacArgs {
     const u32* a[kValueCh] = {};
     int real[kValueCh] = {};
 };
-void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32* outR, const ValueMacArgs& a, int n, const u32* pt, int nl,
-                             LimbMap map);
-
-// --- typed value decode: per-slot weights and a signed hi nibble ----------------
-// launch_value_slots with a real weight wt[j] per slot and, where flags[j] & 1, the signed-nibble table on the
-// channels marked flip[c] (the odd rows of the hi half: sval(x) = x - 16 [x >= 8] negates exactly those rows):
-// w[c][slot j] = (flags[j] & 1 && flip[c] ? -1 : 1) * wt[j] * tab[row[c]][nib].  flags may be null (no slot signed).
-struct ValueTypedSlotArgs {
-    ValueSlotArgs ch;
-    int flip[kValueCh] = {};
-};
-void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueTypedSlotArgs& ch,
-                              int nch, const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos);
-// launch_value_public_mac for G = 1 or 2 weight groups in ONE launch: outT[g] / outR[g] = the two sums over the
-// same n ciphertexts against group g's channels pt[(g * kValueCh + t) * nl ...]; every ciphertext word is read once
-// and used for all groups (n ciphertext and n G plaintext words per element, 2 G 64-bit sums); the 15-term limit
-// per sum is launch_value_public_mac's
-constexpr int kValueGroups = 2;
 struct ValueTypedOut {
     u32* t[kValueGroups] = {};
     u32* r[kValueGroups] = {};

@@ -135,26 +135,12 @@ __global__ void k_lut_public_mac(u32* out1, u32* out2, PubMacArgs a, int n, cons
     out1[idx] = reduce64(acc1, P.q, P.mu, P.r32);
     if (out2) out2[idx] = reduce64(acc2, P.q, P.mu, P.r32);
 }
-// outT = sum_{t: !real_t} a_t (.) pt[t], outR = sum_{t: real_t} a_t (.) pt[t] over n <= kValueCh ciphertexts, channel t of
-// one encoded plaintext buffer per ciphertext (the value decode's T and R, launch_value_public_mac): every ciphertext
-// and plaintext word read once.  64-bit sums with one reduction each: the residues are below 2^30, so the 14 products
-// of T (15 at most, the launcher checks) stay below 15 x 2^60 < 2^64
-__global__ void k_value_public_mac(u32* outT, u32* outR, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc,
-                                   int logn) {
-    EW_PROLOGUE
-    const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
-    u64 accT = 0, accR = 0;
-    for (int t = 0; t < n; ++t) {
-        const u64 prod = (u64)a.a[t][idx] * pt[(size_t)t * chan + pidx];
-        if (a.real[t]) accR += prod;
-        else accT += prod;
-    }
-    outT[idx] = reduce64(accT, P.q, P.mu, P.r32);
-    outR[idx] = reduce64(accR, P.q, P.mu, P.r32);
-}
-// k_value_public_mac for G weight groups (launch_value_typed_mac): group g's plaintext channels follow group g - 1's
-// (kValueCh channels each).  Each ciphertext word is loaded once and multiplied into all G groups; G is a template
-// argument, so the group loop unrolls and the 2 G sums stay in registers.  The 2^64 bound is per sum, as above
+// o.t[g] = sum_{t: !real_t} a_t (.) pt[g kValueCh + t], o.r[g] = sum_{t: real_t} a_t (.) pt[g kValueCh + t] over n <= kValueCh
+// ciphertexts and G weight groups (the value decode's T and R, launch_value_typed_mac): group g's plaintext channels
+// follow group g - 1's (kValueCh channels each).  Each ciphertext word is loaded once and multiplied into all G
+// groups; G is a template argument, so the group loop unrolls and the 2 G sums stay in registers.  64-bit sums with
+// one reduction each: the residues are below 2^30, so the 14 products of T (15 at most, the launcher checks) stay
+// below 15 x 2^60 < 2^64
 template <int G>
 __global__ void k_value_typed_mac(ValueTypedOut o, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     EW_PROLOGUE
@@ -1390,32 +1376,21 @@ __global__ void __launch_bounds__(kBlock) k_public_slots(double2* w, const doubl
     wc[t] = v;
     wc[n - 1 - t] = make_double2(v.x, -v.y);
 }
-// k_public_slots with a channel map (launch_value_slots): channel c takes row ch.row[c] of ONE table at the slot's
-// nibble in nibble array ch.half[c] (two arrays of N/2 bytes, back to back).  The map is a kernel argument: uniform
-// per block, read by the scalar unit
-__global__ void __launch_bounds__(kBlock) k_value_slots(double2* w, const double2* tab, ValueSlotArgs ch, const uint8_t* nib,
-                                                        const u32* slot_pos, int logn) {
-    const int c = blockIdx.y;
-    const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
-    const int n = 1 << logn;
-    if (j >= n / 2) return;
-    const double2 v = tab[16 * ch.row[c] + (nib[(size_t)ch.half[c] * (n / 2) + j] & 15)];
-    const u32 t = slot_pos[j];
-    double2* wc = w + ((size_t)c << logn);
-    wc[t] = v;
-    wc[n - 1 - t] = make_double2(v.x, -v.y);
-}
-// k_value_slots with a per-slot real weight and the signed-nibble sign (launch_value_slots_typed): one lane per slot,
-// weight, flag and nibble read coalesced; the sign is a select, not a branch
-__global__ void __launch_bounds__(kBlock) k_value_slots_typed(double2* w, const double2* tab, ValueTypedSlotArgs a, const uint8_t* nib,
+// k_public_slots with a channel map, a per-slot real weight and the signed-nibble sign (launch_value_slots_typed):
+// channel c takes row a.row[c] of ONE table at the slot's nibble in nibble array a.half[c] (two arrays of N/2 bytes,
+// back to back).  The map is a kernel argument: uniform per block, read by the scalar unit.  One lane per slot,
+// weight, flag and nibble read coalesced; the sign is a select, not a branch.  wt null: weight 1 (the product by
+// 1.0 is exact: the table's own values), flags null: no slot signed -- both uniform over the launch
+__global__ void __launch_bounds__(kBlock) k_value_slots_typed(double2* w, const double2* tab, ValueSlotArgs a, const uint8_t* nib,
                                                               const double* wt, const uint8_t* flags, const u32* slot_pos, int logn) {
     const int c = blockIdx.y;
     const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
     const int n = 1 << logn;
     if (j >= n / 2) return;
-    const double2 e = tab[16 * a.ch.row[c] + (nib[(size_t)a.ch.half[c] * (n / 2) + j] & 15)];
+    const double2 e = tab[16 * a.row[c] + (nib[(size_t)a.half[c] * (n / 2) + j] & 15)];
     const bool neg = a.flip[c] && flags && (flags[j] & 1);
-    const double s = neg ? -wt[j] : wt[j];
+    const double wj = wt ? wt[j] : 1.0;
+    const double s = neg ? -wj : wj;
     const double2 v = make_double2(e.x * s, e.y * s);
     const u32 t = slot_pos[j];
     double2* wc = w + ((size_t)c << logn);
@@ -2319,41 +2294,17 @@ void launch_lut_public_mac(hipStream_t st, const DevTables& T, u32* out1, u32* o
     prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + (out2 ? 2 : 1)) + (double)nch * nl), k_lut_public_mac, ew_grid(T.logn, 2 * nl),
                 dim3(kBlock), 0, st, out1, out2, a, n, pt, nl, map, T.pc, T.logn);
 }
-void launch_value_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
-                        const uint8_t* nib, const u32* slot_pos) {
-    if (nch < 1 || nch > kValueCh || !tab || !nib) throw std::runtime_error("launch_value_slots: 1..16 channels");
+void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueSlotArgs& ch, int nch,
+                              const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos) {
+    if (nch < 1 || nch > kValueCh || !tab || !nib) throw std::runtime_error("launch_value_slots_typed: 1..16 channels");
     for (int c = 0; c < nch; ++c)
         if (ch.row[c] < 0 || ch.row[c] >= tab_rows || (ch.half[c] != 0 && ch.half[c] != 1))
-            throw std::runtime_error("launch_value_slots: bad channel map");
-    const double s = (double)(1u << (T.logn - 1));
-    const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
-    prof_launch(KID_ELEMENTWISE, nch * (1.0 * s + 4.0 * s + 32.0 * s), k_value_slots, dim3(gx, nch), dim3(kBlock), 0, st, (double2*)w,
-                (const double2*)tab, ch, nib, slot_pos, T.logn);
-}
-void launch_value_public_mac(hipStream_t st, const DevTables& T, u32* outT, u32* outR, const ValueMacArgs& a, int n, const u32* pt, int nl,
-                             LimbMap map) {
-    if (n < 1 || n > kValueCh || !outT || !outR || !pt) throw std::runtime_error("launch_value_public_mac: 1..16 ciphertexts");
-    int nr = 0;
-    for (int t = 0; t < n; ++t) {
-        if (!a.a[t]) throw std::runtime_error("launch_value_public_mac: bad operand");
-        nr += a.real[t] != 0;
-    }
-    if (nr > 15 || n - nr > 15) throw std::runtime_error("launch_value_public_mac: at most 15 terms per sum");
-    // reads: n ciphertexts and n plaintext channels; writes: two ciphertexts
-    prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * nl * (n + 2) + (double)n * nl), k_value_public_mac, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st,
-                outT, outR, a, n, pt, nl, map, T.pc, T.logn);
-}
-void launch_value_slots_typed(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ValueTypedSlotArgs& ch,
-                              int nch, const uint8_t* nib, const double* wt, const uint8_t* flags, const u32* slot_pos) {
-    if (nch < 1 || nch > kValueCh || !tab || !nib || !wt) throw std::runtime_error("launch_value_slots_typed: 1..16 channels, weights");
-    for (int c = 0; c < nch; ++c)
-        if (ch.ch.row[c] < 0 || ch.ch.row[c] >= tab_rows || (ch.ch.half[c] != 0 && ch.ch.half[c] != 1))
             throw std::runtime_error("launch_value_slots_typed: bad channel map");
     const double s = (double)(1u << (T.logn - 1));
     const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
-    // reads: nibble, flag, weight, slot position; writes: two complex doubles
-    prof_launch(KID_ELEMENTWISE, nch * (2.0 * s + 8.0 * s + 4.0 * s + 32.0 * s), k_value_slots_typed, dim3(gx, nch), dim3(kBlock), 0, st,
-                (double2*)w, (const double2*)tab, ch, nib, wt, flags, slot_pos, T.logn);
+    // reads: nibble, slot position and, where given, flag and weight; writes: two complex doubles
+    prof_launch(KID_ELEMENTWISE, nch * ((flags ? 2.0 : 1.0) * s + (wt ? 8.0 : 0.0) * s + 4.0 * s + 32.0 * s), k_value_slots_typed, dim3(gx, nch),
+                dim3(kBlock), 0, st, (double2*)w, (const double2*)tab, ch, nib, wt, flags, slot_pos, T.logn);
 }
 void launch_value_typed_mac(hipStream_t st, const DevTables& T, const ValueTypedOut& out, int groups, const ValueMacArgs& a, int n,
                             const u32* pt, int nl, LimbMap map) {

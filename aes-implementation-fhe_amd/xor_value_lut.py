@@ -61,22 +61,26 @@ class XorValueLUT:
             return joint_bases(ctx, [(hi, POWERS, "pow"), (lo, POWERS, "pow")])
         return powers(ctx, hi, POWERS), powers(ctx, lo, POWERS)
 
-    def _engine(self, A_hi: Dict[int, Any], A_lo: Dict[int, Any], nib_hi, nib_lo):
-        """(T, R) from ONE engine call (Engine.xor_value_public); None: the context has no such op, or the powers
-        sit too low for it (level)"""
-        ctx = self.ctx
-        ev = getattr(ctx, "xor_value_public", None)
-        if ev is None or not getattr(ctx, "fused_luts", False):
+    def _fused(self, op: str, *args):
+        """the result of ONE engine call ctx.<op>(*args); None: the context has no such op, or the powers sit too
+        low for it (level)"""
+        ev = getattr(self.ctx, op, None)
+        if ev is None or not getattr(self.ctx, "fused_luts", False):
             return None
         try:
-            return ev(A_hi, A_lo, nib_hi, nib_lo, self.tab_hi, self.tab_lo)
+            return ev(*args)
         except RuntimeError as e:
             if "level" in str(e):
                 return None
             raise
 
+    def _engine(self, A_hi: Dict[int, Any], A_lo: Dict[int, Any], nib_hi, nib_lo):
+        """[(T, R)] from Engine.xor_value_public (one group), or None (_fused)"""
+        out = self._fused("xor_value_public", A_hi, A_lo, nib_hi, nib_lo, self.tab_hi, self.tab_lo)
+        return None if out is None else [out]
+
     def _loop(self, A_hi, A_lo, nib_hi, nib_lo):
-        """(T, R) as the product loop over encoded per-slot coefficient vectors (XOR4LUT._public_loop's form):
+        """[(T, R)] as the product loop over encoded per-slot coefficient vectors (XOR4LUT._public_loop's form):
         existing calls only, so it runs on any context"""
         ctx = self.ctx
         T = R = None
@@ -86,18 +90,27 @@ class XorValueLUT:
                 T = t if T is None else ctx.add(T, t)
             r = ctx.multiply(A[8], ctx.encode(tab[8, nib]))
             R = r if R is None else ctx.add(R, r)
-        return T, R
+        return [(T, R)]
 
     def apply_public(self, hi, lo, nib_hi, nib_lo):
-        """ONE ciphertext whose slots hold gain * (16 (hi ^ nib_hi) + (lo ^ nib_lo)) as real numbers, XOR_VALUE_DEPTH
-        levels below the inputs.  hi / lo: clean Zeta16 ciphertexts (unit magnitude, as a renorm or a fresh
-        encryption leaves them); nib_*: the public nibble of every slot (uint8, slot_count entries;
-        StateEncoder.nibble_slots)."""
+        """ONE ciphertext whose slots hold gain * (16 (hi ^ nib_hi) + (lo ^ nib_lo)) as real numbers -- a
+        TypedValueLUT: whose word slots hold gain * q + offset, q the integer the XORed bytes spell in the spec's
+        dtype, and whose other slots hold 0 -- XOR_VALUE_DEPTH levels below the inputs.  hi / lo: clean Zeta16
+        ciphertexts (unit magnitude, as a renorm or a fresh encryption leaves them); nib_*: the public nibble of
+        every slot (uint8, slot_count entries; StateEncoder.nibble_slots).
+
+        _engine / _loop give one (T, R) per weight group; a second group (the other byte of a 16-bit word) is
+        rotated onto the first before the one conjugation."""
         ctx = self.ctx
         nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
         A_hi, A_lo = self._bases(hi, lo)
-        out = self._engine(A_hi, A_lo, nib_hi, nib_lo)
-        T, R = out if out is not None else self._loop(A_hi, A_lo, nib_hi, nib_lo)
+        groups = self._engine(A_hi, A_lo, nib_hi, nib_lo)
+        if groups is None:
+            groups = self._loop(A_hi, A_lo, nib_hi, nib_lo)
+        T, R = groups[0]
+        if len(groups) == 2:
+            t1, r1 = self._rotate_pairs(list(groups[1]))
+            T, R = ctx.add(T, t1), ctx.add(R, r1)
         return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)
 
     def apply(self, hi, lo):
@@ -135,17 +148,8 @@ class TypedValueLUT(XorValueLUT):
         self._tabs = (16.0 * E, 16.0 * Es, E)  # hi unsigned, hi signed, lo (the fallback's)
 
     def _engine(self, A_hi, A_lo, nib_hi, nib_lo):
-        """[(T_g, R_g)] from ONE engine call (Engine.xor_value_typed); None as XorValueLUT._engine"""
-        ctx = self.ctx
-        ev = getattr(ctx, "xor_value_typed", None)
-        if ev is None or not getattr(ctx, "fused_luts", False):
-            return None
-        try:
-            return ev(A_hi, A_lo, nib_hi, nib_lo, self.weights, self.flags if self.flags.any() else None)
-        except RuntimeError as e:
-            if "level" in str(e):
-                return None
-            raise
+        """[(T_g, R_g)] from Engine.xor_value_typed, or None (_fused)"""
+        return self._fused("xor_value_typed", A_hi, A_lo, nib_hi, nib_lo, self.weights, self.flags if self.flags.any() else None)
 
     def _loop(self, A_hi, A_lo, nib_hi, nib_lo):
         """[(T_g, R_g)] as the product loop, the weights and the sign folded into the encoded coefficient vectors"""
@@ -174,18 +178,3 @@ class TypedValueLUT(XorValueLUT):
         if multi is not None:
             return multi([(c, -self.distance) for c in cts])
         return [ctx.rotate(c, -self.distance) for c in cts]
-
-    def apply_public(self, hi, lo, nib_hi, nib_lo):
-        """ONE ciphertext whose word slots hold gain * q + offset, q the integer the XORed bytes spell in the spec's
-        dtype, and whose other slots hold 0; XOR_VALUE_DEPTH levels below the inputs"""
-        ctx = self.ctx
-        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
-        A_hi, A_lo = self._bases(hi, lo)
-        out = self._engine(A_hi, A_lo, nib_hi, nib_lo)
-        if out is None:
-            out = self._loop(A_hi, A_lo, nib_hi, nib_lo)
-        T, R = out[0]
-        if len(out) == 2:
-            t1, r1 = self._rotate_pairs(list(out[1]))
-            T, R = ctx.add(T, t1), ctx.add(R, r1)
-        return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)

@@ -1,7 +1,7 @@
 """Public XOR fused with the value decode (aesfhe_xor_value_public) against the CPU oracle and the
 byte models.
 
-* encode parity: the 16 coefficient plaintexts of the device codec (k_value_slots -> inverse FFT -> untwist -> NTT)
+* encode parity: the 16 coefficient plaintexts of the device codec (k_value_slots_typed -> inverse FFT -> untwist -> NTT)
   against the oracle's host encoding of the same slot vectors, at both FFT pass splits (log N 13 and 16);
 * bit-exact: T and R equal sum_t A_t (.) P_t mod q put through the oracle's rescale, word for word;
 * the five refusals; all 256 (state nibble, public nibble) pairs on both halves at log N 15;
