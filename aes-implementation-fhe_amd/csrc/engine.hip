@@ -2140,109 +2140,181 @@ public:
         launch_key_inner(S(), T_, acc, ext, d, key, nd, ne, nl, hp_.alpha, B.nkey, B.nks, extmap(nl), g, nb,
                          (size_t)nd * ne * n, d_ms, (size_t)2 * ne * n, fold, accum);
     }
+    // the 2 x - c epilogue per member of a relinearisation + rescale (EvalMod's 2 T^2 - 1, the
+    // residues of lincomb(P, 2, nullptr, 0, -c, 0)): dbl bit m doubles member m, cst[m] its constant
+    struct Affine {
+        unsigned dbl = 0;
+        const u32* cst[kMaxKsBatch] = {};
+        bool any() const { return dbl != 0; }
+    };
+    // ------------------------------------------------------------------ ModDown
+    // ONE body for every ModDown of acc = [m][2][ne] (Q*P or q0 q1 P', NTT form): the h source rows from row r0 of
+    // each polynomial (limbs lm) to coefficients, their conversion to the nt target limbs for both polynomials of
+    // every member in one launch, and the NTT finish (acc - conv) pinv (+ the addends, or the Affine epilogue).
+    // Built by moddown (by P), moddown_rescale (by P and the level's dropped limbs) and keyswitch_d2s (by P').
+    struct MdSpec {
+        const char* who = "";  // the refusals' prefix
+        int ne = 0, h = 0, r0 = 0;
+        LimbMap lm{};
+        int nt = 0, out_level = 0;
+        const u32 *tab = nullptr, *qhinv = nullptr, *negq = nullptr, *pinv = nullptr;  // [h][nt] pairs, [h] pairs, [nt]; the final inverse
+        int d0 = 0, split = 0, d1 = 0;  // ConvBatch's: the first source prime; dropped-plus-P sources: P (prime d1) from source `split`
+        bool bx = false;                // k_bx_cols runs the middle (N = 2^16, h <= kBxMaxH)
+        bool rescale = false;           // divides by dropped limbs too: counted as a rescale
+        const u32 *add0 = nullptr, *add1 = nullptr;  // member m adds add0 / add1 + m add_ms words
+        size_t add_ms = 0;
+        bool add_rev = false;           // add0 read in reversed coefficient order (the conjugation's c0, galois)
+        const Affine* af = nullptr;
+    };
+    // nb batched ciphertexts
+    // dst: write the result there (member stride 2 nt N; the caller owns it) instead of a new buffer
+    // outm: member m's result into outm[m] (nb <= 8; the returned Ct then carries no data)
+    // ys_in: the source rows already through the INTT's row pass (ki_core, [m][2][h]): only its column pass runs here
+    Ct run_moddown(const MdSpec& s, const u32* acc, int nb, u32* dst = nullptr, u32* const* outm = nullptr, u32* ys_in = nullptr) {
+        const int n = hp_.n, npl = 2 * nb, h = s.h, nt = s.nt;
+        const bool fz = fused_conv(false), aff = s.af && s.af->any();
+        auto refuse = [&](const char* why) { throw std::runtime_error(std::string(s.who) + why); };
+        if (fz && aff) refuse(": the epilogue needs the separate conversion");
+        if (fz && ys_in) refuse(": a fused-core input needs the separate conversion");
+        if (fz && s.add_rev) refuse(": the reversed addend needs the separate conversion");
+        u32* ys = ys_in ? ys_in : tmp((size_t)npl * h);
+        if (s.bx) {  // the source rows through the INTT's row pass only (k_bx_cols runs the rest)
+            if (!ys_in) launch_ntt_inv_rows(S(), T_, ys, acc, npl * h, RowMap{h, s.ne, h, s.r0, 0}, s.lm);
+            cnt_[C_NTT_ROWS] += (size_t)npl * h;
+        } else if (ys_in) {
+            launch_ntt_inv_cols(S(), T_, ys, npl * h, rows_dense(h), s.lm, conv_pre_ ? s.qhinv : nullptr);
+            cnt_[C_NTT_ROWS] += (size_t)npl * h;
+        } else {
+            intt(ys, acc, npl * h, RowMap{h, s.ne, h, s.r0, 0}, s.lm, fz || conv_pre_ ? s.qhinv : nullptr);
+        }
+        u32* conv = tmp((size_t)npl * nt);
+        ConvBatch cb;
+        cb.n = npl;
+        cb.pre = conv_pre_ && !s.bx;
+        for (int p = 0; p < npl; ++p) {
+            cb.h[p] = h, cb.d0[p] = s.d0, cb.split[p] = s.split, cb.d1[p] = s.d1, cb.skip0[p] = 1 << 30;
+            cb.src[p] = ys + (size_t)p * h * n;
+            cb.dst[p] = conv + (size_t)p * nt * n;
+            cb.tab[p] = s.tab;
+            cb.qhinv[p] = s.qhinv;
+            cb.negq[p] = s.negq;
+        }
+        if (s.bx) launch_bx_cols(S(), T_, cb, nt, qmap());
+        else if (!fz) launch_base_convert(S(), T_, cb, nt, qmap());
+        Ct o;
+        if (dst || outm) {
+            o.level = s.out_level, o.npoly = npl, o.nb = nb, o.words = (size_t)npl * nt * n, o.data = dst;
+        } else {
+            o = alloc_ct(s.out_level, npl, nb);
+        }
+        const unsigned dbl = s.af ? s.af->dbl : 0u;
+        const u32* const* cst = aff ? s.af->cst : nullptr;
+        if (s.bx)
+            launch_ntt_finish_rows(S(), T_, o.data, conv, acc, s.ne, s.pinv, s.add0, s.add1, npl, nt, s.add_ms, outm, s.add_rev, dbl, cst);
+        else if (fz)
+            launch_ntt_finish_conv(S(), T_, o.data, conv, cb, acc, s.ne, s.pinv, s.add0, s.add1, npl, nt, s.add_ms, outm);
+        else
+            launch_ntt_finish(S(), T_, o.data, conv, acc, s.ne, s.pinv, s.add0, s.add1, npl, nt, s.add_ms, outm, dbl, cst, s.add_rev);
+        cnt_[C_NTT_ROWS] += (size_t)npl * nt;
+        if (!ys_in) untmp(ys, (size_t)npl * h);
+        untmp(conv, (size_t)npl * nt);
+        if (s.rescale) cnt_[C_RESCALE]++;
+        return o;
+    }
     // ModDown by P: coefficients of the P rows (read in place from acc), conversion of both
     // polys in one launch, NTT fused with (acc_Q - conv) P^{-1} (+ add)
-    // nb batched ciphertexts: acc = [m][2][ne]; member m adds add0/add1 + m add_ms words
-    // dst: write the result there (member stride 2 nl N; the caller owns it) instead of a new buffer
-    // outm: member m's result into outm[m] (nb <= 8; the returned Ct then carries no data)
-    // add_rev: add0 read in reversed coefficient order (the conjugation's c0, galois)
-    // ys_in: the P rows already through the INTT's row pass (ki_core, [m][2][np]): only its column pass runs here
     Ct moddown(const u32* acc, int level, const u32* add0, const u32* add1, int nb = 1, size_t add_ms = 0, u32* dst = nullptr,
                u32* const* outm = nullptr, bool add_rev = false, u32* ys_in = nullptr) {
         const KsBasis& B = kb(level);
-        const int n = hp_.n, nl = hp_.nl(level), np = B.np, ne = nl + np, npl = 2 * nb;
-        if (npl > kMaxConvGroups) throw std::runtime_error("moddown: batch too large");
-        const bool fz = fused_conv(false);
-        u32* yp = ys_in ? ys_in : tmp((size_t)npl * np);
-        const bool bx = bx_ok() && np <= kBxMaxH;
-        if (bx) {  // the P rows through the INTT's row pass only (k_bx_cols runs the rest)
-            if (!ys_in) launch_ntt_inv_rows(S(), T_, yp, acc, npl * np, RowMap{np, ne, np, nl, 0}, LimbMap{np, hp_.p_off(), 0});
-            cnt_[C_NTT_ROWS] += (size_t)npl * np;
-        } else if (ys_in) {
-            if (fz) throw std::runtime_error("moddown: a fused-core input needs the separate conversion");
-            launch_ntt_inv_cols(S(), T_, yp, npl * np, rows_dense(np), LimbMap{np, hp_.p_off(), 0}, conv_pre_ ? B.phinv : nullptr);
-            cnt_[C_NTT_ROWS] += (size_t)npl * np;
-        } else {
-            intt(yp, acc, npl * np, RowMap{np, ne, np, nl, 0}, LimbMap{np, hp_.p_off(), 0}, fz || conv_pre_ ? B.phinv : nullptr);
-        }
-        u32* conv = tmp((size_t)npl * nl);
-        ConvBatch dn;
-        dn.n = npl;
-        dn.pre = conv_pre_ && !bx;
-        for (int p = 0; p < npl; ++p) {
-            dn.h[p] = np, dn.d0[p] = hp_.p_off(), dn.skip0[p] = 1 << 30;
-            dn.src[p] = yp + (size_t)p * np * n;
-            dn.dst[p] = conv + (size_t)p * nl * n;
-            dn.tab[p] = B.moddown;
-            dn.qhinv[p] = B.phinv;
-            dn.negq[p] = B.negp;
-        }
-        if (bx) launch_bx_cols(S(), T_, dn, nl, qmap());
-        else if (!fz) launch_base_convert(S(), T_, dn, nl, qmap());
+        const int nl = hp_.nl(level), np = B.np;
+        if (2 * nb > kMaxConvGroups) throw std::runtime_error("moddown: batch too large");
+        MdSpec s;
+        s.who = "moddown", s.ne = nl + np, s.h = np, s.r0 = nl, s.lm = LimbMap{np, hp_.p_off(), 0};
+        s.nt = nl, s.out_level = level;
+        s.tab = B.moddown, s.qhinv = B.phinv, s.negq = B.negp, s.pinv = B.pinv, s.d0 = hp_.p_off();
+        s.bx = bx_ok() && np <= kBxMaxH;
+        s.add0 = add0, s.add1 = add1, s.add_ms = add_ms, s.add_rev = add_rev;
+        return run_moddown(s, acc, nb, dst, outm, ys_in);
+    }
+    // ------------------------------------------------------------------ one complete key switch
+    // ModUp, key inner product, ModDown of nb members at one level (run_ks): what keyswitch, relin_rescale,
+    // relin_rescale_tensor and the automorphisms of one ciphertext (galois, galois_lazy) each build.  The hoisted and
+    // accumulating forms (one ModUp for several inner products, sums across calls) are not jobs.
+    struct KsJob {
+        int level = 0, nb = 1;
+        // the polynomials to switch (NTT form; member m at d + m d_ms) and their keys.  nsrc == 2 (nb == 1 only): a
+        // deferred tensor's sigma(d1), sigma(d2) under the sigma(s) and sigma(s)^2 keys, summed in Q*P before the ModDown
+        int nsrc = 1;
+        const u32* d[2] = {};
+        const u32* key[2] = {};
+        size_t d_ms = 0;
+        const TensorPtrs* tp = nullptr;  // tensor mode (modup): the sources are products formed on load, d unused
+        bool rev = false;                // the sources read in reversed coefficient order (the conjugation)
+        bool separate = false;           // never the fused core (the permuted copy of a deferred tensor keeps its launches)
+        KsFold fold{};
+        // the end: ModDown by P plus the addends, or (rescale) by P and the dropped limbs with the optional epilogue
+        bool rescale = false;
+        const u32 *add0 = nullptr, *add1 = nullptr;
+        size_t add_ms = 0;
+        bool add_rev = false;
+        const Affine* af = nullptr;
+        // the result: a new ciphertext, or written to dst (member stride 2 nl N), or member m's to outm[m]
+        u32* dst = nullptr;
+        u32* const* outm = nullptr;
+    };
+    // -> (c0', c1') per member with c0' + c1' s = d s' (+ the addends / the fold), at `level` or, rescaled, one below.
+    // A stack of more members than one batched key switch carries (ks_chunk) goes through in chunks, each chunk's
+    // ModDown writing its rows of the one stacked result.
+    Ct run_ks(const KsJob& j) {
+        const int l = j.level, n = hp_.n, ne = hp_.nl(l) + np_at(l), ch = ks_chunk(l), nb = j.nb;
+        if (j.tp && nb > ch) throw std::runtime_error("relin_rescale_tensor: more members than one chunk");
+        if (j.outm && nb > ch) throw std::runtime_error("relin_rescale: per-member outputs need one chunk");
+        const int lo = j.rescale ? l - 1 : l, kept = hp_.nl(lo), h = ne - kept;
+        const bool fused = fused_ki_ok() && !j.separate;
+        const size_t oms = (size_t)2 * kept * n, xr = (size_t)j.nsrc * ext_rows(l);
         Ct o;
-        if (dst || outm) {
-            o.level = level, o.npoly = npl, o.nb = nb, o.words = (size_t)npl * nl * n, o.data = dst;
-        } else {
-            o = alloc_ct(level, npl, nb);
+        o.level = lo, o.npoly = 2 * nb, o.nb = nb, o.words = nb * oms, o.data = j.dst;
+        for (int m0 = 0; m0 < nb; m0 += ch) {
+            const int c = std::min(ch, nb - m0);
+            const u32* d[2] = {j.d[0] ? j.d[0] + m0 * j.d_ms : nullptr, j.d[1]};
+            KsFold fold = j.fold;
+            if (fold.add0) fold.add0 += m0 * fold.ms;
+            if (fold.add1) fold.add1 += m0 * fold.ms;
+            // two sources are consecutive polynomials of one tensor: ONE ModUp for both
+            u32* ext = modup(d[0], l, c * j.nsrc, j.nsrc == 2 ? (size_t)(d[1] - d[0]) : j.d_ms, j.tp, j.rev, fused);
+            u32* acc = tmp(2 * (size_t)ne * c);
+            u32* ys = fused ? tmp(2 * (size_t)h * c) : nullptr;
+            if (fused) {
+                KiSrc src[2];
+                for (int i = 0; i < j.nsrc; ++i) src[i] = KiSrc{ext + i * (size_t)ext_rows(l) * n, d[i], j.key[i]};
+                ki_core(acc, ys, l, kept, c, src, j.nsrc, j.d_ms, fold);
+            } else {
+                for (int i = 0; i < j.nsrc; ++i)
+                    key_inner(acc, ext + i * (size_t)ext_rows(l) * n, d[i], j.key[i], l, 0, c, j.d_ms, fold, i > 0);
+            }
+            untmp(ext, c * xr);
+            if (!o.data && !j.outm) o.data = alloc_words(o.words);
+            u32* out = o.data ? o.data + m0 * oms : nullptr;
+            if (j.rescale)
+                moddown_rescale(acc, l, c, out, j.outm, j.af, ys);
+            else
+                moddown(acc, l, j.add0 ? j.add0 + m0 * j.add_ms : nullptr, j.add1 ? j.add1 + m0 * j.add_ms : nullptr, c, j.add_ms, out, j.outm,
+                        j.add_rev, ys);
+            if (ys) untmp(ys, 2 * (size_t)h * c);
+            untmp(acc, 2 * (size_t)ne * c);
         }
-        if (fz && add_rev) throw std::runtime_error("moddown: the reversed addend needs the separate conversion");
-        if (bx)
-            launch_ntt_finish_rows(S(), T_, o.data, conv, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm, add_rev);
-        else if (fz)
-            launch_ntt_finish_conv(S(), T_, o.data, conv, dn, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm);
-        else
-            launch_ntt_finish(S(), T_, o.data, conv, acc, ne, B.pinv, add0, add1, npl, nl, add_ms, outm, 0u, nullptr, add_rev);
-        cnt_[C_NTT_ROWS] += (size_t)npl * nl;
-        if (!ys_in) untmp(yp, (size_t)npl * np);
-        untmp(conv, (size_t)npl * nl);
+        cnt_[C_KS] += nb * j.nsrc;
+        tally(LV_KS, l, nb * j.nsrc);
         return o;
     }
     // key switch of d (nl rows); nb > 1: the d polynomials of nb batched ciphertexts (d + m d_ms
     // words, add0 / add1 + m add_ms), one key read for all of them -> (c0', c1') per member
-    // A stack of more members than one batched key switch carries (ks_chunk) goes through in
-    // chunks, each chunk's ModDown writing its rows of the one stacked result.
     Ct keyswitch(const u32* d, int level, const u32* key, const u32* add0, const u32* add1, int nb = 1, size_t d_ms = 0,
                  size_t add_ms = 0, u32* dst = nullptr) {
-        const int ne = hp_.nl(level) + np_at(level), ch = ks_chunk(level);
-        if (nb > ch) {
-            Ct o;
-            if (dst) {
-                o.level = level, o.npoly = 2 * nb, o.nb = nb, o.words = (size_t)2 * nb * hp_.nl(level) * hp_.n, o.data = dst;
-            } else {
-                o = alloc_ct(level, 2 * nb, nb);
-            }
-            const size_t oms = (size_t)2 * hp_.nl(level) * hp_.n;
-            for (int m0 = 0; m0 < nb; m0 += ch) {
-                const int c = std::min(ch, nb - m0);
-                keyswitch(d + m0 * d_ms, level, key, add0 ? add0 + m0 * add_ms : nullptr, add1 ? add1 + m0 * add_ms : nullptr, c, d_ms, add_ms,
-                          o.data + m0 * oms);
-            }
-            return o;
-        }
-        if (fused_ki_ok()) {
-            const int np = np_at(level);
-            u32* ext = modup(d, level, nb, d_ms, nullptr, false, true);
-            u32* acc = tmp(2 * (size_t)ne * nb);
-            u32* ys = tmp(2 * (size_t)np * nb);
-            const KiSrc src{ext, d, key};
-            ki_core(acc, ys, level, hp_.nl(level), nb, &src, 1, d_ms, KsFold{});
-            untmp(ext, (size_t)nb * ext_rows(level));
-            Ct o = moddown(acc, level, add0, add1, nb, add_ms, dst, nullptr, false, ys);
-            untmp(ys, 2 * (size_t)np * nb);
-            untmp(acc, 2 * (size_t)ne * nb);
-            cnt_[C_KS] += nb;
-            tally(LV_KS, level, nb);
-            return o;
-        }
-        u32* ext = modup(d, level, nb, d_ms);
-        u32* acc = tmp(2 * (size_t)ne * nb);
-        key_inner(acc, ext, d, key, level, 0, nb, d_ms);
-        untmp(ext, (size_t)nb * ext_rows(level));
-        Ct o = moddown(acc, level, add0, add1, nb, add_ms, dst);
-        untmp(acc, 2 * (size_t)ne * nb);
-        cnt_[C_KS] += nb;
-        tally(LV_KS, level, nb);
-        return o;
+        KsJob j;
+        j.level = level, j.nb = nb, j.d[0] = d, j.key[0] = key, j.d_ms = d_ms;
+        j.add0 = add0, j.add1 = add1, j.add_ms = add_ms, j.dst = dst;
+        return run_ks(j);
     }
     // bootstrapping step 2: the single-limb (q0) ciphertexts' d = c1 switched to the sparse
     // secret with ksk_d2s (modulus q0 * P', P' = d2s_np() special primes); (c0', c1') with
@@ -2255,7 +2327,7 @@ public:
         const LimbMap em = extmap(nq);
         const u32* key = ksk(tag_d2s());
         // ModUp Q0 -> P' (the own limbs q0, q1 are read from d by the key inner product)
-        const bool fz = fused_conv(true), fzd = fused_conv(false);
+        const bool fz = fused_conv(true);
         u32* coef = tmp((size_t)nb * nq);
         intt(coef, d, nb * nq, RowMap{nq, (int)(ms / n), nq, 0, 0}, qmap(), fz || conv_pre_ ? d_d2s_ + d2s_off_.up_qhinv : nullptr);
         u32* ext = tmp((size_t)nb * ne);
@@ -2283,30 +2355,16 @@ public:
         u32* acc = tmp((size_t)npl * ne);
         launch_key_inner(S(), T_, acc, ext, d, key, 1, ne, nq, hp_.alpha, ne, nq, em, 0, nb, (size_t)ne * n, ms, (size_t)2 * ne * n);
         untmp(ext, (size_t)nb * ne);
-        // ModDown by P' onto (q0, q1), + add0
-        u32* yp = tmp((size_t)npl * np);
-        intt(yp, acc, npl * np, RowMap{np, ne, np, nq, 0}, LimbMap{np, hp_.p_off(), 0}, fzd || conv_pre_ ? d_d2s_ + d2s_off_.dn_qhinv : nullptr);
-        u32* conv = tmp((size_t)npl * nq);
-        ConvBatch dn;
-        dn.n = npl;
-        dn.pre = conv_pre_;
-        for (int p = 0; p < npl; ++p) {
-            dn.h[p] = np, dn.d0[p] = hp_.p_off(), dn.skip0[p] = 1 << 30;
-            dn.src[p] = yp + (size_t)p * np * n;
-            dn.dst[p] = conv + (size_t)p * nq * n;
-            dn.tab[p] = d_d2s_ + d2s_off_.dn_tab;      // [np][nq] pairs: (P' / p_k) mod q_t
-            dn.qhinv[p] = d_d2s_ + d2s_off_.dn_qhinv;  // [np] pairs: (P' / p_k)^-1 mod p_k
-            dn.negq[p] = d_d2s_ + d2s_off_.dn_negq;    // [nq]: -P' mod q_t
-        }
-        if (!fzd) launch_base_convert(S(), T_, dn, nq, qmap());
-        Ct o = alloc_ct(0, npl, nb);
-        if (fzd)
-            launch_ntt_finish_conv(S(), T_, o.data, conv, dn, acc, ne, d_d2s_ + d2s_off_.pinv, add0, nullptr, npl, nq, ms);
-        else
-            launch_ntt_finish(S(), T_, o.data, conv, acc, ne, d_d2s_ + d2s_off_.pinv, add0, nullptr, npl, nq, ms);
-        untmp(yp, (size_t)npl * np);
-        cnt_[C_NTT_ROWS] += (size_t)npl * nq;
-        untmp(conv, (size_t)npl * nq);
+        // ModDown by P' onto (q0, q1), + add0 (its own tables; no k_bx_cols form)
+        MdSpec s;
+        s.who = "keyswitch_d2s", s.ne = ne, s.h = np, s.r0 = nq, s.lm = LimbMap{np, hp_.p_off(), 0};
+        s.nt = nq, s.out_level = 0;
+        s.tab = d_d2s_ + d2s_off_.dn_tab;      // [np][nq] pairs: (P' / p_k) mod q_t
+        s.qhinv = d_d2s_ + d2s_off_.dn_qhinv;  // [np] pairs: (P' / p_k)^-1 mod p_k
+        s.negq = d_d2s_ + d2s_off_.dn_negq;    // [nq]: -P' mod q_t
+        s.pinv = d_d2s_ + d2s_off_.pinv, s.d0 = hp_.p_off();
+        s.add0 = add0, s.add_ms = ms;
+        Ct o = run_moddown(s, acc, nb);
         untmp(acc, (size_t)npl * ne);
         cnt_[C_KS] += nb;
         tally(LV_KS, 0, nb);
@@ -2328,118 +2386,38 @@ public:
         if (!fuse_rr_ || pm(c) != 3 || c.pend < 1 || c.level < 1 || c.zero) return false;
         return kb(c.level).mdr && 2 * ks_chunk(c.level) <= kMaxConvGroups;
     }
-    // a stack of more than ks_chunk members in chunks, each chunk's ModDown writing its rows of
-    // the one stacked result
+    // a stack of more than ks_chunk members goes through in chunks (run_ks)
     // outm (nb <= ks_chunk): member m's result straight into outm[m]; the returned Ct has no data
     Ct relin_rescale(const Ct& c, u32* const* outm = nullptr) {
-        const int l = c.level, n = hp_.n, nl = hp_.nl(l), ne = nl + np_at(l), nb = c.nb, ch = ks_chunk(l);
-        if (outm && nb > ch) throw std::runtime_error("relin_rescale: per-member outputs need one chunk");
-        const size_t ms = (size_t)3 * nl * n;
-        Ct o;
-        if (nb > ch) {
-            o = alloc_ct(l - 1, 2 * nb, nb);
-            const size_t oms = (size_t)2 * hp_.nl(l - 1) * n;
-            for (int m0 = 0; m0 < nb; m0 += ch) {
-                const int k = std::min(ch, nb - m0);
-                const u32* base = c.data + m0 * ms;
-                const KsFold fold{base, base + (size_t)nl * n, ms, kb(l).gadget};
-                if (fused_ki_ok()) {
-                    const int h = ne - hp_.nl(l - 1);
-                    u32* ext = modup(base + (size_t)2 * nl * n, l, k, ms, nullptr, false, true);
-                    u32* acc = tmp(2 * (size_t)ne * k);
-                    u32* ys = tmp(2 * (size_t)h * k);
-                    const KiSrc src{ext, base + (size_t)2 * nl * n, ksk_at(0, l)};
-                    ki_core(acc, ys, l, hp_.nl(l - 1), k, &src, 1, ms, fold);
-                    untmp(ext, (size_t)k * ext_rows(l));
-                    moddown_rescale(acc, l, k, o.data + m0 * oms, nullptr, nullptr, ys);
-                    untmp(ys, 2 * (size_t)h * k);
-                    untmp(acc, 2 * (size_t)ne * k);
-                    continue;
-                }
-                u32* ext = modup(base + (size_t)2 * nl * n, l, k, ms);
-                u32* acc = tmp(2 * (size_t)ne * k);
-                key_inner(acc, ext, base + (size_t)2 * nl * n, ksk_at(0, l), l, 0, k, ms, fold);
-                untmp(ext, (size_t)k * ext_rows(l));
-                moddown_rescale(acc, l, k, o.data + m0 * oms);
-                untmp(acc, 2 * (size_t)ne * k);
-            }
-        } else {
-            const u32* d2 = c.data + (size_t)2 * nl * n;
-            const KsFold fold{c.data, c.data + (size_t)nl * n, ms, kb(l).gadget};
-            if (fused_ki_ok()) {
-                const int h = ne - hp_.nl(l - 1);
-                u32* ext = modup(d2, l, nb, ms, nullptr, false, true);
-                u32* acc = tmp(2 * (size_t)ne * nb);
-                u32* ys = tmp(2 * (size_t)h * nb);
-                const KiSrc src{ext, d2, ksk_at(0, l)};
-                ki_core(acc, ys, l, hp_.nl(l - 1), nb, &src, 1, ms, fold);
-                untmp(ext, (size_t)nb * ext_rows(l));
-                o = moddown_rescale(acc, l, nb, nullptr, outm, nullptr, ys);
-                untmp(ys, 2 * (size_t)h * nb);
-                untmp(acc, 2 * (size_t)ne * nb);
-            } else {
-                u32* ext = modup(d2, l, nb, ms);
-                u32* acc = tmp(2 * (size_t)ne * nb);
-                key_inner(acc, ext, d2, ksk_at(0, l), l, 0, nb, ms, fold);
-                untmp(ext, (size_t)nb * ext_rows(l));
-                o = moddown_rescale(acc, l, nb, nullptr, outm);
-                untmp(acc, 2 * (size_t)ne * nb);
-            }
-        }
+        const int l = c.level;
+        const size_t rn = (size_t)hp_.nl(l) * hp_.n, ms = 3 * rn;
+        KsJob j;
+        j.level = l, j.nb = c.nb, j.d[0] = c.data + 2 * rn, j.key[0] = ksk_at(0, l), j.d_ms = ms;
+        j.fold = KsFold{c.data, c.data + rn, ms, kb(l).gadget};
+        j.rescale = true, j.outm = outm;
+        Ct o = run_ks(j);
         o.pend = c.pend - 1;
         o.lazy = c.lazy && o.pend > 0;
-        cnt_[C_KS] += nb;
-        tally(LV_KS, l, nb);
         cnt_[C_RELIN]++;
         return o;
     }
-    // the 2 x - c epilogue per member of a relinearisation + rescale (EvalMod's 2 T^2 - 1, the
-    // residues of lincomb(P, 2, nullptr, 0, -c, 0)): dbl bit m doubles member m, cst[m] its constant
-    struct Affine {
-        unsigned dbl = 0;
-        const u32* cst[kMaxKsBatch] = {};
-        bool any() const { return dbl != 0; }
-    };
     // relin_rescale of the products a[m] * b[m] (2-polynomial ciphertexts at one level, NTT form,
     // pend 0; nb <= ks_chunk) without materialising their tensors: the ModUp's inverse NTT forms
     // c2 = a1 (.) b1 on load, k_key_inner forms the own digit's c2 and the fold's (c0, c1) -- the
     // residues k_tensor_ptrs would have written, so the result is the same bit for bit, one launch
     // and 3 written + 3 re-read tensor rows per limb fewer (AESFHE_FUSED_TENSOR=0: tensor first)
     void relin_rescale_tensor(const TensorPtrs& tp, int l, int nb, u32* const* outm, const Affine* af = nullptr) {
-        const int n = hp_.n, nl = hp_.nl(l), ne = nl + np_at(l);
-        if (nb > ks_chunk(l) || nb > kMaxKsBatch) throw std::runtime_error("relin_rescale_tensor: more members than one chunk");
+        const size_t rn = (size_t)hp_.nl(l) * hp_.n;
         TensorPtrs t1;  // a1, b1
-        KsFold f{nullptr, nullptr, 0, kb(l).gadget};
-        f.tnl = nl;
-        for (int m = 0; m < nb; ++m) {
-            t1.a[m] = tp.a[m] + (size_t)nl * n, t1.b[m] = tp.b[m] + (size_t)nl * n;
-            f.ta[m] = tp.a[m], f.tb[m] = tp.b[m];
+        KsJob j;
+        j.level = l, j.nb = nb, j.key[0] = ksk_at(0, l), j.tp = &t1;
+        j.fold.gad = kb(l).gadget, j.fold.tnl = hp_.nl(l);
+        for (int m = 0; m < std::min(nb, kMaxKsBatch); ++m) {
+            t1.a[m] = tp.a[m] + rn, t1.b[m] = tp.b[m] + rn;
+            j.fold.ta[m] = tp.a[m], j.fold.tb[m] = tp.b[m];
         }
-        if (fused_ki_ok()) {
-            const int h = ne - hp_.nl(l - 1);
-            u32* ext = modup(nullptr, l, nb, 0, &t1, false, true);
-            u32* acc = tmp(2 * (size_t)ne * nb);
-            u32* ys = tmp(2 * (size_t)h * nb);
-            const KiSrc src{ext, nullptr, ksk_at(0, l)};
-            ki_core(acc, ys, l, hp_.nl(l - 1), nb, &src, 1, 0, f);
-            untmp(ext, (size_t)nb * ext_rows(l));
-            moddown_rescale(acc, l, nb, nullptr, outm, af, ys);
-            untmp(ys, 2 * (size_t)h * nb);
-            untmp(acc, 2 * (size_t)ne * nb);
-            cnt_[C_KS] += nb;
-            tally(LV_KS, l, nb);
-            cnt_[C_RELIN]++;
-            return;
-        }
-        u32* ext = modup(nullptr, l, nb, 0, &t1);
-        u32* acc = tmp(2 * (size_t)ne * nb);
-        key_inner(acc, ext, nullptr, ksk_at(0, l), l, 0, nb, 0, f);
-        untmp(ext, (size_t)nb * ext_rows(l));
-        Ct o = moddown_rescale(acc, l, nb, nullptr, outm, af);
-        (void)o;
-        untmp(acc, 2 * (size_t)ne * nb);
-        cnt_[C_KS] += nb;
-        tally(LV_KS, l, nb);
+        j.rescale = true, j.outm = outm, j.af = af;
+        run_ks(j);
         cnt_[C_RELIN]++;
     }
     // device residues of the constant -c at (level, pend 0), [limb][lo, hi] (k_lincomb's cadd), cached
@@ -2460,58 +2438,19 @@ public:
     Ct moddown_rescale(const u32* acc, int l, int nb, u32* dst = nullptr, u32* const* outm = nullptr, const Affine* af = nullptr,
                        u32* ys_in = nullptr) {
         const KsBasis& B = kb(l);
-        const int n = hp_.n, nl = hp_.nl(l), r = hp_.nl(l - 1), k = nl - r, np = B.np, ne = nl + np;
-        const int npl = 2 * nb, h = k + np;
-        if (!B.mdr || npl > kMaxConvGroups) throw std::runtime_error("moddown_rescale: unsupported level or batch");
-        const bool fz = fused_conv(false);
-        if (fz && af && af->any()) throw std::runtime_error("moddown_rescale: the epilogue needs the separate conversion");
-        const u32* mdr = B.mdr;
-        u32* ys = ys_in ? ys_in : tmp((size_t)npl * h);
-        const bool bx = bx_ok() && h <= kBxMaxH;
-        if (bx) {  // the dropped + P rows through the INTT's row pass only (k_bx_cols runs the rest)
-            if (!ys_in) launch_ntt_inv_rows(S(), T_, ys, acc, npl * h, RowMap{h, ne, h, r, 0}, LimbMap{k, r, hp_.p_off()});
-            cnt_[C_NTT_ROWS] += (size_t)npl * h;
-        } else if (ys_in) {
-            if (fz) throw std::runtime_error("moddown_rescale: a fused-core input needs the separate conversion");
-            launch_ntt_inv_cols(S(), T_, ys, npl * h, rows_dense(h), LimbMap{k, r, hp_.p_off()}, conv_pre_ ? mdr + 2 * (size_t)h * r : nullptr);
-            cnt_[C_NTT_ROWS] += (size_t)npl * h;
-        } else {
-            intt(ys, acc, npl * h, RowMap{h, ne, h, r, 0}, LimbMap{k, r, hp_.p_off()}, fz || conv_pre_ ? mdr + 2 * (size_t)h * r : nullptr);
-        }
-        u32* conv = tmp((size_t)npl * r);
-        ConvBatch cb;
-        cb.n = npl;
-        cb.pre = conv_pre_ && !bx;
-        for (int p = 0; p < npl; ++p) {
-            cb.h[p] = h, cb.d0[p] = r, cb.split[p] = k, cb.d1[p] = hp_.p_off(), cb.skip0[p] = 1 << 30;
-            cb.src[p] = ys + (size_t)p * h * n;
-            cb.dst[p] = conv + (size_t)p * r * n;
-            cb.tab[p] = mdr;                           // [h][r] pairs
-            cb.qhinv[p] = mdr + 2 * (size_t)h * r;     // [h] pairs
-            cb.negq[p] = mdr + 2 * (size_t)h * (r + 1);  // [r]
-        }
-        if (bx) launch_bx_cols(S(), T_, cb, r, qmap());
-        else if (!fz) launch_base_convert(S(), T_, cb, r, qmap());
-        Ct o;
-        if (dst || outm) {
-            o.level = l - 1, o.npoly = npl, o.nb = nb, o.words = (size_t)npl * r * n, o.data = dst;
-        } else {
-            o = alloc_ct(l - 1, npl, nb);
-        }
-        const u32* qinv = mdr + 2 * (size_t)h * (r + 1) + r;
-        if (bx)
-            launch_ntt_finish_rows(S(), T_, o.data, conv, acc, ne, qinv, nullptr, nullptr, npl, r, 0, outm, false, af ? af->dbl : 0u,
-                                   af && af->any() ? af->cst : nullptr);
-        else if (fz)
-            launch_ntt_finish_conv(S(), T_, o.data, conv, cb, acc, ne, qinv, nullptr, nullptr, npl, r, 0, outm);
-        else
-            launch_ntt_finish(S(), T_, o.data, conv, acc, ne, qinv, nullptr, nullptr, npl, r, 0, outm, af ? af->dbl : 0u,
-                              af && af->any() ? af->cst : nullptr);
-        if (!ys_in) untmp(ys, (size_t)npl * h);
-        cnt_[C_NTT_ROWS] += (size_t)npl * r;
-        untmp(conv, (size_t)npl * r);
-        cnt_[C_RESCALE]++;
-        return o;
+        const int nl = hp_.nl(l), r = hp_.nl(l - 1), k = nl - r, np = B.np, h = k + np;
+        if (!B.mdr || 2 * nb > kMaxConvGroups) throw std::runtime_error("moddown_rescale: unsupported level or batch");
+        MdSpec s;
+        s.who = "moddown_rescale", s.ne = nl + np, s.h = h, s.r0 = r, s.lm = LimbMap{k, r, hp_.p_off()};
+        s.nt = r, s.out_level = l - 1;
+        s.tab = B.mdr;                             // [h][r] pairs
+        s.qhinv = B.mdr + 2 * (size_t)h * r;       // [h] pairs
+        s.negq = B.mdr + 2 * (size_t)h * (r + 1);  // [r]
+        s.pinv = s.negq + r;
+        s.d0 = r, s.split = k, s.d1 = hp_.p_off();
+        s.bx = bx_ok() && h <= kBxMaxH;
+        s.rescale = true, s.af = af;
+        return run_moddown(s, acc, nb, dst, outm, ys_in);
     }
 
     // ct x ct.  Inputs are brought to canonical form; the tensor owes one rescale.  relin:
@@ -3117,63 +3056,29 @@ public:
         return pm(c) == 3 ? c.lazy : (pm(c) == 2 && c.pend > 0);  // an explicit 3-polynomial product stays an error
     }
     bool lazy_galois_ = std::getenv("AESFHE_LAZY_GALOIS") == nullptr || std::getenv("AESFHE_LAZY_GALOIS")[0] != '0';
+    // the conjugation (X -> X^(2N-1)) is the index reversal i -> N - 1 - i in this NTT order:
+    // read reversed where the permuted copy was read -- the ModUp's inverse NTT, the own
+    // digit's key inner product and the ModDown finish's c0 -- no k_automorph, same residues
+    bool conj_reversed(u64 g) const { return g == conj_galois() && conj_rev_ && !fused_conv(true) && !fused_conv(false); }
     Ct galois_lazy(const Ct& c, u64 g) {
-        const int l = c.level, nl = hp_.nl(l), np = np_at(l), ne = nl + np, n = hp_.n, k = pm(c);
-        if (g == conj_galois() && conj_rev_ && !fused_conv(true) && !fused_conv(false)) {
-            // the conjugation (X -> X^(2N-1)) is the index reversal i -> N - 1 - i in this NTT order:
-            // read reversed where the permuted copy was read -- the ModUp's inverse NTT, the own
-            // digit's key inner product and the ModDown finish's c0 -- no k_automorph, same residues
-            const int nsrc = k - 1;
-            KsFold fr{};
-            fr.rev_d = 1;
-            if (fused_ki_ok()) {
-                u32* ext = modup(c.data + (size_t)nl * n, l, nsrc, (size_t)nl * n, nullptr, true, true);
-                u32* acc = tmp(2 * (size_t)ne);
-                u32* ys = tmp(2 * (size_t)np);
-                const KiSrc src[2] = {{ext, c.data + (size_t)nl * n, ksk_at(g, l)},
-                                      {ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, nsrc == 2 ? ksk_at(tag_sq(g), l) : nullptr}};
-                ki_core(acc, ys, l, nl, 1, src, nsrc, 0, fr);
-                untmp(ext, (size_t)nsrc * ext_rows(l));
-                Ct o = moddown(acc, l, c.data, nullptr, 1, 0, nullptr, nullptr, true, ys);
-                untmp(ys, 2 * (size_t)np);
-                untmp(acc, 2 * (size_t)ne);
-                o.pend = c.pend;
-                o.lazy = c.pend > 0;
-                cnt_[C_KS] += nsrc;
-                tally(LV_KS, l, nsrc);
-                return o;
-            }
-            u32* ext = modup(c.data + (size_t)nl * n, l, nsrc, (size_t)nl * n, nullptr, true);
-            u32* acc = tmp(2 * (size_t)ne);
-            key_inner(acc, ext, c.data + (size_t)nl * n, ksk_at(g, l), l, 0, 1, 0, fr);
-            if (nsrc == 2)
-                key_inner(acc, ext + (size_t)ext_rows(l) * n, c.data + (size_t)2 * nl * n, ksk_at(tag_sq(g), l), l, 0, 1, 0, fr, true);
-            untmp(ext, (size_t)nsrc * ext_rows(l));
-            Ct o = moddown(acc, l, c.data, nullptr, 1, 0, nullptr, nullptr, true);
-            untmp(acc, 2 * (size_t)ne);
-            o.pend = c.pend;
-            o.lazy = c.pend > 0;
-            cnt_[C_KS] += nsrc;
-            tally(LV_KS, l, nsrc);
-            return o;
+        const int l = c.level, k = pm(c);
+        const size_t rn = (size_t)hp_.nl(l) * hp_.n;
+        const bool rev = conj_reversed(g);
+        u32* perm = nullptr;
+        if (!rev) {
+            perm = tmp((size_t)k * hp_.nl(l));
+            launch_automorph(S(), T_, perm, c.data, g, k * hp_.nl(l));
         }
-        u32* perm = tmp((size_t)k * nl);
-        launch_automorph(S(), T_, perm, c.data, g, k * nl);
-        // d1 (and d2) of the permuted tensor are consecutive rows: ONE ModUp for both sources
-        const int nsrc = k - 1;
-        u32* ext = modup(perm + (size_t)nl * n, l, nsrc, (size_t)nl * n);
-        u32* acc = tmp(2 * (size_t)ne);
-        key_inner(acc, ext, perm + (size_t)nl * n, ksk_at(g, l), l, 0);
-        if (nsrc == 2)
-            key_inner(acc, ext + (size_t)ext_rows(l) * n, perm + (size_t)2 * nl * n, ksk_at(tag_sq(g), l), l, 0, 1, 0, KsFold{}, true);
-        untmp(ext, (size_t)nsrc * ext_rows(l));
-        Ct o = moddown(acc, l, perm, nullptr);
-        untmp(acc, 2 * (size_t)ne);
-        untmp(perm, (size_t)k * nl);
+        const u32* t = rev ? c.data : perm;
+        KsJob j;
+        j.level = l, j.nsrc = k - 1, j.d[0] = t + rn, j.key[0] = ksk_at(g, l);
+        if (k == 3) j.d[1] = t + 2 * rn, j.key[1] = ksk_at(tag_sq(g), l);
+        j.rev = j.add_rev = rev, j.fold.rev_d = rev, j.separate = !rev;
+        j.add0 = t;
+        Ct o = run_ks(j);
+        if (perm) untmp(perm, (size_t)k * hp_.nl(l));
         o.pend = c.pend;
         o.lazy = c.pend > 0;
-        cnt_[C_KS] += nsrc;
-        tally(LV_KS, l, nsrc);
         return o;
     }
 
@@ -3190,45 +3095,22 @@ public:
     Ct galois(const Ct& c_in, u64 g) {
         if (vis_npoly(c_in) != 2) throw std::runtime_error("rotation/conjugation expects a 2-polynomial ciphertext");
         Ct c = normalize(c_in);
-        const int nl = hp_.nl(c.level), n = hp_.n;
+        const int nl = hp_.nl(c.level);
+        const size_t rn = (size_t)nl * hp_.n, ms = 2 * rn;  // ms: member stride of a batched ciphertext
         const u32* key = ksk_at(g, c.level);
-        if (g == conj_galois() && conj_rev_ && c.nb == 1 && !fused_conv(true) && !fused_conv(false)) {
-            // the conjugation as reversed reads (galois_lazy): no permuted copy
-            const int ne = nl + np_at(c.level);
-            KsFold fr{};
-            fr.rev_d = 1;
-            if (fused_ki_ok()) {
-                const int np = np_at(c.level);
-                u32* ext = modup(c.data + (size_t)nl * n, c.level, 1, 0, nullptr, true, true);
-                u32* acc = tmp(2 * (size_t)ne);
-                u32* ys = tmp(2 * (size_t)np);
-                const KiSrc src{ext, c.data + (size_t)nl * n, key};
-                ki_core(acc, ys, c.level, nl, 1, &src, 1, 0, fr);
-                untmp(ext, (size_t)ext_rows(c.level));
-                Ct o = moddown(acc, c.level, c.data, nullptr, 1, 0, nullptr, nullptr, true, ys);
-                untmp(ys, 2 * (size_t)np);
-                untmp(acc, 2 * (size_t)ne);
-                cnt_[C_KS]++;
-                tally(LV_KS, c.level, 1);
-                if (c.data != c_in.data) release(c);
-                return o;
-            }
-            u32* ext = modup(c.data + (size_t)nl * n, c.level, 1, 0, nullptr, true);
-            u32* acc = tmp(2 * (size_t)ne);
-            key_inner(acc, ext, c.data + (size_t)nl * n, key, c.level, 0, 1, 0, fr);
-            untmp(ext, (size_t)ext_rows(c.level));
-            Ct o = moddown(acc, c.level, c.data, nullptr, 1, 0, nullptr, nullptr, true);
-            untmp(acc, 2 * (size_t)ne);
-            cnt_[C_KS]++;
-            tally(LV_KS, c.level, 1);
-            if (c.data != c_in.data) release(c);
-            return o;
+        const bool rev = c.nb == 1 && conj_reversed(g);      // the conjugation as reversed reads (galois_lazy): no permuted copy
+        u32* perm = nullptr;
+        if (!rev) {
+            perm = tmp(2 * (size_t)nl * c.nb);
+            launch_automorph(S(), T_, perm, c.data, g, 2 * nl * c.nb);
         }
-        u32* perm = tmp(2 * (size_t)nl * c.nb);
-        launch_automorph(S(), T_, perm, c.data, g, 2 * nl * c.nb);
-        const size_t ms = (size_t)2 * nl * n;  // member stride of a batched ciphertext
-        Ct o = keyswitch(perm + (size_t)nl * n, c.level, key, perm, nullptr, c.nb, ms, ms);
-        untmp(perm, 2 * (size_t)nl * c.nb);
+        const u32* t = rev ? c.data : perm;
+        KsJob j;
+        j.level = c.level, j.nb = c.nb, j.d[0] = t + rn, j.key[0] = key, j.d_ms = ms;
+        j.rev = j.add_rev = rev, j.fold.rev_d = rev;
+        j.add0 = t, j.add_ms = ms;
+        Ct o = run_ks(j);
+        if (perm) untmp(perm, 2 * (size_t)nl * c.nb);
         if (c.data != c_in.data) release(c);
         return o;
     }

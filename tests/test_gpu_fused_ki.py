@@ -5,36 +5,17 @@ the same ciphertext bytes: relinearisation (keyswitch), relinearisation fused wi
 (gadget fold), products relinearised from their factors (tensor fold, batched members), rotations
 (permuted copy + keyswitch), conjugations (reversed own-digit read) of canonical and deferred
 ciphertexts (two summed sources), a stack wider than one key-switch chunk, and a bootstrap."""
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
+sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
+
+from keyswitch_ops import run as _run  # noqa: E402  the operation list shared with tools/keyswitch_digest.py
+
 pytestmark = pytest.mark.gpu
-
-
-def _run(E, sparse: bool):
-    rng = np.random.default_rng(23)
-    zs = [np.exp(2j * np.pi * rng.random(E.slot_count)) for _ in range(6)]
-    a, b, c = (E.encrypt(z) for z in zs[:3])
-    out = []
-    prod = E.multiply(a, b, "rlk")                       # lazy product (deferred relinearisation)
-    out.append(E.relinearize(E.multiply(a, b)))          # keyswitch (relin_raw)
-    out.append(E.add(prod, c))                           # normalize: relin fused with its rescale
-    out += E.multiply_many([(a, b), (b, c), (a, c)])     # tensor fold, 3 members
-    out.append(E.rotate(a, None, 3))                     # permuted copy + keyswitch
-    out.append(E.conjugate(a))                           # reversed own digit
-    out.append(E.conjugate(prod))                        # deferred tensor: two summed sources
-    out += E.conjugate_many([b, E.multiply(c, 0.5 + 0.25j)])
-    st = E.stack([E.encrypt(z) for z in zs[:4] + zs[:4] + zs[:2]])  # 10 members: chunked key switches
-    out.append(E.multiply(st, st, "rlk"))
-    out.append(E.conjugate(st))
-    if sparse:
-        P = 32
-        z = np.exp(2j * np.pi * rng.random(P))
-        out.append(E.bootstrap_sparse(E.encrypt(np.tile(z, E.slot_count // P)), P))
-    flat = []
-    for x in out:
-        flat += E.unstack(x) if E.members(x) > 1 else [x]
-    return [E.export(x).tobytes() for x in flat]
 
 
 @pytest.mark.parametrize("logn", [13, 16])

@@ -1,0 +1,49 @@
+"""The complete key switch pinned bit for bit (tools/keyswitch_digest.py against tests/golden/keyswitch_digests.json,
+recorded at the commit the file names): every operation of tests/helpers/keyswitch_ops.py -- relinearisation alone
+and fused with its rescale, products relinearised from their factors, rotations, conjugations of canonical, deferred
+and lazy three-polynomial ciphertexts, stacks wider than one key-switch chunk, a sparse bootstrap -- gives the same
+exported residues, the same levels, the same number of kernel launches and the same engine counters, under every
+setting of AESFHE_FUSED_KI x AESFHE_CONJ_REV (log N 13) and of AESFHE_BX_COLS (log N 16).
+
+The A/B tests (test_gpu_fused_ki, test_gpu_conj_rev, test_gpu_bx_cols) compare two settings of one build with each
+other; these compare each setting with its own past, which also sees a launch more or a counter less.  One engine
+per case, so a case is one test; a failure names the first operation that differs."""
+import json
+import sys
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT / "tools") not in sys.path:
+    sys.path.insert(0, str(ROOT / "tools"))
+
+import keyswitch_digest as ksd  # noqa: E402
+from keyswitch_ops import operations  # noqa: E402  (tests/helpers: the tool put it on the path)
+
+GOLDEN = json.loads((ROOT / "tests" / "golden" / "keyswitch_digests.json").read_text())
+
+
+def test_golden_covers_every_case():
+    """no GPU: the golden file holds every case the tool defines, and each case every operation of the shared list
+    that its engine runs (the bootstrap only where the engine has one)"""
+    import inspect
+    import re
+    assert sorted(GOLDEN["cases"]) == sorted(ksd.CASES)
+    ops = re.findall(r'yield "(\w+)"', inspect.getsource(operations))
+    assert len(ops) == 12 and ops[-1] == "bootstrap_sparse32"
+    for case, (_, sparse, _) in ksd.CASES.items():
+        rec = GOLDEN["cases"][case]
+        assert sorted(rec) == sorted(ops if sparse else ops[:-1]), case
+        for name, r in rec.items():
+            assert sorted(r) == ["counters", "launches", "level", "sha256"] and r["launches"] > 0, (case, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(ksd.CASES))
+def test_keyswitch_bit_identical(case):
+    want = GOLDEN["cases"][case]
+    got = ksd.case_digests(case)
+    assert sorted(got) == sorted(want)
+    for name in got:  # in the order the operations ran: the first difference is the one to look at
+        assert got[name] == want[name], f"first differing operation: {name} (golden of {GOLDEN['parent']})"
