@@ -1900,10 +1900,11 @@ public:
         const uint8_t* nib = nullptr;    // both nibble arrays, hi then lo
         const double* wt = nullptr;      // [G][slots], null: weight 1
         const uint8_t* flags = nullptr;  // [G][slots], null: no slot signed
-        double top[kValueGroups] = {};   // max |w| per group
+        double top[kValueGroupsMax] = {};  // max |w| per group
     };
     // nibbles, weights and flags checked and copied into this stream's staging buffer in ONE copy:
-    // (weights given) [G][s] doubles, then 2 s nibble bytes, then (flags given) G s flag bytes
+    // (weights given) [G][s] doubles, then 2 s nibble bytes, then (flags given) G s flag bytes.  The buffer of the
+    // plain and typed decodes holds kValueGroups groups; more groups (xor_value_groups) take a second, wider one
     ValueStage stage_value(const std::string& who, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights,
                            const uint8_t* flags) {
         const int s = slot_count();
@@ -1925,9 +1926,11 @@ public:
         copy_nibbles(who, nib_hi, h.data() + o_nib);
         copy_nibbles(who, nib_lo, h.data() + o_nib + s);
         if (flags) std::memcpy(h.data() + o_flag, flags, nw);
-        // sized for kValueGroups groups with weights and flags: 8 G s + 2 s + G s bytes
-        if (!d_val_[t_sidx]) d_val_[t_sidx] = (uint8_t*)dev_alloc(((size_t)(9 * kValueGroups + 2) * s + 3) / 4);
-        uint8_t* d = d_val_[t_sidx];
+        // sized for kValueGroups (kValueGroupsMax) groups with weights and flags: 8 G s + 2 s + G s bytes
+        const bool wide = G > kValueGroups;
+        uint8_t*& buf = wide ? d_val_wide_[t_sidx] : d_val_[t_sidx];
+        if (!buf) buf = (uint8_t*)dev_alloc(((size_t)(9 * (wide ? kValueGroupsMax : kValueGroups) + 2) * s + 3) / 4);
+        uint8_t* d = buf;
         HIP_OK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, S()));
         st.wt = weights ? (const double*)d : nullptr;
         st.nib = d + o_nib;
@@ -1935,8 +1938,9 @@ public:
         return st;
     }
     // the G x 16 per-slot coefficient plaintexts: channel t = half * 8 + (p - 1) of group g holds E_p of nibble array
-    // `half` (p = 1..8) times group g's weights, one codec pass per group (encode_channels).  G x 16 x nl rows (tmp)
-    u32* value_encode(const ValueTab& V, const ValueStage& st, int G, double scale, int nl) {
+    // `half` (p = 1..8) times group g's weights, one codec pass per group (encode_channels), for the G groups from
+    // g0 on.  G x 16 x nl rows (tmp)
+    u32* value_encode(const ValueTab& V, const ValueStage& st, int g0, int G, double scale, int nl) {
         ValueSlotArgs ch;
         for (int t = 0; t < kValueCh; ++t) {
             const int half = t / 8, p = (t % 8) + 1;
@@ -1946,13 +1950,16 @@ public:
         const int s = slot_count();
         return encode_channels(G, kValueCh, scale, nl, [&](int g, double* w) {
             launch_value_slots_typed(S(), T_, w, (const double*)V.tab.first, 2 * kValueRows, ch, kValueCh, st.nib,
-                                     st.wt ? st.wt + (size_t)g * s : nullptr, st.flags ? st.flags + (size_t)g * s : nullptr, d_slot_pos_);
+                                     st.wt ? st.wt + (size_t)(g0 + g) * s : nullptr, st.flags ? st.flags + (size_t)(g0 + g) * s : nullptr,
+                                     d_slot_pos_);
         });
     }
     // per group g: oT[g] = sum_{p = 1..7} w_g E_p[nib_hi] (.) hi^p + w_g E_p[nib_lo] (.) lo^p and oR[g] = the two E_8 terms.
     // A_hi / A_lo are indexed by the power p (entry 0 unused), the operands canonical and dropped exactly to their
-    // common lowest logical level l as lut_eval_public's, ONE k_value_typed_mac launch for all 2 G sums; each output
-    // owes its rescale (applied here when the raw scale has no headroom)
+    // common lowest logical level l as lut_eval_public's, ONE k_value_typed_mac launch for all 2 G sums -- per chunk
+    // of kValueChunk groups where G is larger (xor_value_groups: the codec buffer holds one chunk's rows, and every
+    // chunk reads the same canonical operands); each output owes its rescale (applied here when the raw scale has no
+    // headroom)
     void value_decode(const std::string& who, const char* what, aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo,
                       const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT,
                       Ct* oR) {
@@ -1963,19 +1970,22 @@ public:
         const int l = public_operands(who, what, A, kValueCh);
         const ValueStage st = stage_value(who, nib_hi, nib_lo, n_slots, G, weights, flags);
         const int nl = hp_.nl(l);
-        Ct out[2 * kValueGroups];  // T_0, R_0, T_1, R_1
+        Ct out[2 * kValueGroupsMax];  // T_0, R_0, T_1, R_1, ...
         public_op([&](PubTemps& s) {
             ValueMacArgs a;
             operands_at(A, kValueCh, l, a.a, s.own);
             for (int t = 0; t < kValueCh; ++t) a.real[t] = (t % 8) == 7;  // the a^8 terms: R
             cnt_[C_PTMUL] += (G - 1) * kValueCh;                          // every group multiplies every operand
-            s.mrows = (size_t)G * kValueCh * nl;
-            s.m = value_encode(V, st, G, hp_.ptscale[l], nl);
-            ValueTypedOut o;
-            for (int k = 0; k < 2 * G; ++k) s.res.push_back(out[k] = alloc_ct(l, 2));
-            for (int g = 0; g < G; ++g) o.t[g] = out[2 * g].data, o.r[g] = out[2 * g + 1].data;
-            launch_value_typed_mac(S(), T_, o, G, a, kValueCh, s.m, nl, qmap());
-            untmp(s.m, s.mrows), s.m = nullptr;
+            for (int g0 = 0; g0 < G; g0 += kValueChunk) {
+                const int gc = std::min(kValueChunk, G - g0);
+                s.mrows = (size_t)gc * kValueCh * nl;
+                s.m = value_encode(V, st, g0, gc, hp_.ptscale[l], nl);
+                ValueChunkOut o;
+                for (int k = 2 * g0; k < 2 * (g0 + gc); ++k) s.res.push_back(out[k] = alloc_ct(l, 2));
+                for (int g = 0; g < gc; ++g) o.t[g] = out[2 * (g0 + g)].data, o.r[g] = out[2 * (g0 + g) + 1].data;
+                launch_value_chunk_mac(S(), T_, o, gc, a, kValueCh, s.m, nl, qmap());
+                untmp(s.m, s.mrows), s.m = nullptr;
+            }
             for (int k = 0; k < 2 * G; ++k) owe_rescale(out[k], s.res[k], (k & 1 ? V.mag_r : V.mag_t) * st.top[k / 2], s.own);
         });
         for (int g = 0; g < G; ++g) oT[g] = out[2 * g], oR[g] = out[2 * g + 1];
@@ -1988,7 +1998,11 @@ public:
         debug_args(who, level, out, scale);
         const ValueStage st = stage_value(op, nib_hi, nib_lo, n_slots, G, weights, flags);
         const int nl = hp_.nl(level);
-        read_rows(value_encode(V, st, G, hp_.ptscale[level], nl), (size_t)G * kValueCh * nl, level, out, scale);
+        for (int g0 = 0; g0 < G; g0 += kValueChunk) {  // chunk by chunk, as value_decode encodes them
+            const int gc = std::min(kValueChunk, G - g0);
+            read_rows(value_encode(V, st, g0, gc, hp_.ptscale[level], nl), (size_t)gc * kValueCh * nl, level,
+                      out + (size_t)g0 * kValueCh * nl * hp_.n, scale);
+        }
     }
     // the entry points: the plain decode is one group with unit weights and no flags; only the typed one takes (and
     // then requires) weights
@@ -1996,6 +2010,22 @@ public:
         vtab(hv);
         if (G < 1 || G > kValueGroups) throw std::runtime_error(who + ": n_groups must be 1 or 2");
         if (!weights) throw std::runtime_error(who + ": missing weights");
+    }
+    // the linear decode's entry: up to 16 groups, the cyclic diagonals of a 16 x 16 matrix per state
+    void groups_args(const std::string& who, aesfhe_handle hv, int G, const double* weights) const {
+        vtab(hv);
+        if (G < 1 || G > kValueGroupsMax) throw std::runtime_error(who + ": n_groups must be 1..16");
+        if (!weights) throw std::runtime_error(who + ": missing weights");
+    }
+    void xor_value_groups(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                          int n_slots, int G, const double* weights, const uint8_t* flags, Ct* oT, Ct* oR) {
+        groups_args("xor_value_groups", hv, G, weights);
+        value_decode("xor_value_groups", "linear value decode", hv, A_hi, A_lo, nib_hi, nib_lo, n_slots, G, weights, flags, oT, oR);
+    }
+    void debug_value_groups_pt(aesfhe_handle hv, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int G, const double* weights,
+                               const uint8_t* flags, int level, u32* out, double* scale) {
+        groups_args("debug_xor_value_groups_pt", hv, G, weights);
+        debug_value_rows("debug_xor_value_groups_pt", "xor_value_groups", hv, nib_hi, nib_lo, n_slots, G, weights, flags, level, out, scale);
     }
     void xor_value_public(aesfhe_handle hv, const aesfhe_handle* A_hi, const aesfhe_handle* A_lo, const uint8_t* nib_hi,
                           const uint8_t* nib_lo, int n_slots, Ct* oT, Ct* oR) {
@@ -5661,6 +5691,7 @@ private:
     uint8_t* d_pub_nib_[kStreams] = {};        // lut_eval_public: the public nibbles, one byte per slot
     std::vector<uint8_t> h_pub_nib_[kStreams];  // their host staging copy
     uint8_t* d_val_[kStreams] = {};        // the value decode: weights, both nibble arrays, flags (stage_value)
+    uint8_t* d_val_wide_[kStreams] = {};   // the same for more than kValueGroups groups (xor_value_groups)
     std::vector<uint8_t> h_val_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
@@ -5903,6 +5934,21 @@ int aesfhe_xor_value_typed(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_ha
 int aesfhe_debug_xor_value_typed_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int n_groups,
                                     const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale) {
     API_BEGIN ctx->eng->debug_value_typed_pt(table, nib_hi, nib_lo, n_slots, n_groups, weights, flags, level, out, scale);
+    API_END
+}
+int aesfhe_xor_value_groups(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo, const uint8_t* nib_hi,
+                            const uint8_t* nib_lo, int n_slots, int n_groups, const double* weights, const uint8_t* flags, aesfhe_handle* out_t,
+                            aesfhe_handle* out_r) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out_t || !out_r) throw std::runtime_error("xor_value_groups: missing output handles");
+    Ct t[kValueGroupsMax], r[kValueGroupsMax];
+    e.xor_value_groups(table, a_hi, a_lo, nib_hi, nib_lo, n_slots, n_groups, weights, flags, t, r);
+    for (int g = 0; g < n_groups; ++g) out_t[g] = e.put_ct(t[g]), out_r[g] = e.put_ct(r[g]);
+    API_END
+}
+int aesfhe_debug_xor_value_groups_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int n_groups,
+                                     const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale) {
+    API_BEGIN ctx->eng->debug_value_groups_pt(table, nib_hi, nib_lo, n_slots, n_groups, weights, flags, level, out, scale);
     API_END
 }
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table) {

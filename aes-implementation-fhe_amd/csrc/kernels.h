@@ -642,3 +642,16 @@ struct ValueTypedOut {
 };
 void launch_value_typed_mac(hipStream_t st, const DevTables& T, const ValueTypedOut& out, int groups, const ValueMacArgs& a, int n,
                             const u32* pt, int nl, LimbMap map);
+// More weight groups (the cyclic diagonals of a 16 x 16 matrix, up to kValueGroupsMax) are walked
+// kValueChunk at a time: one codec buffer of at most kValueChunk x kValueCh x nl rows and ONE MAC launch per chunk,
+// every ciphertext word loaded once for all of the chunk's groups.  launch_value_chunk_mac is launch_value_typed_mac
+// for 1..kValueChunk groups (one or two: that launcher and its kernels; more: k_value_typed_mac<G, ValueChunkOut>);
+// the 15-terms-per-sum refusal holds per group.  gfx950: G = 8 takes 60 VGPRs / 58 SGPRs, no scratch, 8 waves per SIMD
+constexpr int kValueGroupsMax = 16;
+constexpr int kValueChunk = 8;
+struct ValueChunkOut {
+    u32* t[kValueChunk] = {};
+    u32* r[kValueChunk] = {};
+};
+void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunkOut& out, int groups, const ValueMacArgs& a, int n,
+                            const u32* pt, int nl, LimbMap map);

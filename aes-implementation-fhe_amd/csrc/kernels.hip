@@ -140,9 +140,10 @@ __global__ void k_lut_public_mac(u32* out1, u32* out2, PubMacArgs a, int n, cons
 // follow group g - 1's (kValueCh channels each).  Each ciphertext word is loaded once and multiplied into all G
 // groups; G is a template argument, so the group loop unrolls and the 2 G sums stay in registers.  64-bit sums with
 // one reduction each: the residues are below 2^30, so the 14 products of T (15 at most, the launcher checks) stay
-// below 15 x 2^60 < 2^64
-template <int G>
-__global__ void k_value_typed_mac(ValueTypedOut o, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc, int logn) {
+// below 15 x 2^60 < 2^64.  Out holds the 2 G output pointers: ValueTypedOut for the typed decode's one or two groups,
+// ValueChunkOut for a chunk of the linear decode's (launch_value_chunk_mac)
+template <int G, class Out>
+__global__ void k_value_typed_mac(Out o, ValueMacArgs a, int n, const u32* pt, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     EW_PROLOGUE
     const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
     u64 accT[G] = {}, accR[G] = {};
@@ -2321,9 +2322,43 @@ void launch_value_typed_mac(hipStream_t st, const DevTables& T, const ValueTyped
     // reads: n ciphertexts and groups x n plaintext channels; writes: 2 x groups ciphertexts
     const double bytes = 2.0 * nl * (n + 2 * groups) + (double)groups * n * nl;
     if (groups == 1)
-        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<1>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n, pt, nl, map,
-                    T.pc, T.logn);
+        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<1, ValueTypedOut>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n,
+                    pt, nl, map, T.pc, T.logn);
     else
-        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<2>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n, pt, nl, map,
-                    T.pc, T.logn);
+        prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<2, ValueTypedOut>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n,
+                    pt, nl, map, T.pc, T.logn);
+}
+// one chunk of the value decode's groups: one or two go to launch_value_typed_mac (the typed decode's kernels,
+// unchanged), more to k_value_typed_mac<groups, ValueChunkOut> -- one instantiation per chunk size, so a short last
+// chunk (a 3-tap filter) carries no idle sums
+template <int G>
+static void value_chunk_mac(hipStream_t st, const DevTables& T, double bytes, const ValueChunkOut& out, int groups, const ValueMacArgs& a, int n,
+                            const u32* pt, int nl, LimbMap map) {
+    if constexpr (G > kValueGroups) {
+        if (groups == G)
+            prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_value_typed_mac<G, ValueChunkOut>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, out, a, n,
+                        pt, nl, map, T.pc, T.logn);
+        else
+            value_chunk_mac<G - 1>(st, T, bytes, out, groups, a, n, pt, nl, map);
+    }
+}
+void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunkOut& out, int groups, const ValueMacArgs& a, int n,
+                            const u32* pt, int nl, LimbMap map) {
+    if (groups >= 1 && groups <= kValueGroups) {
+        ValueTypedOut o;
+        for (int g = 0; g < groups; ++g) o.t[g] = out.t[g], o.r[g] = out.r[g];
+        return launch_value_typed_mac(st, T, o, groups, a, n, pt, nl, map);
+    }
+    if (groups < 1 || groups > kValueChunk) throw std::runtime_error("launch_value_chunk_mac: 1..8 groups");
+    if (n < 1 || n > kValueCh || !pt) throw std::runtime_error("launch_value_chunk_mac: 1..16 ciphertexts");
+    for (int g = 0; g < groups; ++g)
+        if (!out.t[g] || !out.r[g]) throw std::runtime_error("launch_value_chunk_mac: missing output");
+    int nr = 0;
+    for (int t = 0; t < n; ++t) {
+        if (!a.a[t]) throw std::runtime_error("launch_value_chunk_mac: bad operand");
+        nr += a.real[t] != 0;
+    }
+    if (nr > 15 || n - nr > 15) throw std::runtime_error("launch_value_chunk_mac: at most 15 terms per sum");
+    // reads: n ciphertexts and groups x n plaintext channels; writes: 2 x groups ciphertexts
+    value_chunk_mac<kValueChunk>(st, T, 2.0 * nl * (n + 2 * groups) + (double)groups * n * nl, out, groups, a, n, pt, nl, map);
 }

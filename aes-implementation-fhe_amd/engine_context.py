@@ -439,3 +439,9 @@ class EngineContext:
         weight groups over the same powers -- one engine call (Engine.xor_value_typed).  Modules
         test for it with getattr(ctx, "xor_value_typed", None)."""
         return self.engine.xor_value_typed(a_hi, a_lo, nib_hi, nib_lo, weights, flags)
+
+    def xor_value_groups(self, a_hi, a_lo, nib_hi, nib_lo, weights, flags=None):
+        """[(T_k, R_k)]: xor_value_typed for up to 16 weight groups -- the cyclic diagonals of a 16 x 16 matrix applied
+        to the decoded bytes -- in one engine call (Engine.xor_value_groups).  Modules test for it
+        with getattr(ctx, "xor_value_groups", None)."""
+        return self.engine.xor_value_groups(a_hi, a_lo, nib_hi, nib_lo, weights, flags)

@@ -52,6 +52,7 @@ EXPORTED = [
     "aesfhe_rot_pt_sum", "aesfhe_rot_pt_affine", "aesfhe_export_ksk_at",
     "aesfhe_xor_value_create", "aesfhe_xor_value_public", "aesfhe_debug_xor_value_pt", "aesfhe_xor_value_free",
     "aesfhe_xor_value_typed", "aesfhe_debug_xor_value_typed_pt",
+    "aesfhe_xor_value_groups", "aesfhe_debug_xor_value_groups_pt",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -154,6 +155,8 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_xor_value_free"] = [vp, _H]
     sig["aesfhe_xor_value_typed"] = [vp, _H, _Hp, _Hp, _bp, _bp, c_int, c_int, vp, vp, _Hp, _Hp]
     sig["aesfhe_debug_xor_value_typed_pt"] = [vp, _H, _bp, _bp, c_int, c_int, vp, vp, c_int, _up, ctypes.POINTER(c_dbl)]
+    sig["aesfhe_xor_value_groups"] = sig["aesfhe_xor_value_typed"]
+    sig["aesfhe_debug_xor_value_groups_pt"] = sig["aesfhe_debug_xor_value_typed_pt"]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -1201,6 +1204,33 @@ class Engine:
         scale = ctypes.c_double(0.0)
         self._ctx.check(self._lib.aesfhe_debug_xor_value_typed_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), G, w, fp, int(level),
                                                                   out, ctypes.byref(scale)))
+        return out, scale.value
+
+    def xor_value_groups(self, a_hi, a_lo, nib_hi, nib_lo, weights, flags=None):
+        """[(T_k, R_k)] of the linear value decode (aesfhe_xor_value_groups): xor_value_typed for
+        G = 1..16 weight groups over the same powers, the groups walked in chunks of 8 (one codec buffer and one MAC
+        launch per chunk).  With group k weighing byte position p's slot by W[(p - k) % 16, p],
+        sum_k rotate(X_k, k unit) is W applied to the decoded bytes.  weights: (G, slot_count) float64, finite;
+        flags: the same shape of uint8, or None.  Errors as xor_value_typed's ("n_groups" outside 1..16)."""
+        nh, nl_, G, w, fp, _keep = self._typed_args(nib_hi, nib_lo, weights, flags, "xor_value_groups")
+        self._ensure_keys()
+        tab = self._value_table(*self._unit_value_tables())
+        n_out = max(1, min(G, 16))
+        t, r = (ctypes.c_uint64 * n_out)(), (ctypes.c_uint64 * n_out)()
+        self._ctx.check(self._lib.aesfhe_xor_value_groups(self._ctx.ptr, tab.handle, self._power_handles(a_hi), self._power_handles(a_lo),
+                                                          nh, nl_, int(nh.size), G, w, fp, t, r))
+        return [(Ciphertext(self._ctx, t[g]), Ciphertext(self._ctx, r[g])) for g in range(G)]
+
+    def debug_xor_value_groups_pt(self, nib_hi, nib_lo, weights, flags, level: int):
+        """tests: (rows, scale) -- the G x 16 coefficient plaintexts xor_value_groups multiplies by at `level` as
+        (G, 16, nl(level), N) uint32 in NTT form (debug_xor_value_typed_pt's order), and their scale"""
+        nh, nl_, G, w, fp, _keep = self._typed_args(nib_hi, nib_lo, weights, flags, "debug_xor_value_groups_pt")
+        self._ensure_keys()
+        tab = self._value_table(*self._unit_value_tables())
+        out = np.zeros((max(1, min(G, 16)), 16, self.nl(level), self.n), np.uint32)
+        scale = ctypes.c_double(0.0)
+        self._ctx.check(self._lib.aesfhe_debug_xor_value_groups_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), G, w, fp, int(level),
+                                                                   out, ctypes.byref(scale)))
         return out, scale.value
 
     @staticmethod

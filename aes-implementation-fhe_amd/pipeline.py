@@ -49,7 +49,8 @@ Real-valued slots (xor_value_lut.py): ``transcipher_values`` /
 state slots hold gain * byte as real numbers (read back by ``encoder.decode_values``) instead of the Zeta16 pair -- the
 last public XOR of counter mode fused with the value decode, no renorm after the keystream.  ``dtype`` / ``gain`` /
 ``offset`` read the bytes as int8 / uint8 or 16-bit words of either sign and byte order, with per-word
-gains and offsets, for no further level.
+gains and offsets, for no further level.  ``transcipher_linear`` / ``to_linear`` apply a 16 x 16 matrix
+per state to the decoded bytes inside the same step: the matrix's cyclic diagonals as weight groups of the decode.
 
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
 11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
@@ -632,6 +633,37 @@ class AESPipeline:
         check_layout(self.layout, ct_hi, ct_lo)
         typed = self._typed_lut(dtype, gain, offset)
         lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
+        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+
+    # ---------------------------------------------------------------- a linear map fused with the value decode
+    def _linear_lut(self, weight, bias, dtype, in_scale, zero_point):
+        from xor_value_lut import LinearValueLUT
+        return LinearValueLUT(self.ctx, self.encoder.linear_slots(weight, bias, dtype, in_scale, zero_point))
+
+    def transcipher_linear(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys, weight,
+                           bias=0.0, dtype: str = "i1", in_scale=None, zero_point=0):
+        """AES-CTR transciphering with a 16 x 16 LINEAR MAP over the bytes of every block fused into the value decode:
+        transcipher_values' inputs and one layout-tagged output ciphertext, whose slot of byte position i of state b holds
+            y[b, i] = sum_j weight[b, i, j] * (q[b, j] - zero_point[j]) * in_scale + bias[b, i],
+        q the message bytes read as `dtype` ("u1" or "i1"; 16-bit types raise ValueError).  weight: (16, 16) or
+        (states, 16, 16); bias broadcasts to (states, 16); in_scale a scalar (None: 1/256); zero_point a scalar or
+        (16,).  A channel-mixing layer, a short FIR filter, a de-interleave or a dot product over a block costs no
+        plaintext product and no level: the output sits utils.XOR_VALUE_DEPTH = 4 levels below the keystream, as
+        transcipher_values' does (xor_value_lut.LinearValueLUT: the matrix's non-zero cyclic diagonals are weight
+        groups of the decode, rotated together in one batched key switch).  Slots that hold no state hold 0;
+        encoder.decode_values returns (states, 16)."""
+        self._no_pairs("transcipher_linear")
+        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
+        lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
+        ks = self.ctr_keystream(nonce12, counter0, round_keys)
+        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
+
+    def to_linear(self, ct_hi, ct_lo, weight, bias=0.0, dtype: str = "i1", in_scale=None, zero_point=0):
+        """a clean layout-tagged (hi, lo) pair as ONE ciphertext of weight (bytes - zero_point) * in_scale + bias per
+        state (LinearValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair); arguments as transcipher_linear's"""
+        self._no_pairs("to_linear")
+        check_layout(self.layout, ct_hi, ct_lo)
+        lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
         return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
 
     # ---------------------------------------------------------------- decrypt

@@ -148,6 +148,21 @@ class ValueSlots:
         return self.weights.shape[0]
 
 
+class LinearSlots:
+    """StateEncoder.linear_slots' result: weights / flags (G, slots) for the G kept cyclic diagonals of the matrix,
+    the np.roll steps that bring each group onto its output slots, and two per-slot constants: `affine`, the map's
+    own (the bias minus the zero point's share: sum_k roll(w_k * q_slots, steps[k]) + affine is y), and `const`,
+    what the decode adds (affine plus the groups' E_0 terms rotated with them, as ValueSlots.const)"""
+
+    def __init__(self, dtype, weights, flags, const, steps, diagonals, affine):
+        self.dtype, self.weights, self.flags, self.const, self.steps, self.diagonals = dtype, weights, flags, const, steps, diagonals
+        self.affine = affine
+
+    @property
+    def groups(self) -> int:
+        return self.weights.shape[0]
+
+
 def tag_value_dtype(dtype, ct):
     """mark a value ciphertext with the dtype its slots hold (decode_values' default); returns it"""
     try:
@@ -311,6 +326,59 @@ class StateEncoder:
             # E_0 of both nibbles: 16 * 7.5 + 7.5, the signed hi nibble's E_0 is -0.5; rotated with its group
             const += np.roll(weights[j] * (16.0 * (-0.5 if top else 7.5) + 7.5), -j * self.word_distance)
         return ValueSlots(dtype, weights, flags, const, self.word_distance if w > 1 else 0)
+
+    def _position_slots(self, per_position: np.ndarray) -> np.ndarray:
+        """(states, 16) floats indexed by SLOT POSITION (position p of state b: slot p * unit + b) -> the slot vector,
+        0 in every slot that holds no state: _float_slots without the byte order"""
+        grid = np.zeros((16, self.stride), np.float64)
+        grid[:, :self.states] = np.asarray(per_position, np.float64).reshape(self.states, 16).T
+        return np.ascontiguousarray(self.layout.tile(grid.reshape(-1)))
+
+    def linear_slots(self, W, bias=0.0, dtype: str = "i1", in_scale=None, zero_point=0.0) -> "LinearSlots":
+        """The weight groups with which the value decode applies a 16 x 16 matrix to the decoded bytes of every state
+        (xor_value_lut.LinearValueLUT): output byte position i of state b holds
+            y[b, i] = sum_j W[b, i, j] * (q[b, j] - zero_point[j]) * in_scale + bias[b, i],
+        q the block's bytes read as `dtype` ("u1" or "i1").  W: (16, 16) or (states, 16, 16); bias broadcasts to
+        (states, 16); in_scale a scalar (None: 1/256); zero_point a scalar or (16,).
+
+        The diagonal method in slot-position space.  Position p holds byte at[p] (the encoder's own byte map, so the
+        transposed order works), W'[po, pi] = W[at[po], at[pi]], and group k weighs position p's slot by
+        W'[(p - k) % 16, p] * in_scale: what sits at p belongs to output position p - k, so the group is rolled by
+        steps[k] = -k * unit (slot j takes slot j + k unit; the state is 16-unit-periodic, so that is cyclic inside
+        each state).  sum_k roll(X_k, steps[k]) + affine is y.  A diagonal that is zero in every state is dropped
+        (`diagonals` lists the kept k); "i1" flags every state slot (signed hi nibble), as value_slots does."""
+        if self.pairs > 1:
+            raise ValueError("linear_slots: multi-pair batches (pairs > 1) are not supported")
+        w, signed, _ = value_dtype(dtype)
+        if w != 1:
+            raise ValueError(f"linear_slots: the matrix acts on bytes, dtype must be 'u1' or 'i1', got {dtype!r}")
+        W = np.asarray(W, np.float64)
+        if W.shape not in ((16, 16), (self.states, 16, 16)):
+            raise ValueError(f"linear_slots: W must be (16, 16) or ({self.states}, 16, 16), got {W.shape}")
+        W = np.broadcast_to(W, (self.states, 16, 16))
+        scale = 1.0 / 256.0 if in_scale is None else float(in_scale)
+        try:
+            b = np.broadcast_to(np.asarray(bias, np.float64), (self.states, 16))
+            zp = np.broadcast_to(np.asarray(zero_point, np.float64), (16,))
+        except ValueError:
+            raise ValueError(f"linear_slots: bias must broadcast to ({self.states}, 16) and zero_point to (16,)") from None
+        if not (np.all(np.isfinite(W)) and np.all(np.isfinite(b)) and np.all(np.isfinite(zp)) and np.isfinite(scale)):
+            raise ValueError("linear_slots: W, bias, zero_point and in_scale must be finite")
+        at = self._order(np.arange(16, dtype=np.uint8)[None, :])[0].astype(np.int64)  # the byte at slot position p
+        Wp = W[:, at][:, :, at]
+        p = np.arange(16)
+        diag = [Wp[:, (p - k) % 16, p] * scale for k in range(16)]  # (states, 16) per diagonal, by input position
+        keep = [k for k in range(16) if np.any(diag[k])] or [0]
+        weights = np.stack([self._position_slots(diag[k]) for k in keep])
+        state_slots = self._position_slots(np.ones((self.states, 16)))
+        flags = np.tile(state_slots.astype(np.uint8) if signed else np.zeros(self.sc, np.uint8), (len(keep), 1))
+        steps = [-k * self.stride for k in keep]
+        e0 = 16.0 * (-0.5 if signed else 7.5) + 7.5  # E_0 of both nibbles, as value_slots
+        affine = self._float_slots(b - scale * (W @ zp))
+        const = affine.copy()
+        for wk, st in zip(weights, steps):
+            const += np.roll(wk * e0, st)
+        return LinearSlots(dtype, np.ascontiguousarray(weights), np.ascontiguousarray(flags), const, steps, keep, affine)
 
     def values_from_slots(self, slots: np.ndarray, dtype=None) -> np.ndarray:
         """the pure unpacking of decode_values: a slot vector whose word slots hold one real number per word

@@ -19,7 +19,8 @@ utils.XOR_VALUE_DEPTH = 4 levels.  With b = 0 everywhere this is the plain decod
 The last XOR of counter mode has a public operand (the AES ciphertext byte), so transciphering ends here instead of
 in an XOR4, a renorm and a separate decode: AESPipeline.transcipher_values.
 
-TypedValueLUT is the same sum with per-slot weights, a signed top nibble and 16-bit words.
+TypedValueLUT (DESIGN.md §3.21) is the same sum with per-slot weights, a signed top nibble and 16-bit words;
+LinearValueLUT carries a 16 x 16 matrix per state in up to 16 weight groups.
 """
 from typing import Any, Dict
 
@@ -133,17 +134,22 @@ class TypedValueLUT(XorValueLUT):
 
     spec: a state_encoder.ValueSlots (StateEncoder.value_slots((dtype, gain, offset)))."""
 
+    MAX_GROUPS = 2
+
     def __init__(self, ctx, spec):
         super().__init__(ctx, 1.0)  # the unit tables 16 E and E: the weights carry the gain
+        self._set_spec(spec)
+        self.distance = int(spec.distance)
+
+    def _set_spec(self, spec):
         if spec.weights.shape != (spec.groups, self.sc) or spec.flags.shape != spec.weights.shape or spec.const.shape != (self.sc,):
             raise ValueError(f"value spec: per-slot vectors of {self.sc} entries")
-        if not 1 <= spec.groups <= 2:
-            raise ValueError("value spec: one or two weight groups")
+        if not 1 <= spec.groups <= self.MAX_GROUPS:
+            raise ValueError("value spec: one or two weight groups" if self.MAX_GROUPS == 2 else f"value spec: 1..{self.MAX_GROUPS} weight groups")
         self.spec = spec
         self.weights = np.ascontiguousarray(spec.weights, np.float64)
         self.flags = np.ascontiguousarray(spec.flags, np.uint8)
         self.const = np.ascontiguousarray(spec.const, np.float64)  # per slot, unlike XorValueLUT's scalar
-        self.distance = int(spec.distance)
         E, Es = xor_value_table()[:9], xor_value_table(signed=True)[:9]
         self._tabs = (16.0 * E, 16.0 * Es, E)  # hi unsigned, hi signed, lo (the fallback's)
 
@@ -178,3 +184,56 @@ class TypedValueLUT(XorValueLUT):
         if multi is not None:
             return multi([(c, -self.distance) for c in cts])
         return [ctx.rotate(c, -self.distance) for c in cts]
+
+
+class LinearValueLUT(TypedValueLUT):
+    """The value decode with a 16 x 16 linear map over the bytes of every state fused in, for no
+    level beyond XorValueLUT's four.
+
+    §3.21's two weight groups are the diagonal method with two diagonals.  With group k weighing the slot of byte
+    position p by W'[(p - k) % 16, p] * in_scale (StateEncoder.linear_slots), sum_k rotate(X_k, steps[k]) is W applied
+    to the decoded bytes; by linearity that is sum_k rot(R_k) + V + conj(V) + const with V = sum_k rot(T_k).  All
+    rotations of a call go through ONE rotate_multi, the conjugation is the last key switch, and an all-zero diagonal
+    costs nothing: a 3-tap filter is 3 groups.
+
+    spec: a state_encoder.LinearSlots (StateEncoder.linear_slots(W, bias, dtype, in_scale, zero_point))."""
+
+    MAX_GROUPS = 16
+
+    def __init__(self, ctx, spec):
+        XorValueLUT.__init__(self, ctx, 1.0)  # the unit tables: the weights carry the matrix and in_scale
+        self._set_spec(spec)
+        if len(spec.steps) != spec.groups:
+            raise ValueError("linear spec: one rotation step per weight group")
+        self.steps = [int(st) for st in spec.steps]
+
+    def _engine(self, A_hi, A_lo, nib_hi, nib_lo):
+        """[(T_k, R_k)] from Engine.xor_value_groups, or None (_fused)"""
+        return self._fused("xor_value_groups", A_hi, A_lo, nib_hi, nib_lo, self.weights, self.flags if self.flags.any() else None)
+
+    def _rotate_items(self, items):
+        """[rotate(ct, steps)] for all (ct, steps) of the call as one batched key switch where the context has it"""
+        ctx = self.ctx
+        multi = getattr(ctx, "rotate_multi", None)
+        if multi is not None:
+            return list(multi(items))
+        return [ctx.rotate(c, st) for c, st in items]
+
+    def apply_public(self, hi, lo, nib_hi, nib_lo):
+        """ONE ciphertext whose state slots hold W (q - zero_point) * in_scale + bias, q the bytes hi ^ nib_hi,
+        lo ^ nib_lo spell in the spec's dtype, and whose other slots hold 0 -- XOR_VALUE_DEPTH levels below the inputs
+        (XorValueLUT.apply_public's operands)"""
+        ctx = self.ctx
+        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
+        A_hi, A_lo = self._bases(hi, lo)
+        groups = self._engine(A_hi, A_lo, nib_hi, nib_lo)
+        if groups is None:
+            groups = self._loop(A_hi, A_lo, nib_hi, nib_lo)
+        moved = [g for g, st in enumerate(self.steps) if st % self.sc]
+        rot = iter(self._rotate_items([(c, self.steps[g]) for g in moved for c in groups[g]]))
+        T = R = None
+        for g, (t, r) in enumerate(groups):
+            if g in moved:
+                t, r = next(rot), next(rot)
+            T, R = (t, r) if T is None else (ctx.add(T, t), ctx.add(R, r))
+        return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)

@@ -216,6 +216,20 @@ int aesfhe_xor_value_typed(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_ha
  * 16 channels (aesfhe_debug_xor_value_pt's order) after group g - 1's -- and the scale they were encoded at */
 int aesfhe_debug_xor_value_typed_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
                                     int n_groups, const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale);
+/* Linear value decode: aesfhe_xor_value_typed for n_groups G = 1..16 weight groups.  With group k
+ * weighing the slot of byte position p by W[(p - k) mod 16][p] (the k-th cyclic diagonal of a 16 x 16 matrix W, in
+ * slot-position space), sum_k rotate(X_k, k unit) is W applied to the decoded bytes of every state, for no level
+ * beyond the decode's own: the caller rotates out_t[k] and out_r[k], adds, and conjugates once.  Arguments, outputs
+ * (n_groups handle pairs), levels and refusals are aesfhe_xor_value_typed's, with n_groups outside 1..16 refused
+ * ("n_groups").  The groups are walked in chunks of 8: one codec buffer of at most 8 x 16 coefficient plaintexts
+ * and ONE kernel per chunk, which reads every ciphertext word once for all of the chunk's sums. */
+int aesfhe_xor_value_groups(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const aesfhe_handle* a_lo,
+                            const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, int n_groups,
+                            const double* weights, const uint8_t* flags, aesfhe_handle* out_t, aesfhe_handle* out_r);
+/* tests only: the G x 16 coefficient plaintexts aesfhe_xor_value_groups multiplies by at `level` (>= 1), in
+ * aesfhe_debug_xor_value_typed_pt's order, and the scale they were encoded at */
+int aesfhe_debug_xor_value_groups_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                                     int n_groups, const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale);
 /* Releases a value table; fails if `table` is not one.  aesfhe_free also accepts value tables. */
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table);
 /* Deferred evaluation switch, default on: API-level ct x ct products
