@@ -88,6 +88,69 @@ def xor_value_table(signed: bool = False) -> np.ndarray:
     return E
 
 
+BYTE_LUT_Q = tuple(range(-7, 9))  # the lo-side exponents q of byte_value_table, in the order of its q index (q + 7)
+
+
+def _byte_table(f) -> np.ndarray:
+    f = np.asarray(f, np.float64)
+    if f.shape != (256,) or not np.all(np.isfinite(f)):
+        raise ValueError(f"a byte table is 256 finite reals, got shape {f.shape}")
+    return f
+
+
+def byte_value_table(f):
+    """(K, C_00) for a 256-entry real table f (xor_value_lut.ByteValueLUT).  A byte x = 16 x_hi + x_lo
+    with Zeta16 codewords a = ζ16^x_hi, c = ζ16^x_lo and a public byte b = 16 b_hi + b_lo:
+        f(x ⊕ b) = Σ_{p,q<16} C_pq[b] a^p c^q,   C_pq[b] = (1/256) Σ_{k,l<16} f(16 (k ⊕ b_hi) + (l ⊕ b_lo)) ζ16^{-pk-ql}.
+    f is real, so C_(-p,-q) = conj(C_pq): C_00 = mean(f) whatever b is, C_08, C_80 and C_88 are real, and
+        f(x ⊕ b) = C_00 + T + conj(T),   T = Σ_{q=-7..8} y_q U_q,   U_q = Σ_{p=0..8} K_pq[b] a^p,
+    y_q = c^q (q >= 0, y_0 = 1), conj(c^-q) (q < 0).  K[p, q + 7, b] (9 x 16 x 256 complex) holds one of every
+    conjugate pair: K_pq = C_{p, q mod 16} for p = 1..7 and every q; K_0q = C_0q and K_8q = C_8q for q = 1..7; the real
+    self-conjugate C_08, C_88, C_80 enter as halves at (0, 8), (8, 8), (8, 0); every other entry is 0."""
+    f = _byte_table(f)
+    b = np.arange(256)
+    k, l = np.indices((16, 16))
+    g = f[16 * (k[None] ^ (b >> 4)[:, None, None]) + (l[None] ^ (b & 15)[:, None, None])]  # [b][k][l]
+    C = np.moveaxis(np.fft.fft2(g, axes=(1, 2)) / 256.0, 0, -1)  # fft's e^(-2 pi i pk / 16) is ζ16^(pk): C[p][q][b]
+    C = C[(-np.arange(16)) % 16][:, (-np.arange(16)) % 16]       # ... so index (p, q) -> (-p, -q)
+    K = np.zeros((9, 16, 256), np.complex128)
+    for qi, q in enumerate(BYTE_LUT_Q):
+        K[1:8, qi] = C[1:8, q % 16]
+        if 1 <= q <= 7:
+            K[0, qi], K[8, qi] = C[0, q], C[8, q]
+    K[0, 8 + 7] = 0.5 * C[0, 8].real
+    K[8, 8 + 7] = 0.5 * C[8, 8].real
+    K[8, 0 + 7] = 0.5 * C[8, 0].real
+    return K, float(C[0, 0, 0].real)
+
+
+def byte_value_eval(K, c00, b, a, c):
+    """C_00 + T + conj(T) of byte_value_table's K at public bytes b and (possibly perturbed) codewords a, c"""
+    b = np.asarray(b)
+    T = 0.0
+    for qi, q in enumerate(BYTE_LUT_Q):
+        y = c ** q if q >= 0 else np.conj(c ** -q)
+        T = T + y * sum(K[p, qi, b] * a ** p for p in range(9))
+    return c00 + T + np.conj(T)
+
+
+def byte_value_sensitivity(f, eps: float = 1e-4) -> float:
+    """max |F(perturbed) - f| / eps over all bytes x (public byte 0) and the four sign combinations, F the formula of
+    byte_value_table with both codewords perturbed to ζ16^k e^(+-i eps) (1 +- eps): how much the decode amplifies a
+    codeword error, per unit of it (§3.20's 930 figure for the byte value, in table units)"""
+    f = _byte_table(f)
+    K, c00 = byte_value_table(f)
+    x = np.arange(256)
+    zero = np.zeros(256, np.int64)
+    worst = 0.0
+    for sa in (1.0, -1.0):
+        for sr in (1.0, -1.0):
+            d = np.exp(1j * sa * eps) * (1.0 + sr * eps)
+            F = byte_value_eval(K, c00, zero, _zeta(16) ** (x >> 4) * d, _zeta(16) ** (x & 15) * d)
+            worst = max(worst, float(np.abs(F - f).max()))
+    return worst / eps
+
+
 def _entries_1d(a, tol):
     return [[int(k), float(c.real), float(c.imag)] for k, c in enumerate(a) if abs(c) > tol]
 

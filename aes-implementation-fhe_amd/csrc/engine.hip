@@ -161,6 +161,12 @@ struct ValueTab {
     double mag_t = 0.0, mag_r = 0.0;  // sum over T's / R's channels of max_b |E_p[b]|
 };
 
+// the byte-table decode's coefficient table: K[p][q + 7][b], [9][16][256] complex double on the device
+struct ByteTab {
+    std::pair<u32*, size_t> tab{nullptr, 0};
+    double mag[kByteLutGroups] = {};  // per group q: sum_p max_b |K_pq[b]|
+};
+
 struct Pt {
     std::vector<double> re, im;
     bool constant = false;
@@ -326,6 +332,12 @@ public:
         if (iv != vtabs_.end()) {
             give_back(iv->second.tab.first, iv->second.tab.second);
             vtabs_.erase(iv);
+            return;
+        }
+        auto ib = btabs_.find(h);
+        if (ib != btabs_.end()) {
+            give_back(ib->second.tab.first, ib->second.tab.second);
+            btabs_.erase(ib);
             return;
         }
         auto ip = pts_.find(h);
@@ -2043,6 +2055,161 @@ public:
                               const uint8_t* flags, int level, u32* out, double* scale) {
         typed_args("debug_xor_value_typed_pt", hv, G, weights);
         debug_value_rows("debug_xor_value_typed_pt", "xor_value_typed", hv, nib_hi, nib_lo, n_slots, G, weights, flags, level, out, scale);
+    }
+
+    // ------------------------------------------------------------------ a 256-entry byte table fused with the value decode
+    // f(x ^ b) = C_00 + T + conj(T), T = sum_{q = -7..8} y_q U_q, U_q = sum_{p = 0..8} K_pq[b] a^p: the engine forms the
+    // 16 sums U_q (ciphertext x per-slot plaintext, the p = 0 column a plaintext added inside the sum); the ct x ct
+    // products with the lo-side operands y_q and the conjugation are the caller's.  K (made by Python,
+    // coeffgen.byte_value_table) is uploaded once, waiting for its copy once as value_create does
+    aesfhe_handle byte_lut_create(const double* re, const double* im) {
+        if (!re || !im) throw std::runtime_error("byte_lut_create: missing table");
+        ByteTab B;
+        const size_t n = (size_t)kByteLutRows * kByteLutGroups * 256;
+        std::vector<double> h(2 * n);
+        for (int p = 0; p < kByteLutRows; ++p)
+            for (int q = 0; q < kByteLutGroups; ++q) {
+                double top = 0.0;
+                for (int b = 0; b < 256; ++b) {
+                    const size_t c = ((size_t)p * kByteLutGroups + q) * 256 + b;
+                    if (!std::isfinite(re[c]) || !std::isfinite(im[c])) throw std::runtime_error("byte_lut_create: table entry not finite");
+                    h[2 * c] = re[c], h[2 * c + 1] = im[c];
+                    top = std::max(top, std::hypot(re[c], im[c]));
+                }
+                B.mag[q] += top;
+            }
+        ensure_slot_pos();
+        const size_t words = (2 * h.size() + (size_t)hp_.n - 1) / hp_.n * hp_.n;
+        u32* d = alloc_words(words);
+        HIP_OK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, S()));
+        HIP_OK(hipStreamSynchronize(S()));  // cached for every stream; host vector dies here
+        B.tab = {d, words};
+        const aesfhe_handle hd = next_++;
+        btabs_.emplace(hd, B);
+        return hd;
+    }
+    const ByteTab& btab(aesfhe_handle h) const {
+        auto it = btabs_.find(h);
+        if (it == btabs_.end()) throw std::runtime_error("invalid byte table handle");
+        return it->second;
+    }
+    void free_byte_lut(aesfhe_handle h) {
+        if (!btabs_.count(h)) throw std::runtime_error("aesfhe_byte_lut_free: not a byte table handle");
+        free_handle(h);
+    }
+    struct ByteStage {
+        const uint8_t* nib = nullptr;  // both nibble arrays, hi then lo
+        const double* wt = nullptr;    // [slots]
+        double top = 0.0;              // max |w|
+    };
+    // nibbles and weights checked and copied into this stream's staging buffer (its own) in ONE copy: s doubles, then
+    // 2 s nibble bytes
+    ByteStage stage_byte_lut(const std::string& who, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, const double* weights) {
+        const int s = slot_count();
+        need_slots(who, nib_hi && nib_lo && n_slots == s);
+        if (!weights) throw std::runtime_error(who + ": missing weights");
+        const size_t o_nib = (size_t)s * sizeof(double), bytes = o_nib + (size_t)2 * s;
+        std::vector<uint8_t>& h = h_blut_[t_sidx];
+        h.resize(bytes);
+        ByteStage st;
+        for (int j = 0; j < s; ++j) {
+            if (!std::isfinite(weights[j])) throw std::runtime_error(who + ": weight not finite at slot " + std::to_string(j));
+            st.top = std::max(st.top, std::fabs(weights[j]));
+        }
+        std::memcpy(h.data(), weights, o_nib);
+        copy_nibbles(who, nib_hi, h.data() + o_nib);
+        copy_nibbles(who, nib_lo, h.data() + o_nib + s);
+        if (!d_blut_[t_sidx]) d_blut_[t_sidx] = (uint8_t*)dev_alloc((bytes + 3) / 4);
+        uint8_t* d = d_blut_[t_sidx];
+        HIP_OK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, S()));
+        st.wt = (const double*)d;
+        st.nib = d + o_nib;
+        return st;
+    }
+    // one chunk's product plaintexts: channel g kByteLutTerms + (p - 1) holds w K_pq[b] for group q index g0 + g and
+    // p = 1..8, at `scale`, 16 channels (two groups) per codec pass.  gc x 8 x nl rows (tmp)
+    u32* byte_lut_encode(const ByteTab& B, const ByteStage& st, int g0, int gc, double scale, int nl) {
+        static_assert(kValueCh == 2 * kByteLutTerms, "two groups per codec pass");
+        if (gc % 2) throw std::runtime_error("byte_lut_encode: an even number of groups");
+        return encode_channels(gc / 2, kValueCh, scale, nl, [&](int pass, double* w) {
+            ByteLutSlotArgs ch;
+            for (int c = 0; c < kValueCh; ++c) ch.row[c] = ((c % kByteLutTerms) + 1) * kByteLutGroups + g0 + 2 * pass + c / kByteLutTerms;
+            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, kValueCh, st.nib, st.wt, d_slot_pos_);
+        });
+    }
+    // one chunk's fills: channel g holds w K_0q[b] for group q index g0 + g at `scale` (the product scale of the sum
+    // it joins, as pt_fill_at's).  gc x nl rows (tmp)
+    u32* byte_lut_fills(const ByteTab& B, const ByteStage& st, int g0, int gc, double scale, int nl) {
+        return encode_channels(1, gc, scale, nl, [&](int, double* w) {
+            ByteLutSlotArgs ch;
+            for (int c = 0; c < gc; ++c) ch.row[c] = g0 + c;
+            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, gc, st.nib, st.wt, d_slot_pos_);
+        });
+    }
+    // out[q + 7] = U_q = sum_{p = 1..8} w K_pq[b] (.) a^p + (w K_0q[b] as a plaintext) for q = -7..8.  A_hi is indexed by
+    // the power p (entry 0 unused), the operands canonical and dropped exactly to their common lowest logical level l
+    // as value_decode's; the 16 groups are walked in chunks of kByteLutChunk: one bounded codec buffer and ONE
+    // k_byte_lut_mac launch per chunk, every chunk reading the same canonical operands.  The fill is encoded at
+    // ct scale x ptscale[l] = raw_scale(l, 1), the scale of the sums before their owed rescale
+    void byte_lut_public(aesfhe_handle hb, const aesfhe_handle* A_hi, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                         const double* weights, Ct* oU) {
+        const std::string who = "byte_lut_public";
+        const ByteTab& B = btab(hb);
+        if (!A_hi) throw std::runtime_error(who + ": missing element handles");
+        aesfhe_handle A[kByteLutTerms];
+        for (int t = 0; t < kByteLutTerms; ++t) A[t] = A_hi[t + 1];
+        const int l = public_operands(who, "byte table decode", A, kByteLutTerms);
+        const ByteStage st = stage_byte_lut(who, nib_hi, nib_lo, n_slots, weights);
+        const int nl = hp_.nl(l);
+        Ct out[kByteLutGroups];
+        public_op([&](PubTemps& s) {
+            ByteLutMacArgs a;
+            operands_at(A, kByteLutTerms, l, a.a, s.own);
+            cnt_[C_PTMUL] += (kByteLutGroups - 1) * kByteLutTerms;  // every group multiplies every operand
+            cnt_[C_ADD] += kByteLutGroups;                           // the fills
+            for (int g0 = 0; g0 < kByteLutGroups; g0 += kByteLutChunk) {
+                const int gc = kByteLutChunk;
+                s.mrows = (size_t)gc * nl;
+                s.m = byte_lut_fills(B, st, g0, gc, raw_scale(l, 1), nl);
+                const size_t prows = (size_t)gc * kByteLutTerms * nl;
+                u32* pm = byte_lut_encode(B, st, g0, gc, hp_.ptscale[l], nl);
+                try {
+                    for (int g = 0; g < gc; ++g) s.res.push_back(out[g0 + g] = alloc_ct(l, 2)), a.out[g] = out[g0 + g].data;
+                    launch_byte_lut_mac(S(), T_, a, gc, kByteLutTerms, pm, s.m, nl, qmap());
+                } catch (...) {
+                    untmp(pm, prows);
+                    throw;
+                }
+                untmp(pm, prows);
+                untmp(s.m, s.mrows), s.m = nullptr;
+            }
+            for (int g = 0; g < kByteLutGroups; ++g) owe_rescale(out[g], s.res[g], B.mag[g] * st.top, s.own);
+        });
+        for (int g = 0; g < kByteLutGroups; ++g) oU[g] = out[g];
+    }
+    // tests: the 16 x 9 encoded rows -- group q index g, then p = 0 (the fill, at scales[1]) and p = 1..8 (at
+    // scales[0]) -- of nl(level) limbs each, encoded chunk by chunk as byte_lut_public does
+    void debug_byte_lut_pt(aesfhe_handle hb, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, const double* weights, int level,
+                           u32* out, double* scales) {
+        const ByteTab& B = btab(hb);
+        debug_args("debug_byte_lut_pt", level, out, scales);
+        const ByteStage st = stage_byte_lut("byte_lut_public", nib_hi, nib_lo, n_slots, weights);
+        const int nl = hp_.nl(level);
+        const size_t row = (size_t)nl * hp_.n;
+        std::vector<u32> hf((size_t)kByteLutChunk * row), hp((size_t)kByteLutChunk * kByteLutTerms * row);
+        double sc = 0.0;
+        for (int g0 = 0; g0 < kByteLutGroups; g0 += kByteLutChunk) {
+            read_rows(byte_lut_fills(B, st, g0, kByteLutChunk, raw_scale(level, 1), nl), (size_t)kByteLutChunk * nl, level, hf.data(), &sc);
+            read_rows(byte_lut_encode(B, st, g0, kByteLutChunk, hp_.ptscale[level], nl), (size_t)kByteLutChunk * kByteLutTerms * nl, level,
+                      hp.data(), &sc);
+            for (int g = 0; g < kByteLutChunk; ++g) {
+                u32* o = out + (size_t)(g0 + g) * kByteLutRows * row;
+                std::memcpy(o, hf.data() + (size_t)g * row, row * sizeof(u32));
+                std::memcpy(o + row, hp.data() + (size_t)g * kByteLutTerms * row, kByteLutTerms * row * sizeof(u32));
+            }
+        }
+        scales[0] = hp_.ptscale[level];
+        scales[1] = raw_scale(level, 1);
     }
 
     // ------------------------------------------------------------------ key switching
@@ -5679,6 +5846,7 @@ private:
     CrtConsts crt_[4] = {};
     std::unordered_map<aesfhe_handle, Lut> luts_;
     std::unordered_map<aesfhe_handle, ValueTab> vtabs_;
+    std::unordered_map<aesfhe_handle, ByteTab> btabs_;
     Slot16 slots_ = {};    // the reference layout's 16 state slots, 5^(i N/32)
     Slot32 slots32_ = {};  // the first 32 slots, 5^j (the packed period-32 form)
     // AESFHE_RENORM_DIRECT32=0: the packed renorms through the FFT codec (A/B runs)
@@ -5693,6 +5861,8 @@ private:
     uint8_t* d_val_[kStreams] = {};        // the value decode: weights, both nibble arrays, flags (stage_value)
     uint8_t* d_val_wide_[kStreams] = {};   // the same for more than kValueGroups groups (xor_value_groups)
     std::vector<uint8_t> h_val_[kStreams];  // their host staging copy
+    uint8_t* d_blut_[kStreams] = {};        // the byte-table decode: weights, then both nibble arrays (stage_byte_lut)
+    std::vector<uint8_t> h_blut_[kStreams];  // their host staging copy
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;
@@ -5953,6 +6123,30 @@ int aesfhe_debug_xor_value_groups_pt(aesfhe_ctx* ctx, aesfhe_handle table, const
 }
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table) {
     API_BEGIN ctx->eng->free_value(table);
+    API_END
+}
+int aesfhe_byte_lut_create(aesfhe_ctx* ctx, const double* re, const double* im, aesfhe_handle* out) {
+    API_BEGIN
+    if (!out) throw std::runtime_error("byte_lut_create: missing output handle");
+    *out = ctx->eng->byte_lut_create(re, im);
+    API_END
+}
+int aesfhe_byte_lut_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                           int n_slots, const double* weights, aesfhe_handle* out) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out) throw std::runtime_error("byte_lut_public: missing output handles");
+    Ct u[kByteLutGroups];
+    e.byte_lut_public(table, a_hi, nib_hi, nib_lo, n_slots, weights, u);
+    for (int g = 0; g < kByteLutGroups; ++g) out[g] = e.put_ct(u[g]);
+    API_END
+}
+int aesfhe_debug_byte_lut_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                             const double* weights, int level, uint32_t* out, double* scales) {
+    API_BEGIN ctx->eng->debug_byte_lut_pt(table, nib_hi, nib_lo, n_slots, weights, level, out, scales);
+    API_END
+}
+int aesfhe_byte_lut_free(aesfhe_ctx* ctx, aesfhe_handle table) {
+    API_BEGIN ctx->eng->free_byte_lut(table);
     API_END
 }
 int aesfhe_set_enc_nonce(aesfhe_ctx* ctx, uint64_t nonce) {

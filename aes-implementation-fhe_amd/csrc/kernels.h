@@ -655,3 +655,30 @@ struct ValueChunkOut {
 };
 void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunkOut& out, int groups, const ValueMacArgs& a, int n,
                             const u32* pt, int nl, LimbMap map);
+
+// --- a 256-entry byte table fused with the value decode --------------------------
+// f(x ^ b) of a Zeta16 byte (a, c) with b public is C_00 + T + conj(T), T = sum_q y_q U_q over the 16 lo-side
+// operands y_q and U_q = sum_{p = 0..8} K_pq[b] a^p: per-slot plaintext coefficients again, gathered from ONE table of
+// kByteLutRows x 16 rows of 256 complex doubles at the slot's public BYTE.  launch_byte_lut_slots writes the codec's
+// FFT input: channel c takes row row[c] of the table,  w[c][slot j] = wt[j] * tab[row[c]][16 nib[j] + nib[N/2 + j]],
+// in launch_value_slots_typed's output order (nib: the hi array, then the lo array).
+constexpr int kByteLutRows = 9;    // p = 0..8
+constexpr int kByteLutGroups = 16;  // q = -7..8
+constexpr int kByteLutTerms = 8;    // the ciphertext powers a^1..a^8 of one sum
+constexpr int kByteLutChunk = 8;    // groups per MAC launch and codec buffer
+struct ByteLutSlotArgs {
+    int row[kValueCh] = {};
+};
+void launch_byte_lut_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ByteLutSlotArgs& ch, int nch,
+                           const uint8_t* nib, const double* wt, const u32* slot_pos);
+// out[g] = sum_{t < n} a[t] (.) pt[g kByteLutTerms + t] + fill[g] (c0 only) for `groups` sums in ONE launch: every
+// ciphertext word is read once and multiplied into all groups, `groups` 64-bit sums in registers, the fill word (a
+// residue, < 2^30) added before the one reduction.  pt: groups x kByteLutTerms channels of nl limbs, fill: groups
+// channels of nl limbs, NTT form.  n products and the fill may not exceed 15 terms (64-bit sums of 60-bit products).
+// gfx950 (k_byte_lut_mac<G>): see DESIGN.md §3.23 for the register table
+struct ByteLutMacArgs {
+    const u32* a[kByteLutTerms] = {};
+    u32* out[kByteLutChunk] = {};
+};
+void launch_byte_lut_mac(hipStream_t st, const DevTables& T, const ByteLutMacArgs& a, int groups, int n, const u32* pt, const u32* fill, int nl,
+                         LimbMap map);

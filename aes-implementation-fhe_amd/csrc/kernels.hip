@@ -163,6 +163,29 @@ __global__ void k_value_typed_mac(Out o, ValueMacArgs a, int n, const u32* pt, i
         o.r[g][idx] = reduce64(accR[g], P.q, P.mu, P.r32);
     }
 }
+// a.out[g] = sum_{t < n} a_t (.) pt[g kByteLutTerms + t] (+ fill[g] on c0's rows) for G sums over the same n <=
+// kByteLutTerms ciphertexts (the byte-table decode's U_q, launch_byte_lut_mac).  Each ciphertext word
+// is loaded once and multiplied into all G groups; G is a template argument, so the group loop unrolls and the G
+// 64-bit sums stay in registers.  The fill is a plaintext at the product scale: its residue (< 2^30) joins the sum
+// before the one reduction -- 8 products below 2^60 and the fill stay below 15 x 2^60 < 2^64 (the launcher checks).
+// Rows >= nl are c1's: block-uniform, so the fill read is a uniform branch
+template <int G>
+__global__ void k_byte_lut_mac(ByteLutMacArgs a, int n, const u32* pt, const u32* fill, int nl, LimbMap map, const PrimeConst* pc, int logn) {
+    EW_PROLOGUE
+    const size_t pidx = ((size_t)limb << logn) + k, chan = (size_t)nl << logn;
+    u64 acc[G] = {};
+    for (int t = 0; t < n; ++t) {
+        const u64 c = a.a[t][idx];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] += c * pt[(size_t)(g * kByteLutTerms + t) * chan + pidx];
+    }
+    if (row < nl) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] += fill[(size_t)g * chan + pidx];
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) a.out[g][idx] = reduce64(acc[g], P.q, P.mu, P.r32);
+}
 __global__ void k_tensor(u32* out, const u32* a, const u32* b, int nl, LimbMap map, const PrimeConst* pc, int logn) {
     // row = m * nl + limb: ciphertext m of a stacked batch ([m][2][nl] in, [m][3][nl] out)
     const int row = blockIdx.y;
@@ -1399,6 +1422,27 @@ __global__ void __launch_bounds__(kBlock) k_value_slots_typed(double2* w, const 
     wc[n - 1 - t] = make_double2(v.x, -v.y);
 }
 
+// the byte-table decode's codec input (launch_byte_lut_slots): k_value_slots_typed over ONE table of
+// 256-column rows.  Channel c takes row a.row[c] at the slot's public byte 16 nib_hi + nib_lo (the two nibble arrays
+// of N/2 bytes back to back), times the slot's weight.  The map is a kernel argument: uniform per block, read by the
+// scalar unit.  One lane per slot, both nibbles and the weight read coalesced; the 4 KiB rows are gathered through
+// L1 / L2 (a launch reads at most 16 of them)
+__global__ void __launch_bounds__(kBlock) k_byte_lut_slots(double2* w, const double2* tab, ByteLutSlotArgs a, const uint8_t* nib,
+                                                           const double* wt, const u32* slot_pos, int logn) {
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
+    const int n = 1 << logn;
+    if (j >= n / 2) return;
+    const u32 b = ((u32)(nib[j] & 15) << 4) | (u32)(nib[(size_t)(n / 2) + j] & 15);
+    const double2 e = tab[(size_t)a.row[c] * 256 + b];
+    const double wj = wt[j];
+    const double2 v = make_double2(e.x * wj, e.y * wj);
+    const u32 t = slot_pos[j];
+    double2* wc = w + ((size_t)c << logn);
+    wc[t] = v;
+    wc[n - 1 - t] = make_double2(v.x, -v.y);
+}
+
 // ------------------------------------------------------------------------------------
 // fused LUT evaluation: one launch per LUT instead of a tensor + constant + add per term
 // ------------------------------------------------------------------------------------
@@ -2361,4 +2405,29 @@ void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunk
     if (nr > 15 || n - nr > 15) throw std::runtime_error("launch_value_chunk_mac: at most 15 terms per sum");
     // reads: n ciphertexts and groups x n plaintext channels; writes: 2 x groups ciphertexts
     value_chunk_mac<kValueChunk>(st, T, 2.0 * nl * (n + 2 * groups) + (double)groups * n * nl, out, groups, a, n, pt, nl, map);
+}
+void launch_byte_lut_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ByteLutSlotArgs& ch, int nch,
+                           const uint8_t* nib, const double* wt, const u32* slot_pos) {
+    if (nch < 1 || nch > kValueCh || !w || !tab || !nib || !wt || !slot_pos) throw std::runtime_error("launch_byte_lut_slots: 1..16 channels");
+    for (int c = 0; c < nch; ++c)
+        if (ch.row[c] < 0 || ch.row[c] >= tab_rows) throw std::runtime_error("launch_byte_lut_slots: bad channel map");
+    const double s = (double)(1u << (T.logn - 1));
+    const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
+    // reads: two nibbles, the weight, the slot position and one table entry; writes: two complex doubles
+    prof_launch(KID_ELEMENTWISE, nch * (2.0 * s + 8.0 * s + 4.0 * s + 16.0 * s + 32.0 * s), k_byte_lut_slots, dim3(gx, nch), dim3(kBlock), 0, st,
+                (double2*)w, (const double2*)tab, ch, nib, wt, slot_pos, T.logn);
+}
+void launch_byte_lut_mac(hipStream_t st, const DevTables& T, const ByteLutMacArgs& a, int groups, int n, const u32* pt, const u32* fill, int nl,
+                         LimbMap map) {
+    if (groups != kByteLutChunk) throw std::runtime_error("launch_byte_lut_mac: 8 groups per launch");
+    if (n < 1 || n > kByteLutTerms || !pt || !fill) throw std::runtime_error("launch_byte_lut_mac: 1..8 ciphertexts, plaintexts and fills");
+    if (n + 1 > 15) throw std::runtime_error("launch_byte_lut_mac: at most 15 terms per sum");
+    for (int t = 0; t < n; ++t)
+        if (!a.a[t]) throw std::runtime_error("launch_byte_lut_mac: bad operand");
+    for (int g = 0; g < groups; ++g)
+        if (!a.out[g]) throw std::runtime_error("launch_byte_lut_mac: missing output");
+    // reads: n ciphertexts, groups x n plaintext channels and groups fill channels; writes: groups ciphertexts
+    const double bytes = 2.0 * nl * (n + groups) + (double)groups * (n + 1) * nl;
+    prof_launch(KID_ELEMENTWISE, EW_BYTES(bytes), k_byte_lut_mac<kByteLutChunk>, ew_grid(T.logn, 2 * nl), dim3(kBlock), 0, st, a, n, pt, fill, nl, map,
+                T.pc, T.logn);
 }

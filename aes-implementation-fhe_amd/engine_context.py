@@ -445,3 +445,9 @@ class EngineContext:
         to the decoded bytes -- in one engine call (Engine.xor_value_groups).  Modules test for it
         with getattr(ctx, "xor_value_groups", None)."""
         return self.engine.xor_value_groups(a_hi, a_lo, nib_hi, nib_lo, weights, flags)
+
+    def byte_lut_public(self, a_hi, nib_hi, nib_lo, K, weights):
+        """[U_q for q = -7..8]: the 16 hi-side sums of a 256-entry byte table's value decode at a public byte per slot,
+        the p = 0 column added as a plaintext inside each sum -- one engine call (DESIGN.md §3.23;
+        Engine.byte_lut_public).  Modules test for it with getattr(ctx, "byte_lut_public", None)."""
+        return self.engine.byte_lut_public(a_hi, nib_hi, nib_lo, K, weights)

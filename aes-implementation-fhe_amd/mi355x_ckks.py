@@ -13,6 +13,7 @@ from __future__ import annotations
 import concurrent.futures
 import os
 import ctypes
+import hashlib
 import threading
 import numbers
 from pathlib import Path
@@ -53,6 +54,7 @@ EXPORTED = [
     "aesfhe_xor_value_create", "aesfhe_xor_value_public", "aesfhe_debug_xor_value_pt", "aesfhe_xor_value_free",
     "aesfhe_xor_value_typed", "aesfhe_debug_xor_value_typed_pt",
     "aesfhe_xor_value_groups", "aesfhe_debug_xor_value_groups_pt",
+    "aesfhe_byte_lut_create", "aesfhe_byte_lut_public", "aesfhe_debug_byte_lut_pt", "aesfhe_byte_lut_free",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -157,6 +159,10 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_debug_xor_value_typed_pt"] = [vp, _H, _bp, _bp, c_int, c_int, vp, vp, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_xor_value_groups"] = sig["aesfhe_xor_value_typed"]
     sig["aesfhe_debug_xor_value_groups_pt"] = sig["aesfhe_debug_xor_value_typed_pt"]
+    sig["aesfhe_byte_lut_create"] = sig["aesfhe_xor_value_create"]
+    sig["aesfhe_byte_lut_public"] = [vp, _H, _Hp, _bp, _bp, c_int, vp, _Hp]
+    sig["aesfhe_debug_byte_lut_pt"] = [vp, _H, _bp, _bp, c_int, vp, c_int, _up, ctypes.POINTER(c_dbl)]
+    sig["aesfhe_byte_lut_free"] = [vp, _H]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -275,6 +281,12 @@ class LookupTable(_Handle):
 
 class ValueTable(_Handle):
     """The two 9 x 16 coefficient tables of the public value decode on the device (aesfhe_xor_value_create)."""
+
+    __slots__ = ()
+
+
+class ByteTable(_Handle):
+    """The 9 x 16 x 256 coefficient table of the byte-table decode on the device (aesfhe_byte_lut_create)."""
 
     __slots__ = ()
 
@@ -400,6 +412,7 @@ class Engine:
         self.defer = bool(defer_calls)
         self._defer_luts = {}
         self._value_tables = {}  # xor_value_public: table bytes -> ValueTable (uploaded once)
+        self._byte_tables = {}   # byte_lut_public: digest of the table bytes -> ByteTable (uploaded once)
 
     # ------------------------------------------------------------------ concurrency
     def _executor(self):
@@ -1232,6 +1245,56 @@ class Engine:
         self._ctx.check(self._lib.aesfhe_debug_xor_value_groups_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), G, w, fp, int(level),
                                                                    out, ctypes.byref(scale)))
         return out, scale.value
+
+    def _byte_table(self, K) -> ByteTable:
+        """the device copy of a byte-table decode's K (coeffgen.byte_value_table), uploaded once per table"""
+        t = np.ascontiguousarray(np.asarray(K, np.complex128))
+        if t.shape != (9, 16, 256):
+            raise ValueError(f"byte_lut_public: a (9, 16, 256) complex table, got {t.shape}")
+        cache, key = self._byte_tables, hashlib.sha256(t.tobytes()).digest()
+        if key not in cache:
+            h = ctypes.c_uint64()
+            self._ctx.check(self._lib.aesfhe_byte_lut_create(self._ctx.ptr, np.ascontiguousarray(t.real), np.ascontiguousarray(t.imag),
+                                                             ctypes.byref(h)))
+            cache[key] = ByteTable(self._ctx, h.value)
+        return cache[key]
+
+    def _byte_lut_args(self, nib_hi, nib_lo, weights, what):
+        nh, nl_ = self._nibble_array(nib_hi), self._nibble_array(nib_lo)
+        if nh.size != nl_.size:
+            raise ValueError(f"{what}: the two nibble arrays differ in length")
+        if weights is None:  # the engine refuses a null pointer ("missing weights")
+            return nh, nl_, None, None
+        w = np.ascontiguousarray(np.asarray(weights, np.float64))
+        if w.shape != (nh.size,):
+            raise ValueError(f"{what}: weights must be ({nh.size},), got {w.shape}")
+        return nh, nl_, w.ctypes.data_as(ctypes.c_void_p), w
+
+    def byte_lut_public(self, a_hi, nib_hi, nib_lo, K, weights):
+        """[U_q for q = -7..8] of the byte-table decode (aesfhe_byte_lut_public):
+        U_q = sum_{p = 0..8} weights * K[p, q + 7, 16 nib_hi + nib_lo] * hi^p per slot, the p = 0 column added as a
+        plaintext inside the sum.  a_hi: the powers {p: hi^p} for p = 1..8; nib_*: contiguous uint8 arrays of
+        slot_count entries < 16; K: (9, 16, 256) complex (uploaded once per table); weights: (slot_count,) float64,
+        finite.  Each output sits at the powers' common lowest level, owing its rescale.  Errors as
+        xor_value_public's, plus "weight"."""
+        nh, nl_, w, _keep = self._byte_lut_args(nib_hi, nib_lo, weights, "byte_lut_public")
+        self._ensure_keys()
+        tab = self._byte_table(K)
+        out = (ctypes.c_uint64 * 16)()
+        self._ctx.check(self._lib.aesfhe_byte_lut_public(self._ctx.ptr, tab.handle, self._power_handles(a_hi), nh, nl_, int(nh.size), w, out))
+        return [Ciphertext(self._ctx, out[g]) for g in range(16)]
+
+    def debug_byte_lut_pt(self, nib_hi, nib_lo, K, weights, level: int):
+        """tests: (rows, scale, fill_scale) -- the 16 x 9 coefficient plaintexts byte_lut_public uses at `level` as
+        (16, 9, nl(level), N) uint32 in NTT form: group q + 7, then p = 0 (the fill, encoded at fill_scale) and
+        p = 1..8 (at scale)"""
+        nh, nl_, w, _keep = self._byte_lut_args(nib_hi, nib_lo, weights, "debug_byte_lut_pt")
+        self._ensure_keys()
+        tab = self._byte_table(K)
+        out = np.zeros((16, 9, self.nl(level), self.n), np.uint32)
+        scales = (ctypes.c_double * 2)()
+        self._ctx.check(self._lib.aesfhe_debug_byte_lut_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), w, int(level), out, scales))
+        return out, scales[0], scales[1]
 
     @staticmethod
     def _unit_value_tables():

@@ -51,6 +51,8 @@ last public XOR of counter mode fused with the value decode, no renorm after the
 ``offset`` read the bytes as int8 / uint8 or 16-bit words of either sign and byte order, with per-word
 gains and offsets, for no further level.  ``transcipher_linear`` / ``to_linear`` apply a 16 x 16 matrix
 per state to the decoded bytes inside the same step: the matrix's cyclic diagonals as weight groups of the decode.
+``transcipher_lut`` / ``to_lut`` put an arbitrary 256-entry table of the byte in the slots instead, for
+one ct x ct level more.
 
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
 11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
@@ -72,7 +74,7 @@ from key_expansion import EncryptedRoundKeys, KeyExpansion
 from inv_shiftrows import InvShiftRows
 from mixcol_final import MixColFinal
 from shift_rows import ShiftRows
-from state_encoder import StateEncoder, check_layout, tag_layout, tag_value_dtype
+from state_encoder import LUT_VALUE_TAG, StateEncoder, check_layout, tag_layout, tag_value_dtype
 from shift_rows import shift_rows_bytes
 from shiftrows_mixcolumns import ShiftRowsMixColumnsFusedEnc
 from sub_bytes_ark import SubBytesARK
@@ -665,6 +667,38 @@ class AESPipeline:
         check_layout(self.layout, ct_hi, ct_lo)
         lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
         return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+
+    # ---------------------------------------------------------------- a 256-entry byte table fused with the value decode
+    def _byte_lut(self, table, gain):
+        from xor_value_lut import ByteValueLUT
+        t = np.asarray(table, np.float64)
+        if t.shape != (256,):
+            raise ValueError(f"byte table: 256 reals, got shape {t.shape}")
+        return ByteValueLUT(self.ctx, t, self.encoder.lut_slots(gain)[0])
+
+    def transcipher_lut(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys, table,
+                        gain=1.0):
+        """AES-CTR transciphering through a 256-ENTRY TABLE of the message byte: transcipher_values' inputs and one
+        layout-tagged output ciphertext whose slot of byte i of state b holds gain[b, i] * table[m[b, i]] -- ReLU or
+        GELU of a quantised int8 activation, a G.711 sample, an sRGB pixel, an FP8 number, any 8-bit codebook; exact on
+        the nibble code, where a polynomial of the decoded number would be deep and wrong at the kink.  table: 256
+        finite reals indexed by the byte; gain: a scalar, or broadcastable to (16,) or (states, 16).  The output sits
+        utils.BYTE_LUT_DEPTH = 5 levels below the keystream (one ct x ct level more than transcipher_values; 2 levels
+        left on the fresh-level-7 set); no XOR4, renorm or bootstrap comes after the keystream
+        (xor_value_lut.ByteValueLUT).  Slots that hold no state hold 0; encoder.decode_values returns (states, 16)."""
+        self._no_pairs("transcipher_lut")
+        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
+        lut = self._byte_lut(table, gain)
+        ks = self.ctr_keystream(nonce12, counter0, round_keys)
+        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
+
+    def to_lut(self, ct_hi, ct_lo, table, gain=1.0):
+        """a clean layout-tagged (hi, lo) pair as ONE ciphertext of gain * table[byte] per state slot
+        (ByteValueLUT.apply; utils.BYTE_LUT_DEPTH levels below the pair); table and gain as transcipher_lut's"""
+        self._no_pairs("to_lut")
+        check_layout(self.layout, ct_hi, ct_lo)
+        lut = self._byte_lut(table, gain)
+        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):

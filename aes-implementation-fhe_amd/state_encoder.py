@@ -163,6 +163,11 @@ class LinearSlots:
         return self.weights.shape[0]
 
 
+# the tag of a byte-table value ciphertext (AESPipeline.transcipher_lut / to_lut): one real number
+# per byte, but none of VALUE_DTYPES -- the slots hold table entries, not the integers the bytes spell
+LUT_VALUE_TAG = "lut"
+
+
 def tag_value_dtype(dtype, ct):
     """mark a value ciphertext with the dtype its slots hold (decode_values' default); returns it"""
     try:
@@ -380,11 +385,28 @@ class StateEncoder:
             const += np.roll(wk * e0, st)
         return LinearSlots(dtype, np.ascontiguousarray(weights), np.ascontiguousarray(flags), const, steps, keep, affine)
 
+    def lut_slots(self, gain=1.0, c00: float = 0.0):
+        """(weights, const): the per-slot weight and constant vectors of the byte-table decode
+        (xor_value_lut.ByteValueLUT) -- gain (a scalar, or broadcastable to (16,) or (states, 16), in
+        the caller's byte order) in the slot of each byte and 0 in every slot that holds no state, and
+        const = weights * c00 (the table's mean, byte_value_table's C_00).  _float_slots places the numbers, so the
+        transposed byte order works"""
+        if self.pairs > 1:
+            raise ValueError("lut_slots: multi-pair batches (pairs > 1) are not supported")
+        try:
+            g = np.broadcast_to(np.asarray(gain, np.float64), (self.states, 16))
+        except ValueError:
+            raise ValueError(f"lut_slots: gain must broadcast to (16,) or ({self.states}, 16)") from None
+        if not (np.all(np.isfinite(g)) and np.isfinite(c00)):
+            raise ValueError("lut_slots: gain must be finite")
+        weights = self._float_slots(g)
+        return weights, weights * float(c00)
+
     def values_from_slots(self, slots: np.ndarray, dtype=None) -> np.ndarray:
         """the pure unpacking of decode_values: a slot vector whose word slots hold one real number per word
         (xor_value_lut's output) -> the (states, 16 // w) float array in the caller's byte order, (16 // w,) for one
         state -- _pack's slot order and the encoder's byte order undone, imaginary parts dropped.  dtype None: bytes"""
-        w = value_dtype("u1" if dtype is None else dtype)[0]
+        w = 1 if dtype == LUT_VALUE_TAG else value_dtype("u1" if dtype is None else dtype)[0]
         slots = np.asarray(slots)
         if slots.shape != (self.sc,):
             raise ValueError(f"expected a slot vector of {self.sc} entries, got shape {slots.shape}")

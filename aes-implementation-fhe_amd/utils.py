@@ -34,6 +34,7 @@ RENORM_FLOOR = int(os.environ.get("AESFHE_RENORM_FLOOR", "1"))
 LUT2_DEPTH = 5       # bivariate nibble LUT (XOR4, GF multipliers): basis 3 + product + coefficient
 PUBLIC_XOR_DEPTH = 4  # XOR4 with a public operand (xor4_lut.apply_public): powers up to x^7 3 + plaintext product 1
 XOR_VALUE_DEPTH = 4   # public XOR fused with the value decode (xor_value_lut.py): powers up to x^8 3 + plaintext product 1
+BYTE_LUT_DEPTH = 5    # a 256-entry byte table fused with the value decode (xor_value_lut.ByteValueLUT): powers 3 + plaintext product 1 + ct x ct 1
 SUBBYTES_DEPTH = 13  # lift, b = hi * L(lo), baby/giant steps (sub_bytes_lut.py)
 SHIFTROWS_DEPTH = 1  # masked rotations (shift_rows.py)
 # the level each renorm re-encrypts at = what the step after it needs (engine renorm `level`)

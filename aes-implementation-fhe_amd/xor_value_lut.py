@@ -20,14 +20,15 @@ The last XOR of counter mode has a public operand (the AES ciphertext byte), so 
 in an XOR4, a renorm and a separate decode: AESPipeline.transcipher_values.
 
 TypedValueLUT (DESIGN.md §3.21) is the same sum with per-slot weights, a signed top nibble and 16-bit words;
-LinearValueLUT carries a 16 x 16 matrix per state in up to 16 weight groups.
+LinearValueLUT carries a 16 x 16 matrix per state in up to 16 weight groups.  ByteValueLUT
+ decodes through an arbitrary 256-entry table of the byte instead, for one ct x ct level more.
 """
 from typing import Any, Dict
 
 import numpy as np
 
-from coeffgen import xor_value_table
-from utils import XOR_VALUE_DEPTH
+from coeffgen import BYTE_LUT_Q, byte_value_table, xor_value_table
+from utils import BYTE_LUT_DEPTH, XOR_VALUE_DEPTH, conj_many, mul_many
 from xor4_lut import batched, joint_bases, powers
 
 POWERS = frozenset(range(1, 9))
@@ -237,3 +238,73 @@ class LinearValueLUT(TypedValueLUT):
                 t, r = next(rot), next(rot)
             T, R = (t, r) if T is None else (ctx.add(T, t), ctx.add(R, r))
         return ctx.add_plain(ctx.add(ctx.add(R, T), ctx.conjugate(T)), self.const)
+
+
+class ByteValueLUT(XorValueLUT):
+    """The value decode through an arbitrary 256-entry real table f of the byte: the output slot
+    holds weights * f[byte ^ public byte] -- ReLU of an int8, a G.711 sample, an sRGB pixel, an FP8 number, any 8-bit
+    codebook -- exactly on the nibble code, where a polynomial of the decoded number would be deep and inexact.
+
+    A function of a byte is a bivariate polynomial of degree < 16 in its two codewords a (hi) and c (lo), and the public
+    XOR only permutes its coefficient table per slot (coeffgen.byte_value_table):
+        f(x ^ b) = C_00 + T + conj(T),   T = sum_{q = -7..8} y_q U_q,   U_q = sum_{p = 0..8} K_pq[b] a^p,
+    y_q = c^q (q >= 0, y_0 = 1), conj(c^-q) (q < 0).  The powers take depth 3, the plaintext products of U_q a fourth
+    level and the 15 ct x ct products y_q U_q (q != 0; summed before one relinearisation) a fifth: BYTE_LUT_DEPTH = 5.
+    Everything goes through T + conj(T), which also cancels imaginary noise.
+
+    table: 256 finite reals; weights: one real per slot (StateEncoder.lut_slots: the gain on state slots, 0 elsewhere,
+    so slots that hold no state come out 0)."""
+
+    DEPTH = BYTE_LUT_DEPTH
+
+    def __init__(self, ctx, table, weights):
+        self.ctx = ctx
+        self.sc = ctx.engine.slot_count
+        self.K, self.c00 = byte_value_table(table)  # ValueError: not 256 finite reals
+        self.table = np.asarray(table, np.float64).copy()
+        w = np.asarray(weights, np.float64)
+        if w.shape != (self.sc,) or not np.all(np.isfinite(w)):
+            raise ValueError(f"byte table weights: one finite real per slot ({self.sc}), got shape {w.shape}")
+        self.weights = np.ascontiguousarray(w)
+        self.const = self.weights * self.c00
+
+    def _engine(self, A_hi, nib_hi, nib_lo):
+        """[U_q] from Engine.byte_lut_public, or None (_fused)"""
+        return self._fused("byte_lut_public", A_hi, nib_hi, nib_lo, self.K, self.weights)
+
+    def _loop(self, A_hi, nib_hi, nib_lo):
+        """[U_q] as the product loop over encoded per-slot coefficient vectors: existing calls only, so it runs on any
+        context.  The p = 0 column is added as a plaintext after the products"""
+        ctx = self.ctx
+        b = 16 * nib_hi.astype(np.int64) + nib_lo.astype(np.int64)
+        out = []
+        for qi in range(len(BYTE_LUT_Q)):
+            U = None
+            for p in range(1, 9):
+                k = self.K[p, qi, b]
+                if not np.any(self.K[p, qi]):
+                    continue
+                t = ctx.multiply(A_hi[p], ctx.encode(self.weights * k))
+                U = t if U is None else ctx.add(U, t)
+            if U is None:  # no table leaves a group without a hi power (p = 1..7 are dense in q), kept for safety
+                U = ctx.multiply(A_hi[1], ctx.encode(np.zeros(self.sc)))
+            if np.any(self.K[0, qi]):
+                U = ctx.add_plain(U, self.weights * self.K[0, qi, b])
+            out.append(U)
+        return out
+
+    def apply_public(self, hi, lo, nib_hi, nib_lo):
+        """ONE ciphertext whose slots hold weights * table[(16 hi + lo) ^ (16 nib_hi + nib_lo)] as real numbers,
+        BYTE_LUT_DEPTH levels below the inputs (XorValueLUT.apply_public's operands)"""
+        ctx = self.ctx
+        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
+        A_hi, A_lo = self._bases(hi, lo)
+        bars = conj_many(ctx, [A_lo[k] for k in range(1, 8)])  # conj(c^1..c^7): one batched conjugation
+        y = {q: A_lo[q] if q > 0 else bars[-q - 1] for q in BYTE_LUT_Q if q != 0}
+        U = self._engine(A_hi, nib_hi, nib_lo)
+        if U is None:
+            U = self._loop(A_hi, nib_hi, nib_lo)
+        T = U[BYTE_LUT_Q.index(0)]  # y_0 = 1
+        for t in mul_many(ctx, [(y[q], U[qi]) for qi, q in enumerate(BYTE_LUT_Q) if q != 0]):
+            T = ctx.add(T, t)
+        return ctx.add_plain(ctx.add(T, ctx.conjugate(T)), self.const)

@@ -232,6 +232,29 @@ int aesfhe_debug_xor_value_groups_pt(aesfhe_ctx* ctx, aesfhe_handle table, const
                                      int n_groups, const double* weights, const uint8_t* flags, int level, uint32_t* out, double* scale);
 /* Releases a value table; fails if `table` is not one.  aesfhe_free also accepts value tables. */
 int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table);
+/* A 256-entry byte table fused with the value decode.  For a Zeta16 byte (a, c) = (zeta^x_hi,
+ * zeta^x_lo) and a public byte b, any real table f satisfies f(x ^ b) = C_00 + T + conj(T) with
+ * T = sum_{q = -7..8} y_q U_q, y_q = c^q (q >= 0), conj(c^-q) (q < 0), U_q = sum_{p = 0..8} K_pq[b] a^p.
+ * aesfhe_byte_lut_create uploads K -- re / im: [9][16][256] doubles indexed by p, q + 7 and the public byte -- once
+ * (it waits for its copy once) and refuses a non-finite entry. */
+int aesfhe_byte_lut_create(aesfhe_ctx* ctx, const double* re, const double* im, aesfhe_handle* out);
+/* out[q + 7] = U_q = sum_{p = 1..8} weights (.) K_pq[16 nib_hi + nib_lo] (.) a_hi[p] + weights (.) K_0q[16 nib_hi + nib_lo]
+ * for q = -7..8: 16 ciphertexts at the operands' common lowest level l, each owing its rescale; the p = 0 column is a
+ * per-slot plaintext encoded at the product scale and added inside the sum.  a_hi: 9 handles, the powers hi^p at
+ * index p (entry 0 unused); nib_hi / nib_lo: one public nibble (< 16) per slot, n_slots = slot count; weights: one
+ * finite real per slot (w = 0 leaves the slot 0).  The 16 groups are walked in chunks of 8: one bounded codec buffer
+ * and ONE kernel per chunk, which reads every ciphertext word once for all of the chunk's sums.  Refused with every
+ * handle intact: a nibble >= 16 ("nibble"), n_slots != slot count ("slot_count"), operands at level 0 ("level"), a
+ * stacked operand ("stack"), a missing power ("used row"), a non-finite or missing weight ("weight"). */
+int aesfhe_byte_lut_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const uint8_t* nib_hi,
+                           const uint8_t* nib_lo, int n_slots, const double* weights, aesfhe_handle* out);
+/* tests only: the 16 x 9 coefficient plaintexts of aesfhe_byte_lut_public at `level` (>= 1) as [16][9][nl(level)][N]
+ * uint32 in NTT form -- group q + 7, then p = 0 (the fill) and p = 1..8 -- and their two scales: scales[0] of the
+ * rows p >= 1, scales[1] (the product scale) of the fills */
+int aesfhe_debug_byte_lut_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                             const double* weights, int level, uint32_t* out, double* scales);
+/* Releases a byte table; fails if `table` is not one.  aesfhe_free also accepts byte tables. */
+int aesfhe_byte_lut_free(aesfhe_ctx* ctx, aesfhe_handle table);
 /* Deferred evaluation switch, default on: API-level ct x ct products
  * leave relinearisation and their rescale to the first consumer that needs a
  * 2-polynomial canonical ciphertext (rotate, conjugate, ct x ct, power basis, bootstrap,
