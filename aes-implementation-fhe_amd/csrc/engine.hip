@@ -2227,10 +2227,10 @@ public:
     u32* modup(const u32* d, int level, int nb = 1, size_t d_ms = 0, const TensorPtrs* tp = nullptr, bool rev = false,
                bool cols_only = false) {
         const KsBasis& B = kb(level);
-        const int n = hp_.n, nl = hp_.nl(level), np = B.np, ne = nl + np, alpha = hp_.alpha;
-        const int nd = (nl + alpha - 1) / alpha;
+        const KsGeom k = ks_geom(level);
+        const int n = hp_.n, nl = k.nl, np = k.np, ne = k.ne, alpha = k.alpha, nd = k.nd;
         if (alpha > kMaxConvH || np > kMaxConvH || nb * nd > kMaxConvGroups) throw std::runtime_error("keyswitch: digit too large");
-        const LimbMap em = extmap(nl);
+        const LimbMap em = k.em;
         const bool fz = fused_conv(true);
         if ((tp || rev) && fz) throw std::runtime_error("modup: the tensor / reversed form needs the separate conversion");
         u32* coef = tmp((size_t)nb * nl);
@@ -2313,29 +2313,42 @@ public:
         const u32* d;
         const u32* key;
     };
-    void ki_core(u32* acc, u32* ys, int level, int kept, int nb, const KiSrc* src, int nsrc, size_t d_ms, KsFold fold) {
+    // ------------------------------------------------------------------ key-switch geometry of a level
+    // what every key inner product at `level` is launched with, under the level's special basis (kb: the full one
+    // inside FullP): nl Q limbs + np special primes = ne rows, nd digits of alpha limbs, the key's row layout, the
+    // extended limbs' map, the member strides in words of the ModUp's output [m][nd][ne] and of a Q*P sum [m][2][ne]
+    struct KsGeom {
+        int nl = 0, np = 0, ne = 0, nd = 0, alpha = 0, nkey = 0, nks = 0;
+        LimbMap em{};
+        size_t ext_ms = 0, acc_ms = 0;
+        size_t ext_rows() const { return (size_t)nd * ne; }  // one member's ModUp rows
+    };
+    KsGeom ks_geom(int level) {
         const KsBasis& B = kb(level);
-        const int nl = hp_.nl(level), np = B.np, ne = nl + np, n = hp_.n;
+        KsGeom k;
+        k.nl = hp_.nl(level), k.np = B.np, k.ne = k.nl + k.np, k.alpha = hp_.alpha, k.nd = (k.nl + k.alpha - 1) / k.alpha;
+        k.nkey = B.nkey, k.nks = B.nks, k.em = extmap(k.nl);
+        k.ext_ms = k.ext_rows() * hp_.n, k.acc_ms = (size_t)2 * k.ne * hp_.n;
+        return k;
+    }
+    void ki_core(u32* acc, u32* ys, int level, int kept, int nb, const KiSrc* src, int nsrc, size_t d_ms, KsFold fold) {
+        const KsGeom k = ks_geom(level);
         KiArgs a;
         for (int i = 0; i < nsrc; ++i) a.ext[i] = src[i].ext, a.d[i] = src[i].d, a.key[i] = src[i].key;
         a.nsrc = nsrc;
-        a.nd = (nl + hp_.alpha - 1) / hp_.alpha, a.ne = ne, a.nl = nl, a.alpha = hp_.alpha;
-        a.nkey = B.nkey, a.nks = B.nks;
-        a.kept = kept, a.ys_rows = ne - kept, a.nb = nb;
-        a.ext_ms = (size_t)a.nd * ne * n, a.d_ms = d_ms, a.acc_ms = (size_t)2 * ne * n, a.ys_ms = (size_t)2 * (ne - kept) * n;
+        a.nd = k.nd, a.ne = k.ne, a.nl = k.nl, a.alpha = k.alpha;
+        a.nkey = k.nkey, a.nks = k.nks;
+        a.kept = kept, a.ys_rows = k.ne - kept, a.nb = nb;
+        a.ext_ms = k.ext_ms, a.d_ms = d_ms, a.acc_ms = k.acc_ms, a.ys_ms = (size_t)2 * (k.ne - kept) * hp_.n;
         a.acc = acc, a.ys = ys, a.fold = fold;
-        launch_ntt_ki(S(), T_, a, extmap(nl));  // its row passes are counted with the column passes they pair with
+        launch_ntt_ki(S(), T_, a, k.em);  // its row passes are counted with the column passes they pair with
     }
-    int ext_rows(int level) const { return (hp_.nl(level) + hp_.alpha - 1) / hp_.alpha * (hp_.nl(level) + np_at(level)); }
     // acc (2 x ne rows, Q*P) = sum_j ext_j * key_j; g != 0 reads ext and d through X -> X^g
     // nb batched ciphertexts (ext = [m][nd][ne], d + m d_ms, acc = [m][2][ne]) share the key reads
     void key_inner(u32* acc, const u32* ext, const u32* d, const u32* key, int level, u64 g, int nb = 1, size_t d_ms = 0,
                    KsFold fold = {}, bool accum = false) {
-        const KsBasis& B = kb(level);
-        const int nl = hp_.nl(level), np = B.np, ne = nl + np, n = hp_.n;
-        const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner(S(), T_, acc, ext, d, key, nd, ne, nl, hp_.alpha, B.nkey, B.nks, extmap(nl), g, nb,
-                         (size_t)nd * ne * n, d_ms, (size_t)2 * ne * n, fold, accum);
+        const KsGeom k = ks_geom(level);
+        launch_key_inner(S(), T_, acc, ext, d, key, k.nd, k.ne, k.nl, k.alpha, k.nkey, k.nks, k.em, g, nb, k.ext_ms, d_ms, k.acc_ms, fold, accum);
     }
     // the 2 x - c epilogue per member of a relinearisation + rescale (EvalMod's 2 T^2 - 1, the
     // residues of lincomb(P, 2, nullptr, 0, -c, 0)): dbl bit m doubles member m, cst[m] its constant
@@ -2436,7 +2449,7 @@ public:
     // ------------------------------------------------------------------ one complete key switch
     // ModUp, key inner product, ModDown of nb members at one level (run_ks): what keyswitch, relin_rescale,
     // relin_rescale_tensor and the automorphisms of one ciphertext (galois, galois_lazy) each build.  The hoisted and
-    // accumulating forms (one ModUp for several inner products, sums across calls) are not jobs.
+    // accumulating forms (one ModUp for several inner products, sums across calls) are not jobs: Hoist builds those.
     struct KsJob {
         int level = 0, nb = 1;
         // the polynomials to switch (NTT form; member m at d + m d_ms) and their keys.  nsrc == 2 (nb == 1 only): a
@@ -2463,12 +2476,13 @@ public:
     // A stack of more members than one batched key switch carries (ks_chunk) goes through in chunks, each chunk's
     // ModDown writing its rows of the one stacked result.
     Ct run_ks(const KsJob& j) {
-        const int l = j.level, n = hp_.n, ne = hp_.nl(l) + np_at(l), ch = ks_chunk(l), nb = j.nb;
+        const KsGeom k = ks_geom(j.level);
+        const int l = j.level, n = hp_.n, ne = k.ne, ch = ks_chunk(l), nb = j.nb;
         if (j.tp && nb > ch) throw std::runtime_error("relin_rescale_tensor: more members than one chunk");
         if (j.outm && nb > ch) throw std::runtime_error("relin_rescale: per-member outputs need one chunk");
         const int lo = j.rescale ? l - 1 : l, kept = hp_.nl(lo), h = ne - kept;
         const bool fused = fused_ki_ok() && !j.separate;
-        const size_t oms = (size_t)2 * kept * n, xr = (size_t)j.nsrc * ext_rows(l);
+        const size_t oms = (size_t)2 * kept * n, xr = (size_t)j.nsrc * k.ext_rows();
         Ct o;
         o.level = lo, o.npoly = 2 * nb, o.nb = nb, o.words = nb * oms, o.data = j.dst;
         for (int m0 = 0; m0 < nb; m0 += ch) {
@@ -2483,11 +2497,11 @@ public:
             u32* ys = fused ? tmp(2 * (size_t)h * c) : nullptr;
             if (fused) {
                 KiSrc src[2];
-                for (int i = 0; i < j.nsrc; ++i) src[i] = KiSrc{ext + i * (size_t)ext_rows(l) * n, d[i], j.key[i]};
+                for (int i = 0; i < j.nsrc; ++i) src[i] = KiSrc{ext + i * k.ext_ms, d[i], j.key[i]};
                 ki_core(acc, ys, l, kept, c, src, j.nsrc, j.d_ms, fold);
             } else {
                 for (int i = 0; i < j.nsrc; ++i)
-                    key_inner(acc, ext + i * (size_t)ext_rows(l) * n, d[i], j.key[i], l, 0, c, j.d_ms, fold, i > 0);
+                    key_inner(acc, ext + i * k.ext_ms, d[i], j.key[i], l, 0, c, j.d_ms, fold, i > 0);
             }
             untmp(ext, c * xr);
             if (!o.data && !j.outm) o.data = alloc_words(o.words);
@@ -3140,9 +3154,9 @@ public:
             by_level[s.level].push_back(i);
         }
         for (auto& kv : by_level) {
-            const int l = kv.first, nl = hp_.nl(l), ne = nl + np_at(l), nd = (nl + hp_.alpha - 1) / hp_.alpha;
+            const int l = kv.first, nl = hp_.nl(l);
             const auto& items = kv.second;
-            const int max_src = std::max(1, kMaxConvGroups / nd);
+            const int max_src = std::max(1, kMaxConvGroups / ks_geom(l).nd);
             size_t pos = 0;
             while (pos < items.size()) {
                 std::vector<int> chunk;
@@ -3162,6 +3176,7 @@ public:
                 const int nm = (int)chunk.size(), ns = (int)srcs.size();
                 // c1 of every source, stacked: used in place when the sources already sit at a
                 // member stride of 2 nl N (e.g. one stack rescaled above), else gathered
+                Hoist H(*this);
                 const u32* c1s = srcs[0].c1;
                 size_t d_ms = 0;
                 u32* c1buf = nullptr;
@@ -3172,19 +3187,17 @@ public:
                     if (regular) {
                         d_ms = stride;
                     } else {
-                        std::vector<const u32*> c1v(ns);
-                        for (int j = 0; j < ns; ++j) c1v[j] = srcs[j].c1;
-                        c1buf = tmp((size_t)ns * nl);
+                        c1buf = H.get((size_t)ns * nl);
                         MemberPtrs mp;
-                        for (int j = 0; j < ns; ++j) mp.src[j] = c1v[j], mp.dst[j] = c1buf + (size_t)j * nl * nn;
+                        for (int j = 0; j < ns; ++j) mp.src[j] = srcs[j].c1, mp.dst[j] = c1buf + (size_t)j * nl * nn;
                         launch_copy_members(S(), T_, mp, ns, nl);
                         c1s = c1buf, d_ms = (size_t)nl * nn;
                     }
                 }
-                u32* ext = modup(c1s, l, ns, d_ms);
-                u32* acc = tmp((size_t)nm * 2 * ne);
+                H.up(c1s, l, ns, d_ms);
                 KsMultiArgs ka;
                 AutoMulti am;
+                Ct* om[kMaxMembers];  // each member's ModDown finish writes its own buffer
                 for (int m = 0; m < nm; ++m) {
                     const int i = chunk[m];
                     const KsSrc& s = src_of.at(C[i]->data);
@@ -3193,26 +3206,9 @@ public:
                     ka.src[m] = src_index(s);
                     am.src[m] = s.c0;
                     am.g[m] = G[i];
+                    om[m] = &out[i];
                 }
-                launch_key_inner_multi(S(), T_, acc, ext, c1s, ka, nm, ns, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
-                                       (size_t)ext_rows(l) * nn, d_ms, (size_t)2 * ne * nn);
-                untmp(ext, (size_t)ns * ext_rows(l));
-                if (c1buf) untmp(c1buf, (size_t)ns * nl);
-                const size_t ms = (size_t)2 * nl * nn;
-                u32* c0p = tmp((size_t)nm * 2 * nl);  // member stride 2 nl N (moddown's add stride), first nl rows used
-                launch_automorph_multi(S(), T_, c0p, ms, am, nm, nl);
-                u32* om[kMaxMembers];  // each member's ModDown finish writes its own buffer: no unstack copy
-                for (int m = 0; m < nm; ++m) {
-                    Ct& r = out[chunk[m]];
-                    r = alloc_ct(l, 2);
-                    r.ntt = true, r.pend = 0, r.lazy = false;
-                    om[m] = r.data;
-                }
-                moddown(acc, l, c0p, nullptr, nm, ms, nullptr, om);
-                untmp(acc, (size_t)nm * 2 * ne);
-                untmp(c0p, (size_t)nm * 2 * nl);
-                cnt_[C_KS] += nm;
-                tally(LV_KS, l, nm);
+                H.multi(ka, am, nm, om, c1buf);
             }
         }
         for (const Ct& c : owned) release(c);
@@ -3317,37 +3313,17 @@ public:
     std::vector<Ct> rotate_hoisted(const Ct& c_in, const std::vector<int>& steps) {
         std::vector<Ct> out(steps.size());
         if (vis_npoly(c_in) != 2) throw std::runtime_error("rotation/conjugation expects a 2-polynomial ciphertext");
+        Hoist H(*this);
         Ct c = normalize(c_in);
-        const long sc = slot_count();
+        if (c.data != c_in.data) H.own(c);
         int nrot = 0;
-        for (int st : steps) nrot += (((long)st % sc + sc) % sc) != 0;
+        for (int st : steps) nrot += rot_mod(st) != 0;
         if (c.nb != 1 || nrot < 2 || !batch_ops_) {
             for (size_t i = 0; i < steps.size(); ++i) out[i] = rotate(c, steps[i]);
-            if (c.data != c_in.data) release(c);
             return out;
         }
-        const int l = c.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n;
-        const u32* c1 = c.data + (size_t)nl * n;
-        u32* ext = modup(c1, l, 1, 0);
-        for (size_t i = 0; i < steps.size(); ++i) {
-            if ((((long)steps[i] % sc + sc) % sc) == 0) {
-                out[i] = copy(c);
-                continue;
-            }
-            const u64 g = rot_galois(steps[i]);
-            u32* acc = tmp(2 * (size_t)ne);
-            key_inner(acc, ext, c1, ksk_at(g, l), l, g);
-            u32* p0 = tmp(nl);
-            launch_automorph(S(), T_, p0, c.data, g, nl);
-            out[i] = moddown(acc, l, p0, nullptr);
-            untmp(p0, nl);
-            untmp(acc, 2 * (size_t)ne);
-            cnt_[C_ROT]++;
-            cnt_[C_KS]++;
-            tally(LV_KS, l, 1);
-        }
-        untmp(ext, ext_rows(l));
-        if (c.data != c_in.data) release(c);
+        H.up(c.data + (size_t)hp_.nl(c.level) * hp_.n, c.level);
+        for (size_t i = 0; i < steps.size(); ++i) out[i] = rot_mod(steps[i]) == 0 ? copy(c) : H.step(c.data, rot_galois(steps[i]));
         return out;
     }
     // a mask encoded for the double-hoisted sum at `level` (rot_pt_sum): scale ptscale[level] on the nl Q limbs
@@ -3388,25 +3364,34 @@ public:
         p.encx[key] = {d, (size_t)nl * hp_.n};
         return d;
     }
-    // the temporaries of one call (rot_pt_sum, the renorm): scratch rows and owned ciphertexts go back to the pool
-    // on the way out, by return or by throw.  Fixed capacity: a call allocates nothing for it
+    // the temporaries of one call (the hoisted key switches, rot_pt_sum, the renorm): scratch rows and owned
+    // ciphertexts go back to the pool on the way out, by return or by throw.  Fixed capacity (lin_group holds the
+    // most rows: 15 baby steps, 3 x kLinG sums, a block, the giant sums): a call allocates nothing for it
     struct Guard {
-        static constexpr int kCap = 8;
+        static constexpr int kRows = 48, kCap = 8;
         Engine& e;
-        std::pair<u32*, size_t> rows[kCap];
+        std::pair<u32*, size_t> rows[kRows];
         Ct cts[kCap];
         int nr = 0, nc = 0;
         explicit Guard(Engine& eng) : e(eng) {}
         Guard(const Guard&) = delete;
         [[noreturn]] static void full() { throw std::runtime_error("Guard: more temporaries than it holds"); }
         u32* get(size_t r) {
-            if (nr == kCap) full();
+            if (nr == kRows) full();
             rows[nr] = {e.tmp(r), r};
             return rows[nr++].first;
         }
         void row(u32* p, size_t r) {  // rows taken elsewhere (a ModUp's output)
-            if (nr == kCap) e.untmp(p, r), full();
+            if (nr == kRows) e.untmp(p, r), full();
             rows[nr++] = {p, r};
+        }
+        void put(u32* p) {  // rows done with before the call ends: back to the pool now (nullptr: nothing)
+            for (int x = 0; p && x < nr; ++x)
+                if (rows[x].first == p) {
+                    e.untmp(p, rows[x].second);
+                    rows[x] = rows[--nr];
+                    return;
+                }
         }
         void own(const Ct& c) {
             if (nc == kCap) e.release(c), full();
@@ -3424,6 +3409,80 @@ public:
             for (int x = 0; x < nc; ++x) e.release(cts[x]);
         }
     };
+    // ------------------------------------------------------------------ the hoisted key switch
+    // ONE ModUp of c1 (nb members at c1 + m d_ms) shared by several key inner products, as an owned scope: a Guard
+    // that also holds the ModUp's output ext, the level's geometry k and every row taken through it.  up() runs the
+    // ModUp (the bare constructor: a caller that owns temporaries before it, or may need none).  The three ends
+    // finish the switch -- inner products read through automorphisms, the matching automorphism of c0, ONE ModDown
+    // -- and count it; rot_pt_sum and lin_group run their MAC kernels on ext and k instead.  Rows go back (put) where
+    // the sequences written out by hand returned them, so the pool hands out what it did
+    struct Hoist : Guard {
+        KsGeom k;
+        int level = 0, nb = 1;
+        const u32* c1 = nullptr;
+        size_t d_ms = 0;
+        u32* ext = nullptr;
+        explicit Hoist(Engine& eng) : Guard(eng) {}
+        Hoist(Engine& eng, const u32* d, int l, int m, size_t ms, bool cols_only = false) : Guard(eng) { up(d, l, m, ms, cols_only); }
+        void up(const u32* c1_, int level_, int nb_ = 1, size_t d_ms_ = 0, bool cols_only = false) {
+            k = e.ks_geom(level_), level = level_, nb = nb_, c1 = c1_, d_ms = d_ms_;
+            ext = e.modup(c1, level, nb, d_ms, nullptr, false, cols_only);
+            row(ext, (size_t)nb * k.ext_rows());
+        }
+        void drop_ext() { put(ext), ext = nullptr; }
+        void count(int rot, int ks) {
+            e.cnt_[C_ROT] += rot, e.cnt_[C_KS] += ks, e.tally(LV_KS, level, ks);
+        }
+        // per step (nb = 1): the inner product read through X -> X^g, the permuted c0 added in its ModDown; ext stays
+        Ct step(const u32* c0, u64 g) {
+            u32* acc = get(2 * (size_t)k.ne);
+            e.key_inner(acc, ext, c1, e.ksk_at(g, level), level, g);
+            u32* p0 = get(k.nl);
+            launch_automorph(e.S(), e.T_, p0, c0, g, k.nl);
+            Ct o = e.moddown(acc, level, p0, nullptr);
+            put(p0), put(acc);
+            count(1, 1);
+            return o;
+        }
+        // multi: member m of nm reads source ka.src[m] of the nb ModUp'ed ones through X -> X^ka.g[m] under ka.key[m],
+        // its c0 am.src[m] permuted alike: ONE inner product, ONE automorphism, ONE ModDown launch sequence, member m's
+        // result written straight into the new ciphertext *out[m].  gathered: the caller's copy of the c1s (a row of
+        // this scope, or nullptr), done with once the inner product has read it
+        void multi(const KsMultiArgs& ka, const AutoMulti& am, int nm, Ct* const* out, u32* gathered) {
+            u32* acc = get((size_t)nm * 2 * k.ne);
+            launch_key_inner_multi(e.S(), e.T_, acc, ext, c1, ka, nm, nb, k.nd, k.ne, k.nl, k.alpha, k.nkey, k.nks, k.em, k.ext_ms, d_ms, k.acc_ms);
+            drop_ext();
+            put(gathered);
+            const size_t ms = (size_t)2 * k.nl * e.hp_.n;
+            u32* c0p = get((size_t)nm * 2 * k.nl);  // member stride 2 nl N (moddown's add stride), first nl rows used
+            launch_automorph_multi(e.S(), e.T_, c0p, ms, am, nm, k.nl);
+            u32* om[kMaxMembers];
+            for (int m = 0; m < nm; ++m) {
+                Ct r = e.alloc_ct(level, 2);
+                own(r);
+                r.ntt = true, r.pend = 0, r.lazy = false;
+                *out[m] = r, om[m] = r.data;
+            }
+            e.moddown(acc, level, c0p, nullptr, nm, ms, nullptr, om);
+            for (int m = 0; m < nm; ++m) disown(*out[m]);
+            put(acc), put(c0p);
+            count(0, nm);
+        }
+        // summed: ka's J inner products summed in one launch, c0 + its automorphisms kc in another (bit for bit the
+        // separate launches' sums), ONE ModDown adding both and add1
+        Ct summed(const u32* c0, const KsSumArgs& ka, const KsSumArgs& kc, const u32* add1) {
+            u32* acc = get(2 * (size_t)k.ne * nb);
+            launch_key_inner_sum(e.S(), e.T_, acc, ext, c1, ka, nb, k.nd, k.ne, k.nl, k.alpha, k.nkey, k.nks, k.em, k.ext_ms, d_ms, k.acc_ms);
+            drop_ext();
+            u32* c0s = get(2 * (size_t)k.nl * nb);  // member stride d_ms, first nl rows used (moddown's add0)
+            launch_automorph_sum(e.S(), e.T_, c0s, c0, kc, nb, k.nl, d_ms, qmap());
+            Ct o = e.moddown(acc, level, c0s, add1, nb, d_ms);
+            put(acc), put(c0s);
+            count(kc.J * nb, ka.J * nb);
+            return o;
+        }
+    };
+    long rot_mod(long steps) const { return (steps % slot_count() + slot_count()) % slot_count(); }  // 0: no rotation
     // out[j] = sum_i pts[j n + i] (.) rotate(c, steps[i]), double-hoisted (aesfhe_rot_pt_sum):
     // c1 is ModUp'ed ONCE, k_rot_mask_mac forms every used rotation's key inner product through its
     // automorphism, multiplies it by the term's mask and sums in Q*P -- one ModDown per output, under the
@@ -3438,23 +3497,22 @@ public:
         if (c_in.nb != 1) throw std::runtime_error("rot_pt_sum: a single ciphertext (stacks are refused)");
         if (vis_npoly(c_in) != 2) throw std::runtime_error("rot_pt_sum: expects a 2-polynomial ciphertext");
         if (c_in.level - c_in.pend < 1) throw std::runtime_error("not enough level to multiply by a plaintext (level 0)");
-        Guard G(*this);
+        Hoist G(*this);
         Ct c = normalize(c_in);
         if (c.data != c_in.data) G.own(c);
-        const int l = c.level, nl = hp_.nl(l), np = np_at(l), ne = nl + np, N = hp_.n;
-        const KsBasis& B = kb(l);
-        const long sc = slot_count();
+        const KsGeom k = ks_geom(c.level);
+        const int l = c.level, nl = k.nl, np = k.np, ne = k.ne, N = hp_.n;
         RotMacArgs a;
         a.c0 = c.data, a.c1 = c.data + (size_t)nl * N;
         a.n = n, a.n_out = n_out;
-        a.nd = (nl + hp_.alpha - 1) / hp_.alpha, a.alpha = hp_.alpha, a.nkey = B.nkey, a.nks = B.nks;
+        a.nd = k.nd, a.alpha = k.alpha, a.nkey = k.nkey, a.nks = k.nks;
         bool rot_out[kRotMacOut] = {};
         int nrot = 0, nmask = 0;
         for (int i = 0; i < n; ++i) {
             bool used = false;
             for (int j = 0; j < n_out; ++j)
                 if (const aesfhe_handle h = pts[(size_t)j * n + i]) a.pt[j][i] = pt_ext_at(pt(h), l, np), used = true, ++nmask;
-            if (!used || (((long)steps[i] % sc + sc) % sc) == 0) continue;
+            if (!used || rot_mod(steps[i]) == 0) continue;
             a.gal[i] = rot_galois(steps[i]);
             a.key[i] = ksk_at(a.gal[i], l);
             for (int j = 0; j < n_out; ++j) rot_out[j] = rot_out[j] || a.pt[j][i];
@@ -3463,11 +3521,7 @@ public:
         int nfill = 0;
         for (int j = 0; fills && j < n_out; ++j)
             if (fills[j]) a.fill[j] = pt_fill_at(pt(fills[j]), l, np), ++nfill;
-        if (nrot) {
-            u32* ext = modup(a.c1, l, 1, 0);
-            G.row(ext, (size_t)ext_rows(l));
-            a.ext = ext;
-        }
+        if (nrot) G.up(a.c1, l), a.ext = G.ext;
         std::vector<Ct> out(n_out);
         for (int j = 0; j < n_out; ++j) {
             out[j] = alloc_ct(l, 2);
@@ -3478,7 +3532,7 @@ public:
                 a.out0[j] = out[j].data, a.out1[j] = out[j].data + (size_t)nl * N;
             }
         }
-        launch_rot_mask_mac(S(), T_, a, nl, ne, extmap(nl));
+        launch_rot_mask_mac(S(), T_, a, nl, ne, k.em);
         for (int j = 0; j < n_out; ++j) {
             if (rot_out[j]) moddown(a.outp[j], l, a.out0[j], a.out1[j], 1, 0, out[j].data);
             out[j].pend = 1;
@@ -3500,8 +3554,7 @@ public:
         return out;
     }
     Ct rotate(const Ct& c, int steps) {
-        const long s = slot_count();
-        if (((long)steps % s + s) % s == 0) return copy(c);
+        if (rot_mod(steps) == 0) return copy(c);
         cnt_[C_ROT]++;
         return galois(c, rot_galois(steps));
     }
@@ -4130,69 +4183,31 @@ public:
     // x + rot(x, -a) + rot(x, -2a) + rot(x, -3a) for the nb members of x: the three rotations
     // hoisted (one ModUp of c1, key inner products read through each automorphism) and summed
     // in Q*P (one ModDown adding c0 + the permuted c0s and c1) -- two trace doublings for ~1.5
-    // rotations' work
-    Ct trace4(const Ct& x_in, int a) {
-        if (vis_npoly(x_in) != 2) throw std::runtime_error("trace4: 2-polynomial ciphertext expected");
-        Ct x = normalize(x_in);
-        const int l = x.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n, nb = x.nb;
-        const size_t qs = (size_t)2 * nl * n;
-        const u32* c1 = x.data + (size_t)nl * n;
-        u32* ext = modup(c1, l, nb, qs);
-        u32* acc = tmp(2 * (size_t)ne * nb);
-        // the three rotations' key inner products summed in one launch, c0 + its three
-        // automorphisms in another (bit for bit the separate launches' sums)
-        KsSumArgs ka;
-        ka.J = 3;
-        for (int j = 1; j <= 3; ++j) ka.g[j - 1] = rot_galois(-j * a), ka.key[j - 1] = ksk_at(ka.g[j - 1], l);
-        const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
-                             (size_t)ext_rows(l) * n, qs, (size_t)2 * ne * n);
-        untmp(ext, (size_t)nb * ext_rows(l));
-        u32* c0s = tmp(2 * (size_t)nl * nb);  // member stride qs, first nl rows used (moddown's add0)
-        launch_automorph_sum(S(), T_, c0s, x.data, ka, nb, nl, qs, qmap());
-        Ct o = moddown(acc, l, c0s, c1, nb, qs);
-        o.ntt = x.ntt;
-        untmp(acc, 2 * (size_t)ne * nb);
-        untmp(c0s, 2 * (size_t)nl * nb);
-        if (x.data != x_in.data) release(x);
-        cnt_[C_ROT] += 3 * nb;
-        cnt_[C_KS] += 3 * nb;
-        tally(LV_KS, l, 3 * nb);
-        return o;
-    }
-    // The sparse -> dense switch fused into the first trace step (AESFHE_S2D_TRACE, default on):
-    // raised (under s_sp) -> x + rot(x, -a) + rot(x, -2a) + rot(x, -3a) with x = raised switched to s.
-    // The automorphism of raised decrypts under sigma(s_sp), so each of the four terms is ONE key
-    // inner product from the same hoisted ModUp of raised's c1 (keys s_sp -> s and sigma_j(s_sp) -> s,
-    // tag_s2d_rot) and the four share one ModDown: one ModUp and one ModDown at the top level fewer
-    // than keyswitch(s2d) followed by trace4.  Same plaintext; the key-switch noise terms differ.
+    // rotations' work.
+    // s2d: the sparse -> dense switch fused into the first trace step (AESFHE_S2D_TRACE, default on): x is the
+    // raised ciphertext (under s_sp, taken as it is) and the result x' + its three rotations with x' = x switched
+    // to s.  The automorphism of x decrypts under sigma(s_sp), so each of the four terms is ONE key inner product
+    // from the same hoisted ModUp (keys s_sp -> s and sigma_j(s_sp) -> s, tag_s2d_rot; c1 is switched, not added)
+    // and the four share one ModDown: one ModUp and one ModDown at the top level fewer than keyswitch(s2d)
+    // followed by the plain step.  Same plaintext; the key-switch noise terms differ.
     bool s2d_trace_ = env_int("AESFHE_S2D_TRACE", 1) != 0;
-    Ct s2d_trace4(const Ct& raised, int a) {
-        const int l = raised.level, nl = hp_.nl(l), ne = nl + np_at(l), n = hp_.n, nb = raised.nb;
-        const size_t qs = (size_t)2 * nl * n;
-        const u32* c1 = raised.data + (size_t)nl * n;
-        u32* ext = modup(c1, l, nb, qs);
-        u32* acc = tmp(2 * (size_t)ne * nb);
-        KsSumArgs ka;
-        ka.J = 4;
-        ka.g[0] = 1, ka.key[0] = ksk_at(tag_s2d(), l);
-        for (int j = 1; j <= 3; ++j) ka.g[j] = rot_galois(-j * a), ka.key[j] = ksk_at(tag_s2d_rot(ka.g[j]), l);
-        const int nd = (nl + hp_.alpha - 1) / hp_.alpha;
-        launch_key_inner_sum(S(), T_, acc, ext, c1, ka, nb, nd, ne, nl, hp_.alpha, kb(l).nkey, kb(l).nks, extmap(nl),
-                             (size_t)ext_rows(l) * n, qs, (size_t)2 * ne * n);
-        untmp(ext, (size_t)nb * ext_rows(l));
-        KsSumArgs kc;  // c0 + its three automorphisms
-        kc.J = 3;
-        for (int j = 1; j <= 3; ++j) kc.g[j - 1] = ka.g[j];
-        u32* c0s = tmp(2 * (size_t)nl * nb);  // member stride qs, first nl rows used (moddown's add0)
-        launch_automorph_sum(S(), T_, c0s, raised.data, kc, nb, nl, qs, qmap());
-        Ct o = moddown(acc, l, c0s, nullptr, nb, qs);
-        o.ntt = raised.ntt;
-        untmp(acc, 2 * (size_t)ne * nb);
-        untmp(c0s, 2 * (size_t)nl * nb);
-        cnt_[C_ROT] += 3 * nb;
-        cnt_[C_KS] += 4 * nb;
-        tally(LV_KS, l, 4 * nb);
+    Ct trace4(const Ct& x_in, int a, bool s2d = false) {
+        if (!s2d && vis_npoly(x_in) != 2) throw std::runtime_error("trace4: 2-polynomial ciphertext expected");
+        Hoist H(*this);
+        Ct x = s2d ? x_in : normalize(x_in);
+        if (x.data != x_in.data) H.own(x);
+        const int l = x.level, nl = hp_.nl(l);
+        const u32* c1 = x.data + (size_t)nl * hp_.n;
+        H.up(c1, l, x.nb, (size_t)2 * nl * hp_.n);
+        KsSumArgs ka, kc;  // the key list; c0's automorphisms (the rotations)
+        kc.J = 3, ka.J = 0;
+        if (s2d) ka.g[0] = 1, ka.key[0] = ksk_at(tag_s2d(), l), ka.J = 1;
+        for (int j = 1; j <= 3; ++j) {
+            const u64 g = kc.g[j - 1] = rot_galois(-j * a);
+            ka.g[ka.J] = g, ka.key[ka.J++] = ksk_at(s2d ? tag_s2d_rot(g) : g, l);
+        }
+        Ct o = H.summed(x.data, ka, kc, s2d ? nullptr : c1);
+        o.ntt = x.ntt;
         return o;
     }
     SparseBoot& sparse_variant(int n, bool pair = false) {
@@ -4391,7 +4406,10 @@ public:
         // this path keeps the full special basis at every level
         const FullP full_basis(*this);
         const LinGroup& g = *G.g;
-        const int l = in.level, nl = hp_.nl(l), np = hp_.n_p, ne = nl + np, n = hp_.n;
+        // under FullP no level is a reduced one (low_level): kb() is the full basis and the geometry holds what this
+        // path used to write by hand, np = n_p, nkey = n_ks + n_p, nks = n_ks
+        const KsGeom k = ks_geom(in.level);
+        const int l = in.level, nl = k.nl, ne = k.ne, n = hp_.n;
         if (g.B > kMacMax) throw std::runtime_error("lin_group: more than 16 baby steps");
         auto& P = group_pts(G, l);
         // nb batched ciphertexts (bootstrap_pair): member m at + m qs words; every Q-side
@@ -4410,9 +4428,9 @@ public:
         // (each is then computed once), else materialised by k_key_inner
         const bool fused_baby = fused_baby_ && g.G <= kLinG;
         std::vector<const u32*> bkey(g.B, nullptr);
-        u32* ext = nullptr;
+        Hoist H(*this);  // every row below is taken through it: none outlives the call
         if (any_baby) {
-            ext = modup(c1, l, nb, qs);
+            H.up(c1, l, nb, qs);
             for (int b = 1; b < g.B; ++b) {
                 bool used = false;
                 for (int gg = 0; gg < g.G; ++gg) used = used || P[gg][b];
@@ -4421,30 +4439,21 @@ public:
                 if (fused_baby) {
                     bkey[b] = ksk_at(gal, l);
                 } else {
-                    u[b] = tmp(2 * (size_t)ne * nb);
-                    key_inner(u[b], ext, c1, ksk_at(gal, l), l, gal, nb, qs);
+                    u[b] = H.get(2 * (size_t)ne * nb);
+                    key_inner(u[b], H.ext, c1, ksk_at(gal, l), l, gal, nb, qs);
                 }
                 gals[b] = gal;  // c0's automorphism is read inside k_lin_mac
                 cnt_[C_ROT] += nb;
                 tally(LV_KS, l, nb);  // a baby-step rotation: one key switch per member (hoisted ModUp)
             }
-            if (!fused_baby) {
-                untmp(ext, (size_t)nb * ext_rows(l));
-                ext = nullptr;
-            }
+            if (!fused_baby) H.drop_ext();
         }
         Ct out;
         bool have = false;
         // double hoisting: the rotated giant steps' key inner products are summed in Q*P and
         // share ONE ModDown (their permuted c0 summed beside), the unrotated step folded in
         const bool dh = double_hoist_;
-        u32* dh_acc = nullptr;
-        u32* dh_c0 = nullptr;
-        // the fused-core form's P rows (after the ModDown INTT's row pass), owned by THIS call: an
-        // exception between giant_accumulate_many and the ModDown below cannot leave it to a later
-        // group (it was Engine-wide state that a later call would have taken as its own)
-        u32* dh_ys = nullptr;
-        int dh_n = 0;
+        GiantSum gs;  // owned by THIS call (its rows are H's): nothing of it reaches a later group, whatever throws
         bool continue_giant = false;
         // all giant steps' diagonal sums in one pass per chunk of kLinG giant steps (k_lin_mac):
         // every baby-step residue is read once instead of once per giant step
@@ -4459,9 +4468,9 @@ public:
             m.gad = fold ? d_gadget_ : nullptr;
             for (int b = 0; b < g.B; ++b)
                 m.a[b] = (b == 0 || u[b] || bkey[b]) ? c0 : nullptr, m.u[b] = b ? u[b] : nullptr, m.gal[b] = gals[b], m.key[b] = bkey[b];
-            if (ext) {
-                m.ks_ext = ext, m.ks_d = c1, m.ext_ms = (size_t)ext_rows(l) * n, m.d_ms = qs;
-                m.nd = (nl + hp_.alpha - 1) / hp_.alpha, m.alpha = hp_.alpha, m.nkey = hp_.n_ks + np, m.nks = hp_.n_ks;
+            if (H.ext) {
+                m.ks_ext = H.ext, m.ks_d = c1, m.ext_ms = k.ext_ms, m.d_ms = qs;
+                m.nd = k.nd, m.alpha = k.alpha, m.nkey = k.nkey, m.nks = k.nks;
             }
             bool any[kLinG] = {}, rot[kLinG] = {};
             for (int j = 0; j < gn; ++j)
@@ -4477,36 +4486,37 @@ public:
                 for (int j = 0; j < gn; ++j)
                     if (any[j] && rot[j] && g.giant[g0 + j]) bj.push_back(j);
             if ((int)bj.size() < 2 || 2 * nb * (int)bj.size() > kMaxConvGroups) bj.clear();
-            u32* blk = bj.empty() ? nullptr : tmp(bj.size() * 2 * (size_t)ne * nb);
+            u32* blk = bj.empty() ? nullptr : H.get(bj.size() * 2 * (size_t)ne * nb);
             bool in_blk[kLinG] = {};
             for (size_t i = 0; i < bj.size(); ++i) in_blk[bj[i]] = true;
             for (int j = 0, i = 0; j < gn; ++j) {
                 const bool folded = fold && rot[j];
-                m.out0[j] = folded ? nullptr : tmp(2 * (size_t)nl * nb);  // member stride qs, first nl rows used
-                m.out1[j] = (P[g0 + j][0] && !folded) ? tmp(2 * (size_t)nl * nb) : nullptr;
-                m.outp[j] = in_blk[j] ? blk + (size_t)(i++) * nb * ps : rot[j] ? tmp(2 * (size_t)ne * nb) : nullptr;
+                m.out0[j] = folded ? nullptr : H.get(2 * (size_t)nl * nb);  // member stride qs, first nl rows used
+                m.out1[j] = (P[g0 + j][0] && !folded) ? H.get(2 * (size_t)nl * nb) : nullptr;
+                m.outp[j] = in_blk[j] ? blk + (size_t)(i++) * nb * ps : rot[j] ? H.get(2 * (size_t)ne * nb) : nullptr;
             }
-            launch_lin_mac(S(), T_, m, nl, ne, extmap(nl));
+            launch_lin_mac(S(), T_, m, nl, ne, k.em);
             for (int j = 0; j < gn; ++j)
                 for (int b = 0; b < g.B; ++b)
                     if (P[g0 + j][b]) tally(LV_PTMUL, l, nb);  // one diagonal product per member
             if (!bj.empty()) {
                 Ct rs = moddown_rescale(blk, l, nb * (int)bj.size());
-                std::vector<u64> gs;
-                for (int j : bj) gs.push_back(rot_galois(-(int)g.giant[g0 + j]));
+                std::vector<u64> gv;
+                for (int j : bj) gv.push_back(rot_galois(-(int)g.giant[g0 + j]));
                 // the only accumulation of the group: one chunk, and no other giant step of it rotated
-                bool sole = g.G <= kLinG && dh_n == 0;
+                bool sole = g.G <= kLinG && gs.n == 0;
                 for (int j = 0; j < gn && sole; ++j)
                     if (!in_blk[j] && any[j] && dh && g.giant[g0 + j]) sole = false;
-                giant_accumulate_many(rs, gs, nb, dh_acc, dh_c0, dh_n, dh_ys, sole);
+                H.own(rs);
+                giant_accumulate_many(H, rs, gv, nb, gs, sole);
+                H.disown(rs);
                 release(rs);
-                untmp(blk, bj.size() * 2 * (size_t)ne * nb);
+                H.put(blk);
             }
             for (int j = 0; j < gn; ++j) {
                 const int gg = g0 + j;
                 if (in_blk[j]) {
-                    if (m.out0[j]) untmp(m.out0[j], 2 * (size_t)nl * nb);
-                    if (m.out1[j]) untmp(m.out1[j], 2 * (size_t)nl * nb);
+                    H.put(m.out0[j]), H.put(m.out1[j]);
                     continue;
                 }
                 if (any[j]) {
@@ -4527,7 +4537,9 @@ public:
                         release(inner);
                     }
                     if (dh && g.giant[gg]) {
-                        giant_accumulate(rs, rot_galois(-(int)g.giant[gg]), dh_acc, dh_c0, dh_n);
+                        H.own(rs);
+                        giant_accumulate(H, rs, rot_galois(-(int)g.giant[gg]), gs);
+                        H.disown(rs);
                         release(rs);
                         continue_giant = true;
                     }
@@ -4547,117 +4559,102 @@ public:
                         out = s2;
                     }
                 }
-                if (m.out0[j]) untmp(m.out0[j], 2 * (size_t)nl * nb);
-                if (m.out1[j]) untmp(m.out1[j], 2 * (size_t)nl * nb);
-                if (m.outp[j]) untmp(m.outp[j], 2 * (size_t)ne * nb);
+                H.put(m.out0[j]), H.put(m.out1[j]), H.put(m.outp[j]);
             }
         }
-        for (int b = 1; b < g.B; ++b) {
-            if (u[b]) untmp(u[b], 2 * (size_t)ne * nb);
-        }
-        if (ext) untmp(ext, (size_t)nb * ext_rows(l));
-        if (dh_n > 0) {
-            const int lv = l - 1, r = hp_.nl(lv), ne2 = r + np;
+        for (int b = 1; b < g.B; ++b) H.put(u[b]);
+        H.drop_ext();
+        if (gs.n > 0) {
+            const int lv = l - 1, r = hp_.nl(lv);
             const size_t ms = (size_t)2 * r * n;
             const u32* add1 = nullptr;
             if (have) {  // the unrotated giant step: c0 into the sum, c1 as the second addend
                 if (out.level != lv || pm(out) != 2 || out.pend) throw std::runtime_error("lin_group: unrotated part off level");
-                for (int mb = 0; mb < nb; ++mb) launch_add(S(), T_, dh_c0 + mb * ms, dh_c0 + mb * ms, out.data + mb * ms, r, r, qmap());
+                for (int mb = 0; mb < nb; ++mb) launch_add(S(), T_, gs.c0 + mb * ms, gs.c0 + mb * ms, out.data + mb * ms, r, r, qmap());
                 add1 = out.data + (size_t)r * n;
             }
-            Ct res = moddown(dh_acc, lv, dh_c0, add1, nb, ms, nullptr, nullptr, false, dh_ys);
-            if (dh_ys) untmp(dh_ys, 2 * (size_t)np * nb), dh_ys = nullptr;
+            Ct res = moddown(gs.acc, lv, gs.c0, add1, nb, ms, nullptr, nullptr, false, gs.ys);
+            H.put(gs.ys);
             if (have) release(out);
-            untmp(dh_acc, 2 * (size_t)ne2 * nb);
-            untmp(dh_c0, 2 * (size_t)r * nb);
+            H.put(gs.acc), H.put(gs.c0);
             out = res;
         }
         return out;
     }
+    // the running sums of a double-hoisted group's rotated giant steps (rows of lin_group's Hoist): the key inner
+    // products in Q*P, the permuted c0s (member stride 2 r N), the fused-core form's P rows, the steps summed so far
+    struct GiantSum {
+        u32 *acc = nullptr, *c0 = nullptr, *ys = nullptr;
+        int n = 0;
+    };
     // K rotated giant steps at once: rs holds K x nb stacked members ([j][b]), step j permuted
     // by X -> X^gals[j]; their c1 ModUp'ed together (chunks within kMaxConvGroups), each key
-    // inner product accumulated into acc, the permuted c0 summed into c0sum per member
+    // inner product accumulated into s.acc, the permuted c0 summed into s.c0 per member; rows come from `own`
     // sole: no other giant step of the group is accumulated (lin_group): the fused-core form may run.
     // AESFHE_FUSED_GIANT=0 turns it off: the full-slot bootstrap's groups take it (batch leg 11,551 ->
     // 11,407 launches per step, 4,984-5,000 -> 5,055-5,056 blocks/s, profiles/r4_ab_giant_batch.txt),
     // C2's sparse plans do not; bit-identical (tests/test_gpu_fused_giant.py)
+    // single (giant_accumulate, K = 1): the first adopts its permuted buffer as s.c0 (no launch), a later one adds
+    // per member (launch_add); never the fused-core form, and not a call the test hook counts
     bool fused_giant_ = !(std::getenv("AESFHE_FUSED_GIANT") && std::atoi(std::getenv("AESFHE_FUSED_GIANT")) == 0);
     int test_fail_giant_ = env_int("AESFHE_TEST_FAIL_GIANT", 0);
-    // ys (out): set by the fused form to the P rows after the INTT row pass, for the caller's ModDown
-    void giant_accumulate_many(const Ct& rs, const std::vector<u64>& gals, int nb, u32*& acc, u32*& c0sum, int& count, u32*& ys,
-                               bool sole = false) {
-        const int K = (int)gals.size(), lv = rs.level, r = hp_.nl(lv), ne2 = r + hp_.n_p, n = hp_.n;
+    void giant_accumulate_many(Guard& own, const Ct& rs, const std::vector<u64>& gals, int nb, GiantSum& s, bool sole = false,
+                               bool single = false) {
+        const int K = (int)gals.size(), lv = rs.level, n = hp_.n;
+        const KsGeom k = ks_geom(lv);
+        const int r = k.nl;
         const size_t ms = (size_t)2 * r * n;
-        if (rs.nb != K * nb || K > kMaxMembers) throw std::runtime_error("giant_accumulate_many: batch shape");
-        // test hook (tests/test_gpu_flag_identity.py): the k-th call of the process fails, after
-        // its group allocated its accumulators -- the next bootstrap must not see any of that group's state
-        if (test_fail_giant_ > 0 && --test_fail_giant_ == 0) throw std::runtime_error("giant_accumulate_many: test failure (AESFHE_TEST_FAIL_GIANT)");
-        u32* perm = tmp(2 * (size_t)r * nb * K);
+        if (!single) {
+            if (rs.nb != K * nb || K > kMaxMembers) throw std::runtime_error("giant_accumulate_many: batch shape");
+            // test hook (tests/test_gpu_flag_identity.py): the k-th call of the process fails, after
+            // its group allocated its accumulators -- the next bootstrap must not see any of that group's state
+            if (test_fail_giant_ > 0 && --test_fail_giant_ == 0) throw std::runtime_error("giant_accumulate_many: test failure (AESFHE_TEST_FAIL_GIANT)");
+        }
+        u32* perm = own.get(2 * (size_t)r * nb * K);
         for (int j = 0; j < K; ++j) launch_automorph(S(), T_, perm + (size_t)j * nb * ms, rs.data + (size_t)j * nb * ms, gals[j], 2 * r * nb);
-        if (!acc) acc = tmp(2 * (size_t)ne2 * nb);
-        const int nd = (r + hp_.alpha - 1) / hp_.alpha;
-        const int per = std::max(1, std::min(kMaxConvGroups / (nd * nb), kMaxKsBatch));  // steps per ModUp
-        if (sole && count == 0 && fused_ki_ok() && fused_giant_ && K <= kMaxKiSrc && per >= K) {
+        if (!s.acc) s.acc = own.get(2 * (size_t)k.ne * nb);
+        const int per = std::max(1, std::min(kMaxConvGroups / (k.nd * nb), kMaxKsBatch));  // steps per ModUp
+        auto c1_of = [&](int j) { return perm + (size_t)j * nb * ms + (size_t)r * n; };
+        if (sole && !single && s.n == 0 && fused_ki_ok() && fused_giant_ && K <= kMaxKiSrc && per >= K) {
             // the group's only accumulation: the K key inner products summed in ONE fused-core launch
             // (multi-source k_ntt2_ki: each step's ModUp row pass in registers, no ext written), the P
             // rows through the ModDown INTT's row pass into ys for lin_group's ModDown
-            const u32* c1 = perm + (size_t)r * n;
-            u32* ext = modup(c1, lv, nb * K, ms, nullptr, false, true);
-            const size_t er = (size_t)ext_rows(lv) * n;
+            Hoist X(*this, c1_of(0), lv, nb * K, ms, true);
             KiSrc src[kMaxKiSrc];
-            for (int j = 0; j < K; ++j) src[j] = KiSrc{ext + (size_t)j * nb * er, perm + (size_t)j * nb * ms + (size_t)r * n, ksk(gals[j])};
-            ys = tmp(2 * (size_t)hp_.n_p * nb);
-            ki_core(acc, ys, lv, r, nb, src, K, ms, KsFold{});
-            untmp(ext, (size_t)nb * K * ext_rows(lv));
+            for (int j = 0; j < K; ++j) src[j] = KiSrc{X.ext + (size_t)j * nb * k.ext_ms, c1_of(j), ksk(gals[j])};
+            s.ys = own.get(2 * (size_t)k.np * nb);
+            ki_core(s.acc, s.ys, lv, r, nb, src, K, ms, KsFold{});
         }
-        for (int j0 = 0; j0 < K && !ys; j0 += per) {
-            const int k = std::min(per, K - j0);
-            const u32* c1 = perm + (size_t)j0 * nb * ms + (size_t)r * n;
-            u32* ext = modup(c1, lv, nb * k, ms);
-            const size_t er = (size_t)ext_rows(lv) * n;
-            for (int j = j0; j < j0 + k; ++j) {
-                key_inner(acc, ext + (size_t)(j - j0) * nb * er, perm + (size_t)j * nb * ms + (size_t)r * n, ksk(gals[j]), lv, 0, nb, ms, KsFold{},
-                          count > 0 || j > 0);
+        for (int j0 = 0; j0 < K && !s.ys; j0 += per) {
+            const int kk = std::min(per, K - j0);
+            Hoist X(*this, c1_of(j0), lv, nb * kk, ms);
+            for (int j = j0; j < j0 + kk; ++j)
+                key_inner(s.acc, X.ext + (size_t)(j - j0) * nb * k.ext_ms, c1_of(j), ksk(gals[j]), lv, 0, nb, ms, KsFold{}, s.n > 0 || j > 0);
+        }
+        if (single && !s.c0) {
+            s.c0 = perm;  // the first permuted buffer is the sum
+        } else if (single) {
+            for (int mb = 0; mb < nb; ++mb) launch_add(S(), T_, s.c0 + mb * ms, s.c0 + mb * ms, perm + mb * ms, r, r, qmap());
+            own.put(perm);
+        } else {
+            const bool fresh = s.c0 == nullptr;
+            if (fresh) s.c0 = own.get(2 * (size_t)r * nb);
+            for (int b = 0; b < nb; ++b) {
+                MemberPtrs mp;
+                for (int j = 0; j < K; ++j) mp.src[j] = perm + ((size_t)j * nb + b) * ms;
+                launch_add_members(S(), T_, s.c0 + (size_t)b * ms, mp, K, r, qmap(), !fresh);
             }
-            untmp(ext, (size_t)nb * k * ext_rows(lv));
+            own.put(perm);
         }
-        const bool fresh = c0sum == nullptr;
-        if (fresh) c0sum = tmp(2 * (size_t)r * nb);
-        for (int b = 0; b < nb; ++b) {
-            MemberPtrs mp;
-            for (int j = 0; j < K; ++j) mp.src[j] = perm + ((size_t)j * nb + b) * ms;
-            launch_add_members(S(), T_, c0sum + (size_t)b * ms, mp, K, r, qmap(), !fresh);
-        }
-        untmp(perm, 2 * (size_t)r * nb * K);
-        count += K;
+        s.n += K;
         cnt_[C_ROT] += K * nb;
         cnt_[C_KS] += K * nb;
         tally(LV_KS, lv, K * nb);
     }
-    // one rotated giant step of a double-hoisted group: rs permuted by X -> X^gal, its c1
-    // key switched into the running Q*P sum acc (allocated on the first call), its c0 summed
-    // into c0sum (the first permuted buffer, member stride 2 r N)
-    void giant_accumulate(const Ct& rs, u64 gal, u32*& acc, u32*& c0sum, int& count) {
+    // one rotated giant step of a double-hoisted group on its own: the K = 1, single form (rs's nb members)
+    void giant_accumulate(Guard& own, const Ct& rs, u64 gal, GiantSum& s) {
         if (vis_npoly(rs) != 2 || rs.pend || rs.lazy) throw std::runtime_error("giant_accumulate: canonical input expected");
-        const int lv = rs.level, r = hp_.nl(lv), ne2 = r + hp_.n_p, nb = rs.nb, n = hp_.n;
-        const size_t ms = (size_t)2 * r * n;
-        u32* perm = tmp(2 * (size_t)r * nb);
-        launch_automorph(S(), T_, perm, rs.data, gal, 2 * r * nb);
-        const u32* p1 = perm + (size_t)r * n;
-        u32* ext = modup(p1, lv, nb, ms);
-        if (!acc) acc = tmp(2 * (size_t)ne2 * nb);
-        key_inner(acc, ext, p1, ksk(gal), lv, 0, nb, ms, KsFold{}, count > 0);
-        untmp(ext, (size_t)nb * ext_rows(lv));
-        if (count == 0) {
-            c0sum = perm;
-        } else {
-            for (int mb = 0; mb < nb; ++mb) launch_add(S(), T_, c0sum + mb * ms, c0sum + mb * ms, perm + mb * ms, r, r, qmap());
-            untmp(perm, 2 * (size_t)r * nb);
-        }
-        ++count;
-        cnt_[C_ROT] += nb;
-        cnt_[C_KS] += nb;
-        tally(LV_KS, lv, nb);
+        giant_accumulate_many(own, rs, {gal}, rs.nb, s, false, true);
     }
 
     Ct lin_transform(const Ct& in, std::vector<BootGroupDev>& groups) {
@@ -5214,7 +5211,7 @@ public:
         // 4. back to the dense secret (sparse: fused into the first trace step, s2d_trace4)
         const size_t tms = (size_t)2 * nlt * n;
         const bool fuse_s2d = sv && s2d_trace_ && trace4_ && 4 * sv->n <= slot_count() && stop_after != 12;
-        Ct u = fuse_s2d ? s2d_trace4(raised, sv->n)
+        Ct u = fuse_s2d ? trace4(raised, sv->n, true)
                         : keyswitch(raised.data + (size_t)nlt * n, top, ksk_at(tag_s2d(), top), raised.data, nullptr, nb, tms, tms);
         release(raised);
         if (stop_after == 12) return u;  // debug: back on the dense secret, before the sparse trace

@@ -3,7 +3,12 @@ run_ks): shared by tests/test_gpu_fused_ki.py (fused against separate launches) 
 (the residues, levels, launches and counters pinned against tests/golden/keyswitch_digests.json).
 
 operations(E, sparse) yields (name, [results]) one operation at a time: an operation runs when the generator is
-advanced to it, so a caller can take counters around each.  run(E, sparse) is the flat list of exported bytes."""
+advanced to it, so a caller can take counters around each.  run(E, sparse) is the flat list of exported bytes.
+
+hoisted_operations(E, boot) is the second list, of the same form: the hoisted and accumulating key switches (one
+ModUp for several inner products, sums across calls; csrc/engine.hip Hoist, giant_accumulate_many), pinned against
+tests/golden/hoisted_digests.json.  It is a list of its own so that the first list's encryptions, and so its
+digests, stay where they are."""
 import numpy as np
 
 
@@ -28,6 +33,38 @@ def operations(E, sparse: bool):
         P = 32
         z = np.exp(2j * np.pi * rng.random(P))
         yield "bootstrap_sparse32", [E.bootstrap_sparse(E.encrypt(np.tile(z, E.slot_count // P)), P)]
+
+
+def hoisted_operations(E, boot):
+    """boot: False (no bootstrap), True, or "only" (the full-slot and the sparse bootstrap alone: the log N 16 cases)"""
+    rng = np.random.default_rng(29)
+    sc = E.slot_count
+    zs = [np.exp(2j * np.pi * rng.random(sc)) for _ in range(6)]
+    if boot == "only":
+        yield "bootstrap", [E.bootstrap(E.encrypt(0.5 * zs[0]))]
+        yield "bootstrap_sparse32", [E.bootstrap_sparse(E.encrypt(np.tile(zs[1][:32], sc // 32)), 32)]
+        return
+    a, b, f0, f1, f2 = (E.encrypt(z) for z in zs[:5])
+    yield "rotate_hoisted", E.rotate_many(a, [1, 0, -3, 1])              # a zero step and a repeat
+    rot, conj = E.galois_rotate, E.galois_conj
+    p0, p1 = E._raw_mul(a, 0.5 + 0.25j), E._raw_mul(b, 0.25 - 0.5j)      # deferred scalar products: stacked rescale,
+    low = E.level_down(E.encrypt(zs[5]), a.level - 2)                    # sources at a regular stride; a second chunk
+    yield "galois_multi", E.galois_multi([
+        (a, rot(1)), (a, rot(-5)), (a, conj), (b, conj), (a, 1),         # one source three times, a second, identity
+        (p0, rot(2)), (p1, rot(7)), (low, rot(3)),
+        (f2, rot(4)), (f0, conj), (f1, rot(-2))])                        # unrelated sources, out of order: gathered c1
+    own = [(np.arange(sc) % 3 == i).astype(np.complex128) for i in range(3)]
+    m = [E.encode(v) for v in own]
+    yield "rot_pt_sum1", E.rot_pt_sum(a, [0, 3, -5], [m])
+    yield "rot_pt_sum2", E.rot_pt_sum(b, [0, 3, -5], [[m[0], m[1], m[2]], [m[1], None, None]])  # the second: unrotated only
+    fill = E.encode(np.exp(2j * np.pi * rng.integers(0, 16, sc) / 16))
+    yield "rot_pt_affine", E.rot_pt_affine(a, [0, 16, -7], [[m[2], m[0], m[1]]], [fill])
+    if boot:
+        P = 32
+        tiled = [np.tile(np.exp(2j * np.pi * rng.random(P)), sc // P) for _ in range(3)]
+        yield "bootstrap", [E.bootstrap(E.encrypt(0.5 * zs[0]))]
+        yield "bootstrap_sparse32", [E.bootstrap_sparse(E.encrypt(tiled[0]), P)]       # trace steps: s2d_trace4, trace4
+        yield "bootstrap_pair_sparse32", list(E.bootstrap_pair_sparse(E.encrypt(tiled[1]), E.encrypt(tiled[2]), P))  # nb = 2
 
 
 def exported(E, results):

@@ -7,7 +7,14 @@ setting of AESFHE_FUSED_KI x AESFHE_CONJ_REV (log N 13) and of AESFHE_BX_COLS (l
 
 The A/B tests (test_gpu_fused_ki, test_gpu_conj_rev, test_gpu_bx_cols) compare two settings of one build with each
 other; these compare each setting with its own past, which also sees a launch more or a counter less.  One engine
-per case, so a case is one test; a failure names the first operation that differs."""
+per case, so a case is one test; a failure names the first operation that differs.
+
+The hoisted and accumulating key switches (csrc/engine.hip Hoist, giant_accumulate_many) are pinned the same way by
+the second list, hoisted_operations, against tests/golden/hoisted_digests.json: hoisted rotations with a zero step
+and a repeat, one galois_multi call over shared, stacked, gathered and lower-level sources, rot_pt_sum / rot_pt_affine,
+and the full-slot, sparse and paired sparse bootstraps -- by default and with each of AESFHE_S2D_TRACE,
+AESFHE_GIANT_BATCH, AESFHE_FUSED_GIANT, AESFHE_FUSED_BABY, AESFHE_DOUBLE_HOIST off (log N 13), and the log N 16
+bootstraps whose groups take the fused-core giant steps."""
 import json
 import sys
 from pathlib import Path
@@ -19,9 +26,10 @@ if str(ROOT / "tools") not in sys.path:
     sys.path.insert(0, str(ROOT / "tools"))
 
 import keyswitch_digest as ksd  # noqa: E402
-from keyswitch_ops import operations  # noqa: E402  (tests/helpers: the tool put it on the path)
+from keyswitch_ops import hoisted_operations, operations  # noqa: E402  (tests/helpers: the tool put it on the path)
 
 GOLDEN = json.loads((ROOT / "tests" / "golden" / "keyswitch_digests.json").read_text())
+HOISTED = json.loads((ROOT / "tests" / "golden" / "hoisted_digests.json").read_text())
 
 
 def test_golden_covers_every_case():
@@ -47,3 +55,33 @@ def test_keyswitch_bit_identical(case):
     assert sorted(got) == sorted(want)
     for name in got:  # in the order the operations ran: the first difference is the one to look at
         assert got[name] == want[name], f"first differing operation: {name} (golden of {GOLDEN['parent']})"
+
+
+def test_hoisted_golden_covers_every_case():
+    """no GPU: the second golden file holds every case of the hoisted list, each case every operation its engine runs
+    (the bootstraps only where the engine has one; the log N 16 cases the two bootstraps alone), and the record itself
+    shows that each switch reaches a path of its own: its case differs from the default's in a launch count"""
+    import inspect
+    import re
+    assert HOISTED["parent"] == "3e58fd4" and sorted(HOISTED["cases"]) == sorted(ksd.HOISTED_CASES)
+    ops = re.findall(r'yield "(\w+)"', inspect.getsource(hoisted_operations))[2:]  # after the two of boot == "only"
+    assert len(ops) == 8 and ops[5:] == ["bootstrap", "bootstrap_sparse32", "bootstrap_pair_sparse32"]
+    for case, (_, boot, _) in ksd.HOISTED_CASES.items():
+        rec = HOISTED["cases"][case]
+        assert sorted(rec) == sorted(ops[5:7] if boot == "only" else ops if boot else ops[:5]), case
+        for name, r in rec.items():
+            assert sorted(r) == ["counters", "launches", "level", "sha256"] and r["launches"] > 0, (case, name)
+    launches = {c: {n: r["launches"] for n, r in rec.items()} for c, rec in HOISTED["cases"].items()}
+    for sw in ("s2d_trace", "giant_batch", "fused_baby", "double_hoist"):
+        assert launches[f"n13_boot_{sw}0"] != launches["n13_boot"], sw
+    assert launches["n16_boot_fused_giant0"] != launches["n16_boot"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(ksd.HOISTED_CASES))
+def test_hoisted_bit_identical(case):
+    want = HOISTED["cases"][case]
+    got = ksd.case_digests(case, "hoisted")
+    assert sorted(got) == sorted(want)
+    for name in got:  # in the order the operations ran: the first difference is the one to look at
+        assert got[name] == want[name], f"first differing operation: {name} (golden of {HOISTED['parent']})"

@@ -5,6 +5,9 @@ a stack one by one), the results' levels, and what the operation added to the pr
 every engine counter (--golden COMMIT: in the form of tests/golden/keyswitch_digests.json, recorded from a build of
 that commit).  tests/test_gpu_keyswitch_digest.py compares the result with that file.
 
+--list hoisted: the same record of the second list, hoisted_operations -- the hoisted and accumulating key switches
+(Hoist, giant_accumulate_many) -- over HOISTED_CASES, in the form of tests/golden/hoisted_digests.json.
+
 An operation is measured together with the export of its results: calls are deferred by default, and an export
 settles what a result still owes (a lazy product's relinearisation runs there).
 
@@ -21,7 +24,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT / "tests" / "helpers"), str(ROOT), str(ROOT / "aes-implementation-fhe_amd")]
 
 import mi355x_ckks  # noqa: E402
-from keyswitch_ops import exported, operations  # noqa: E402
+from keyswitch_ops import exported  # noqa: E402
 
 
 def _boot13():
@@ -54,9 +57,32 @@ CASES["n16_default"] = (_ring16, False, _env())
 CASES["n16_bx_cols"] = (_ring16, False, _env(bx="1"))
 
 
-def case_digests(case: str) -> dict:
+# the second list: the default, and each switch that alone reaches a path -- trace4 from the first trace step, the
+# single giant_accumulate, the unfused giant_accumulate_many loop, materialised baby steps, the non-double-hoisted ends
+HOISTED_SWITCHES = ("AESFHE_S2D_TRACE", "AESFHE_GIANT_BATCH", "AESFHE_FUSED_GIANT", "AESFHE_FUSED_BABY", "AESFHE_DOUBLE_HOIST")
+
+
+def _henv(off=None):
+    return {**_env(), **{k: "0" if k == off else "1" for k in HOISTED_SWITCHES}}
+
+
+HOISTED_CASES = {"n13_deep": (_deep13, False, _henv()), "n13_boot": (_boot13, True, _henv())}
+for _k in HOISTED_SWITCHES:
+    HOISTED_CASES["n13_boot_" + _k[len("AESFHE_"):].lower() + "0"] = (_boot13, True, _henv(_k))
+# log N 16: the only ring whose plans reach the fused-core form of giant_accumulate_many (a group's sole accumulation)
+HOISTED_CASES["n16_boot"] = (_ring16, "only", _henv())
+HOISTED_CASES["n16_boot_fused_giant0"] = (_ring16, "only", _henv("AESFHE_FUSED_GIANT"))
+
+# list -> (cases, the generator's name in tests/helpers/keyswitch_ops.py: looked up when a list is run, so the tool
+# loads beside a helper that has only the first list)
+LISTS = {"keyswitch": (CASES, "operations"), "hoisted": (HOISTED_CASES, "hoisted_operations")}
+
+
+def case_digests(case: str, which: str = "keyswitch") -> dict:
     """{operation: {"sha256", "level", "launches", "counters"}} in the order the operations ran"""
-    make, sparse, env = CASES[case]
+    import keyswitch_ops
+    cases, gen = LISTS[which]
+    make, sparse, env = cases[case]
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
@@ -69,7 +95,7 @@ def case_digests(case: str) -> dict:
             else:
                 os.environ[k] = v
     out = {}
-    ops = operations(E, sparse)
+    ops = getattr(keyswitch_ops, gen)(E, sparse)
     while True:
         l0, c0 = mi355x_ckks.launch_count(), E.counters()
         try:
@@ -86,20 +112,20 @@ def case_digests(case: str) -> dict:
 
 
 def main():
-    """[LIB.so] [--golden COMMIT] [--cases A,B]: the golden file's form, naming the commit the library was built from"""
+    """[LIB.so] [--list keyswitch|hoisted] [--golden COMMIT] [--cases A,B]: the golden file's form, naming the commit
+    the library was built from"""
     args = sys.argv[1:]
-    commit, cases = None, list(CASES)
-    for flag in ("--golden", "--cases"):
+    opt = {}
+    for flag in ("--list", "--golden", "--cases"):
         if flag in args:
             i = args.index(flag)
-            if flag == "--golden":
-                commit = args[i + 1]
-            else:
-                cases = args[i + 1].split(",")
+            opt[flag] = args[i + 1]
             del args[i:i + 2]
+    which, commit = opt.get("--list", "keyswitch"), opt.get("--golden")
+    cases = opt["--cases"].split(",") if "--cases" in opt else list(LISTS[which][0])
     if args:
         mi355x_ckks.load_library(Path(args[0]))
-    got = {c: case_digests(c) for c in cases}
+    got = {c: case_digests(c, which) for c in cases}
     print(json.dumps({"parent": commit, "cases": got} if commit else got, indent=1, sort_keys=True), flush=True)
 
 
