@@ -2593,10 +2593,9 @@ public:
         const int nd = (hp_.nl(level) + hp_.alpha - 1) / hp_.alpha;
         return std::max(1, std::min(kMaxKsBatch, kMaxConvGroups / nd));
     }
-    bool fused_relin_rescale_ok(const Ct& c) {
-        if (!fuse_rr_ || pm(c) != 3 || c.pend < 1 || c.level < 1 || c.zero) return false;
-        return kb(c.level).mdr && 2 * ks_chunk(c.level) <= kMaxConvGroups;
-    }
+    // the level's part of the question: it has the fused ModDown's tables and a chunk's two polynomials fit one conversion
+    bool fused_relin_rescale_at(int level) { return fuse_rr_ && level >= 1 && kb(level).mdr && 2 * ks_chunk(level) <= kMaxConvGroups; }
+    bool fused_relin_rescale_ok(const Ct& c) { return pm(c) == 3 && c.pend >= 1 && !c.zero && fused_relin_rescale_at(c.level); }
     // a stack of more than ks_chunk members goes through in chunks (run_ks)
     // outm (nb <= ks_chunk): member m's result straight into outm[m]; the returned Ct has no data
     Ct relin_rescale(const Ct& c, u32* const* outm = nullptr) {
@@ -2664,112 +2663,33 @@ public:
         return run_moddown(s, acc, nb, dst, outm, ys_in);
     }
 
-    // ct x ct.  Inputs are brought to canonical form; the tensor owes one rescale.  relin:
-    // key switch now (eager) or leave it to the first consumer that needs two polynomials
-    // (lazy)
-    // aff (relin, not lazy): the product's 2 P - 1 (EvalMod's 2 T^2 - 1) instead of P -- in the
-    // relinearisation's finish when it is fused (Affine), else one lincomb after it
-    Ct mul(const Ct& a_in, const Ct& b_in, bool relin, bool lazy = false, bool aff = false) {
-        if (vis_npoly(a_in) != 2 || vis_npoly(b_in) != 2) throw std::runtime_error("multiply expects 2-polynomial ciphertexts");
-        if (a_in.level - a_in.pend < 1 || b_in.level - b_in.pend < 1)
-            throw std::runtime_error("not enough level to multiply (level 0)");
-        Ct a = normalize(a_in);
-        Ct b = b_in.data == a_in.data ? a : normalize(b_in);
-        const bool oa = a.data != a_in.data, ob = b.data != b_in.data && b.data != a.data;
-        bool fa, fb;
-        auto xy = align(a, b, fa, fb, true);
-        const Ct &x = xy.first, &y = xy.second;
-        const int nl = hp_.nl(x.level);
-        if (x.nb != y.nb) throw std::runtime_error("multiply: batched operands of different sizes");
-        if (relin && !lazy && fused_tensor_ && !fused_conv(true) && x.nb <= std::min(ks_chunk(x.level), kMaxKsBatch)) {
-            Ct probe;
-            probe.level = x.level, probe.npoly = 3 * x.nb, probe.nb = x.nb, probe.pend = 1, probe.ntt = true;
-            if (fused_relin_rescale_ok(probe)) {  // relinearised and rescaled straight from the factors (relin_rescale_tensor)
-                Ct o = alloc_ct(x.level - 1, 2 * x.nb, x.nb);
-                o.ntt = true, o.pend = 0, o.lazy = false;
-                TensorPtrs tp;
-                u32* om[kMaxKsBatch];
-                const size_t ms = (size_t)2 * nl * hp_.n, oms = (size_t)2 * hp_.nl(x.level - 1) * hp_.n;
-                Affine af;
-                for (int m = 0; m < x.nb; ++m) {
-                    tp.a[m] = x.data + m * ms, tp.b[m] = y.data + m * ms, om[m] = o.data + m * oms;
-                    if (aff) af.dbl |= 1u << m, af.cst[m] = affine_const(x.level - 1, 1.0);
-                }
-                relin_rescale_tensor(tp, x.level, x.nb, om, aff ? &af : nullptr);
-                cnt_[C_MUL]++;
-                tally(LV_MUL, o.level + 1, o.nb);
-                if (fa) release(x);
-                if (fb && y.data != x.data) release(y);
-                if (oa) release(a);
-                if (ob) release(b);
-                return o;
-            }
-        }
-        Ct d = alloc_ct(x.level, 3 * x.nb, x.nb);
-        d.pend = 1;
-        launch_tensor(S(), T_, d.data, x.data, y.data, nl, qmap(), x.nb);
-        if (fa) release(x);
-        if (fb && y.data != x.data) release(y);
-        if (oa) release(a);
-        if (ob) release(b);
-        cnt_[C_MUL]++;
-        tally(LV_MUL, d.level, d.nb);
-        if (!relin) return d;
-        if (lazy) {
-            d.lazy = true;
-            return d;
-        }
-        Ct o;
-        if (fused_relin_rescale_ok(d)) {
-            o = relin_rescale(d);
-            release(d);
-        } else {
-            Ct r = relin_raw(d);
-            release(d);
-            o = rescale(r);
-            release(r);
-        }
-        if (!aff) return o;
-        Ct t = lincomb(o, 2, nullptr, 0, -1.0, 0.0);
-        release(o);
-        return t;
+    // ------------------------------------------------------------------ ct x ct products
+    // One preparation of the operands (mul_operands) and one relinearised, rescaled product of the pairs aligned at
+    // one level (mul_eager): mul is one pair, mul_many its same-level groups.
+    static void mul_check(const Ct& a, const Ct& b) {
+        if (vis_npoly(a) != 2 || vis_npoly(b) != 2) throw std::runtime_error("multiply expects 2-polynomial ciphertexts");
+        if (a.level - a.pend < 1 || b.level - b.pend < 1) throw std::runtime_error("not enough level to multiply (level 0)");
+        if (a.nb != b.nb) throw std::runtime_error("multiply: batched operands of different sizes");
     }
-
-    // n independent products a_i b_i, relinearised and rescaled, batched:
-    // pairs whose aligned operands sit at one level share ONE tensor launch and one fused
-    // relinearisation + rescale per chunk of kMaxKsBatch members (each key residue read once
-    // per chunk, every launch carrying the chunk's rows); the results equal n mul() calls
-    // aff (nullable, one flag per pair): that product's 2 P - 1 (mul's aff)
-    std::vector<Ct> mul_many(const std::vector<const Ct*>& A, const std::vector<const Ct*>& B, const std::vector<char>* aff = nullptr) {
+    struct MulPair {
+        Ct x, y;  // canonical, NTT form, at the product's level; one buffer for a squared pair
+    };
+    // The operands of n products: every pair checked, brought to canonical form and to its product's level (as
+    // align(..., for_mul): never across the region boundary), counted.  An operand that several factors share is
+    // converted once, and the exact-scale drops of operands at one (level, owed rescales) to one target are batched:
+    // ONE copy-and-scale launch and ONE limb drop for the group (convert_many) instead of one convert each.
+    // owned: what was made here, for the caller to release once the products' launches are queued (stream-ordered).
+    std::vector<MulPair> mul_operands(const std::vector<const Ct*>& A, const std::vector<const Ct*>& B, std::vector<Ct>& owned) {
         const int n = (int)A.size();
-        std::vector<Ct> out(n);
-        auto affi = [&](int i) { return aff && (*aff)[i]; };
-        bool batch = batch_ops_ && n >= 2;
+        for (int i = 0; i < n; ++i) mul_check(*A[i], *B[i]);
+        std::vector<MulPair> pr(n);
         for (int i = 0; i < n; ++i) {
-            if (vis_npoly(*A[i]) != 2 || vis_npoly(*B[i]) != 2) throw std::runtime_error("multiply expects 2-polynomial ciphertexts");
-            if (A[i]->level - A[i]->pend < 1 || B[i]->level - B[i]->pend < 1)
-                throw std::runtime_error("not enough level to multiply (level 0)");
-            batch = batch && A[i]->nb == 1 && B[i]->nb == 1;
+            MulPair& P = pr[i];
+            P.x = normalize(*A[i]);
+            if (P.x.data != A[i]->data) owned.push_back(P.x);
+            P.y = B[i]->data == A[i]->data ? P.x : normalize(*B[i]);
+            if (P.y.data != B[i]->data && P.y.data != P.x.data) owned.push_back(P.y);
         }
-        if (!batch) {
-            for (int i = 0; i < n; ++i) out[i] = mul(*A[i], *B[i], true, false, affi(i));
-            return out;
-        }
-        struct Prep {
-            Ct a, b, x, y;
-        };
-        std::vector<Prep> pr(n);
-        std::vector<Ct> owned;  // normalised inputs and level-aligned copies, released after the tensors
-        for (int i = 0; i < n; ++i) {
-            Prep& P = pr[i];
-            P.a = normalize(*A[i]);
-            if (P.a.data != A[i]->data) owned.push_back(P.a);
-            P.b = B[i]->data == A[i]->data ? P.a : normalize(*B[i]);
-            if (P.b.data != B[i]->data && P.b.data != P.a.data) owned.push_back(P.b);
-        }
-        // level alignment of every pair (as align(..., for_mul)), the exact-scale drops of inputs at one
-        // (level, owed rescales) to one target batched: ONE copy-and-scale launch and ONE limb drop
-        // for the group (convert_many) instead of one convert each
         struct Need {
             const Ct* src;
             int t;
@@ -2785,32 +2705,28 @@ public:
         };
         std::vector<int> wa(n), wb(n);
         for (int i = 0; i < n; ++i) {
-            int lv = std::min(pr[i].a.level - pr[i].a.pend, pr[i].b.level - pr[i].b.pend);
+            int lv = std::min(pr[i].x.level - pr[i].x.pend, pr[i].y.level - pr[i].y.pend);
             if (!hp_.homogeneous(lv)) --lv;
-            wa[i] = want(pr[i].a, lv);
-            wb[i] = want(pr[i].b, lv);
+            wa[i] = want(pr[i].x, lv);
+            wb[i] = want(pr[i].y, lv);
         }
+        const int gmax = n > 1 ? kMaxMembers : 1;  // one pair's two drops stay two converts (align's)
         std::vector<bool> conv_done(needs.size(), false);
         for (size_t j = 0; j < needs.size(); ++j) {
             if (conv_done[j]) continue;
             const Ct& c = *needs[j].src;
             std::vector<size_t> grp{j};
-            for (size_t k = j + 1; k < needs.size() && (int)grp.size() < kMaxMembers; ++k) {
+            for (size_t k = j + 1; k < needs.size() && (int)grp.size() < gmax; ++k) {
                 const Ct& d = *needs[k].src;
                 if (!conv_done[k] && needs[k].t == needs[j].t && d.level == c.level && d.pend == c.pend && d.npoly == c.npoly &&
                     d.nb == 1 && c.nb == 1 && d.ntt && c.ntt)
                     grp.push_back(k);
             }
             for (size_t k : grp) conv_done[k] = true;
-            if (grp.size() == 1) {
-                needs[j].res = level_down(c, needs[j].t);
-                owned.push_back(needs[j].res);
-                continue;
-            }
             std::vector<const Ct*> srcs;
             for (size_t k : grp) srcs.push_back(needs[k].src);
             Ct st;
-            if (!convert_many(srcs, needs[j].t, 0, st)) {  // no batched form: one convert each
+            if (grp.size() == 1 || !convert_many(srcs, needs[j].t, 0, st)) {  // alone, or no batched form: one convert each
                 for (size_t k : grp) {
                     needs[k].res = level_down(*needs[k].src, needs[k].t);
                     owned.push_back(needs[k].res);
@@ -2825,81 +2741,144 @@ public:
                 needs[grp[m]].res = v;
             }
         }
-        for (int i = 0; i < n; ++i) {
-            pr[i].x = wa[i] < 0 ? pr[i].a : needs[wa[i]].res;
-            pr[i].y = wb[i] < 0 ? pr[i].b : needs[wb[i]].res;
+        for (int i = 0; i < n; ++i) {  // (every need's source has been read by now)
+            if (wa[i] >= 0) pr[i].x = needs[wa[i]].res;
+            if (wb[i] >= 0) pr[i].y = needs[wb[i]].res;
+            tally(LV_MUL, pr[i].x.level, pr[i].x.nb);
         }
+        cnt_[C_MUL] += n;
+        return pr;
+    }
+    // p <- 2 p - 1, one launch (where the product's own finish does not carry it)
+    void twice_minus_one(Ct& p) {
+        Ct t = lincomb(p, 2, nullptr, 0, -1.0, 0.0);
+        release(p);
+        p = t;
+    }
+    // THE eager product: the pairs pr[idx[i]], i < np, aligned at one level L, relinearised and rescaled into
+    // out[idx[i]] at L - 1.  Its members are the np pairs (single ciphertexts, np <= kMaxMembers: one launch reads them
+    // through their pointers, each result a ciphertext of its own) or, contiguous, the rows of ONE pair of stacks of any
+    // size (the stacked kernels, one stacked result).  Three forms:
+    //   straight from the factors (relin_rescale_tensor; AESFHE_FUSED_TENSOR=0 and a stack wider than a chunk: not),
+    //   the tensor, then the fused relin_rescale (a stack whole: run_ks chunks it; AESFHE_FUSED_RESCALE=0: not),
+    //   the tensor, then relin_raw and rescale.
+    // aff (nullable, indexed as out): that product's 2 P - 1 (EvalMod's 2 T^2 - 1) -- in the relinearisation's finish
+    // when it runs from the factors (Affine), else one launch after it
+    void mul_eager(const MulPair* pr, const int* idx, int np, bool contiguous, const char* aff, Ct* out) {
+        const Ct& x0 = pr[idx[0]].x;
+        const int L = x0.level, nl = hp_.nl(L), g = contiguous ? x0.nb : np, ch = ks_chunk(L);
+        const size_t rn = (size_t)nl * hp_.n, ms = 2 * rn, oms = (size_t)2 * hp_.nl(L - 1) * hp_.n;
+        auto xm = [&](int m) { return contiguous ? x0.data + m * ms : pr[idx[m]].x.data; };
+        auto ym = [&](int m) { return contiguous ? pr[idx[0]].y.data + m * ms : pr[idx[m]].y.data; };
+        auto res = [&](int m) -> Ct& { return out[idx[contiguous ? 0 : m]]; };
+        u32* om[kMaxKsBatch];
+        auto outputs = [&](int m0, int c) {  // fresh results of members m0 .. m0 + c - 1 (a stack: all of them), their rows in om
+            for (int m = 0; m < c; ++m) {
+                Ct& r = res(m0 + m);
+                if (!contiguous || m == 0) {
+                    r = contiguous ? alloc_ct(L - 1, 2 * c, c) : alloc_ct(L - 1, 2);
+                    r.ntt = true, r.pend = 0, r.lazy = false;
+                }
+                om[m] = contiguous ? r.data + m * oms : r.data;
+            }
+        };
+        if (fused_tensor_ && !fused_conv(true) && fused_relin_rescale_at(L) && (!contiguous || g <= ch)) {
+            for (int m0 = 0; m0 < g; m0 += ch) {
+                const int c = std::min(ch, g - m0);
+                TensorPtrs tp;
+                Affine af;
+                outputs(m0, c);
+                for (int m = 0; m < c; ++m) {
+                    tp.a[m] = xm(m0 + m), tp.b[m] = ym(m0 + m);
+                    if (aff && aff[idx[contiguous ? 0 : m0 + m]]) af.dbl |= 1u << m, af.cst[m] = affine_const(L - 1, 1.0);
+                }
+                relin_rescale_tensor(tp, L, c, om, af.any() ? &af : nullptr);
+            }
+            return;
+        }
+        Ct d = alloc_ct(L, 3 * g, g);
+        d.pend = 1;
+        if (contiguous) {
+            launch_tensor(S(), T_, d.data, xm(0), ym(0), nl, qmap(), g);
+        } else {
+            TensorPtrs tp;
+            for (int m = 0; m < g; ++m) tp.a[m] = xm(m), tp.b[m] = ym(m);
+            launch_tensor_ptrs(S(), T_, d.data, tp, g, nl, qmap());
+        }
+        const int step = contiguous ? g : ch;
+        for (int m0 = 0; m0 < g; m0 += step) {
+            const int c = std::min(step, g - m0);
+            Ct v = d;  // view of members m0 .. m0 + c - 1 (not released on its own)
+            v.data = d.data + m0 * 3 * rn, v.npoly = 3 * c, v.nb = c, v.words = c * 3 * rn;
+            if (fused_relin_rescale_ok(v)) {
+                if (contiguous) {
+                    res(0) = relin_rescale(v);
+                } else {  // each member's ModDown finish writes its own output buffer: no unstack copy
+                    outputs(m0, c);
+                    relin_rescale(v, om);
+                }
+                continue;
+            }
+            Ct r = relin_raw(v);
+            Ct o = rescale(r);
+            release(r);
+            if (contiguous) {
+                res(0) = o;
+            } else {
+                unstack(o, out, idx + m0);
+                release(o);
+            }
+        }
+        release(d);
+        for (int i = 0; i < np; ++i)
+            if (aff && aff[idx[i]]) twice_minus_one(out[idx[i]]);
+    }
+
+    // ct x ct.  relin, not lazy: the eager product.  Else the tensor alone, owing one rescale: unrelinearised, or
+    // (lazy) its key switch left to the first consumer that needs two polynomials
+    // aff (relin, not lazy): 2 P - 1 instead of P (mul_eager)
+    Ct mul(const Ct& a, const Ct& b, bool relin, bool lazy = false, bool aff = false) {
+        std::vector<Ct> owned;
+        const MulPair p = mul_operands({&a}, {&b}, owned)[0];
+        const int i0 = 0;
+        const char af = aff;
+        Ct o;
+        if (relin && !lazy) {
+            mul_eager(&p, &i0, 1, true, &af, &o);
+        } else {
+            o = alloc_ct(p.x.level, 3 * p.x.nb, p.x.nb);
+            o.pend = 1, o.lazy = relin;
+            launch_tensor(S(), T_, o.data, p.x.data, p.y.data, hp_.nl(p.x.level), qmap(), p.x.nb);
+        }
+        for (const Ct& c : owned) release(c);
+        return o;
+    }
+    // n independent products a_i b_i, relinearised and rescaled, batched: pairs whose aligned
+    // operands sit at one level, up to kMaxMembers of them, are ONE eager product -- each key residue read once per
+    // chunk of ks_chunk members, every launch carrying the chunk's rows.  Stacked operands, a lone pair and
+    // AESFHE_BATCH_OPS=0: one mul per pair
+    // aff (nullable, one flag per pair): mul's aff
+    std::vector<Ct> mul_many(const std::vector<const Ct*>& A, const std::vector<const Ct*>& B, const std::vector<char>* aff = nullptr) {
+        const int n = (int)A.size();
+        std::vector<Ct> out(n);
+        bool batch = batch_ops_ && n >= 2;
+        for (int i = 0; i < n; ++i) batch = batch && A[i]->nb == 1 && B[i]->nb == 1;
+        if (!batch) {
+            for (int i = 0; i < n; ++i) mul_check(*A[i], *B[i]);  // every pair, before the first product
+            for (int i = 0; i < n; ++i) out[i] = mul(*A[i], *B[i], true, false, aff && (*aff)[i]);
+            return out;
+        }
+        std::vector<Ct> owned;
+        const std::vector<MulPair> pr = mul_operands(A, B, owned);
         std::vector<bool> done(n, false);
         for (int i = 0; i < n; ++i) {
             if (done[i]) continue;
-            std::vector<int> grp;  // members at the same level, up to kMaxMembers
+            std::vector<int> grp;  // the pairs at this level, up to kMaxMembers
             for (int j = i; j < n && (int)grp.size() < kMaxMembers; ++j)
                 if (!done[j] && pr[j].x.level == pr[i].x.level) grp.push_back(j), done[j] = true;
-            const int g = (int)grp.size(), L = pr[i].x.level, nl = hp_.nl(L), nn = hp_.n;
-            TensorPtrs tp;
-            for (int m = 0; m < g; ++m) tp.a[m] = pr[grp[m]].x.data, tp.b[m] = pr[grp[m]].y.data;
-            const int chunk = ks_chunk(L);
-            {  // every chunk relinearised and rescaled straight from its factors (relin_rescale_tensor)
-                Ct probe;
-                probe.level = L, probe.npoly = 3 * std::min(chunk, g), probe.nb = std::min(chunk, g), probe.pend = 1, probe.ntt = true;
-                if (fused_tensor_ && !fused_conv(true) && fused_relin_rescale_ok(probe)) {
-                    cnt_[C_MUL] += g;
-                    tally(LV_MUL, L, g);
-                    for (int m0 = 0; m0 < g; m0 += chunk) {
-                        const int c = std::min(chunk, g - m0);
-                        TensorPtrs sub;
-                        u32* om[kMaxKsBatch];
-                        Affine af;
-                        for (int m = 0; m < c; ++m) {
-                            sub.a[m] = tp.a[m0 + m], sub.b[m] = tp.b[m0 + m];
-                            Ct& r = out[grp[m0 + m]];
-                            r = alloc_ct(L - 1, 2);
-                            r.ntt = true, r.pend = 0, r.lazy = false;
-                            om[m] = r.data;
-                            if (affi(grp[m0 + m])) af.dbl |= 1u << m, af.cst[m] = affine_const(L - 1, 1.0);
-                        }
-                        relin_rescale_tensor(sub, L, c, om, af.any() ? &af : nullptr);
-                    }
-                    continue;
-                }
-            }
-            Ct d = alloc_ct(L, 3 * g, g);
-            d.pend = 1;
-            launch_tensor_ptrs(S(), T_, d.data, tp, g, nl, qmap());
-            cnt_[C_MUL] += g;
-            tally(LV_MUL, L, g);
-            for (int m0 = 0; m0 < g; m0 += chunk) {
-                const int c = std::min(chunk, g - m0);
-                Ct v = d;  // view of members m0 .. m0 + c - 1 (not released on its own)
-                v.data = d.data + (size_t)m0 * 3 * nl * nn, v.npoly = 3 * c, v.nb = c, v.words = (size_t)3 * c * nl * nn;
-                if (fused_relin_rescale_ok(v)) {
-                    // each member's ModDown finish writes its own output buffer: no unstack copy
-                    u32* om[kMaxKsBatch];
-                    for (int m = 0; m < c; ++m) {
-                        Ct& r = out[grp[m0 + m]];
-                        r = alloc_ct(L - 1, 2);
-                        r.ntt = true, r.pend = 0, r.lazy = false;
-                        om[m] = r.data;
-                    }
-                    Ct o = relin_rescale(v, om);
-                    (void)o;
-                } else {
-                    Ct r = relin_raw(v);
-                    Ct o = rescale(r);
-                    release(r);
-                    unstack(o, &out[0], grp.data() + m0);
-                    release(o);
-                }
-            }
-            release(d);
-            for (int m = 0; m < g; ++m)  // the tensor-first form: 2 P - 1 as its own launch
-                if (affi(grp[m])) {
-                    Ct t = lincomb(out[grp[m]], 2, nullptr, 0, -1.0, 0.0);
-                    release(out[grp[m]]);
-                    out[grp[m]] = t;
-                }
+            mul_eager(pr.data(), grp.data(), (int)grp.size(), false, aff ? aff->data() : nullptr, out.data());
         }
-        for (const Ct& c : owned) release(c);  // stream-ordered: the tensors above were queued first
+        for (const Ct& c : owned) release(c);
         return out;
     }
     // convert(c, t, p) of several ciphertexts at one (data level, owed rescales, polys): ONE
@@ -4865,12 +4844,18 @@ public:
         return out;
     }
     bool cheb_sched_ = env_int("AESFHE_CHEB_SCHED", 1) != 0;
-    // products of a list of pairs: one batched multiply (AESFHE_EVALMOD_BATCH=0: one at a time)
-    std::vector<Ct> mul_list(const std::vector<const Ct*>& A, const std::vector<const Ct*>& B, const std::vector<char>* aff = nullptr) {
+    // the products of a list of pairs, the flagged ones (dbl, nullable) finished as 2 P - 1: by the product itself
+    // (mul's aff), or with AESFHE_FUSED_AFFINE=0 one launch each after a plain product.  One batched multiply
+    // (AESFHE_EVALMOD_BATCH=0: one at a time)
+    std::vector<Ct> mul_list(const std::vector<const Ct*>& A, const std::vector<const Ct*>& B, const std::vector<char>* dbl = nullptr) {
         static const bool batch = env_int("AESFHE_EVALMOD_BATCH", 1) != 0;
-        if (batch) return mul_many(A, B, aff);
+        const std::vector<char>* aff = fused_affine_ ? dbl : nullptr;
         std::vector<Ct> P(A.size());
-        for (size_t j = 0; j < A.size(); ++j) P[j] = mul(*A[j], *B[j], true, false, aff && (*aff)[j]);
+        if (batch) P = mul_many(A, B, aff);
+        else
+            for (size_t j = 0; j < A.size(); ++j) P[j] = mul(*A[j], *B[j], true, false, aff && (*aff)[j]);
+        for (size_t j = 0; dbl && !aff && j < A.size(); ++j)
+            if ((*dbl)[j]) twice_minus_one(P[j]);
         return P;
     }
     static constexpr int kBabyDeg = 8;
@@ -4892,40 +4877,28 @@ public:
         for (int lo = 2; lo <= kBabyDeg;) {
             const int hi = batch_baby ? std::min(kBabyDeg, 2 * lo - 2) : lo;
             std::vector<const Ct*> A, B;
-            std::vector<char> aff;  // 2 T_a^2 - 1 in the product's own relinearisation (fused_affine_)
+            std::vector<char> sq;  // T_a^2: the product comes back as 2 T_a^2 - 1 = T_k
             for (int i = 0; i < ni; ++i)
-                for (int k = lo; k <= hi; ++k)
-                    A.push_back(&T[i][(k + 1) / 2]), B.push_back(&T[i][k / 2]), aff.push_back(fused_affine_ && (k + 1) / 2 == k / 2);
-            std::vector<Ct> P = mul_list(A, B, &aff);
+                for (int k = lo; k <= hi; ++k) A.push_back(&T[i][(k + 1) / 2]), B.push_back(&T[i][k / 2]), sq.push_back((k + 1) / 2 == k / 2);
+            std::vector<Ct> P = mul_list(A, B, &sq);
             int j = 0;
             for (int i = 0; i < ni; ++i)
                 for (int k = lo; k <= hi; ++k, ++j) {
-                    const int a = (k + 1) / 2, b = k / 2;
-                    // 2 T_a T_b - T_(a-b) (a > b) / 2 T_a^2 - 1, one launch each (none for the latter when fused)
-                    if (aff[j]) {
-                        T[i][k] = P[j];
-                        continue;
-                    }
-                    T[i][k] = (a == b) ? lincomb(P[j], 2, nullptr, 0, -1.0, 0.0) : lincomb(P[j], 2, &T[i][a - b], -1, 0.0, 0.0);
+                    T[i][k] = P[j];
+                    if (sq[j]) continue;
+                    T[i][k] = lincomb(P[j], 2, &T[i][(k + 1) / 2 - k / 2], -1, 0.0, 0.0);  // 2 T_a T_b - T_(a-b), one launch
                     release(P[j]);
                 }
             lo = hi + 1;
         }
+        const std::vector<char> all(ni, 1);
         std::vector<std::map<int, Ct>> giant(ni);
         for (int i = 0; i < ni; ++i) giant[i][kBabyDeg] = T[i][kBabyDeg];
         for (int m = 2 * kBabyDeg; m <= d; m *= 2) {
             std::vector<const Ct*> A;
             for (int i = 0; i < ni; ++i) A.push_back(&giant[i].at(m / 2));
-            const std::vector<char> aff(ni, fused_affine_ ? 1 : 0);
-            std::vector<Ct> P = mul_list(A, A, &aff);
-            for (int i = 0; i < ni; ++i) {
-                if (fused_affine_) {
-                    giant[i][m] = P[i];
-                    continue;
-                }
-                giant[i][m] = lincomb(P[i], 2, nullptr, 0, -1.0, 0.0);  // 2 T^2 - 1, one launch
-                release(P[i]);
-            }
+            std::vector<Ct> P = mul_list(A, A, &all);  // 2 T^2 - 1
+            for (int i = 0; i < ni; ++i) giant[i][m] = P[i];
         }
         std::vector<int> in(ni);
         for (int i = 0; i < ni; ++i) in[i] = i;
@@ -4939,16 +4912,10 @@ public:
         for (int it = 0; it < bs_.plan.r; ++it) {
             std::vector<const Ct*> A;
             for (int i = 0; i < ni; ++i) A.push_back(&g[i]);
-            const std::vector<char> aff(ni, fused_affine_ ? 1 : 0);
-            std::vector<Ct> P = mul_list(A, A, &aff);
+            std::vector<Ct> P = mul_list(A, A, &all);  // the double angle 2 g^2 - 1
             for (int i = 0; i < ni; ++i) {
                 release(g[i]);
-                if (fused_affine_) {
-                    g[i] = P[i];
-                    continue;
-                }
-                g[i] = lincomb(P[i], 2, nullptr, 0, -1.0, 0.0);  // double angle 2 g^2 - 1, one launch
-                release(P[i]);
+                g[i] = P[i];
             }
         }
         return g;

@@ -8,7 +8,10 @@ advanced to it, so a caller can take counters around each.  run(E, sparse) is th
 hoisted_operations(E, boot) is the second list, of the same form: the hoisted and accumulating key switches (one
 ModUp for several inner products, sums across calls; csrc/engine.hip Hoist, giant_accumulate_many), pinned against
 tests/golden/hoisted_digests.json.  It is a list of its own so that the first list's encryptions, and so its
-digests, stay where they are."""
+digests, stay where they are.
+
+product_operations(E, boot) is the third, again with an rng of its own: the ciphertext x ciphertext products (csrc/engine.hip
+mul, mul_many, and through them the power basis and EvalMod), pinned against tests/golden/product_digests.json."""
 import numpy as np
 
 
@@ -65,6 +68,47 @@ def hoisted_operations(E, boot):
         yield "bootstrap", [E.bootstrap(E.encrypt(0.5 * zs[0]))]
         yield "bootstrap_sparse32", [E.bootstrap_sparse(E.encrypt(tiled[0]), P)]       # trace steps: s2d_trace4, trace4
         yield "bootstrap_pair_sparse32", list(E.bootstrap_pair_sparse(E.encrypt(tiled[1]), E.encrypt(tiled[2]), P))  # nb = 2
+
+
+def product_operations(E, boot):
+    """the ciphertext x ciphertext products (csrc/engine.hip mul, mul_many and what drives them): the undeferred calls,
+    so that each operation is the engine call it names.  boot: the engine has the bootstrap (EvalMod's 2 P - 1 flags)"""
+    rng = np.random.default_rng(31)
+    sc = E.slot_count
+    zs = [np.exp(2j * np.pi * rng.random(sc)) for _ in range(6)]
+    a, b, c, d, e = (E.encrypt(z) for z in zs[:5])
+    low = E.level_down(E.encrypt(zs[5]), a.level - 2)
+    p = E._raw_mul(a, 0.5 + 0.25j)                                       # a deferred scalar product: owes a rescale
+    st3, st10 = E.stack([a, b, c]), E.stack([a, b, c, d, e, a, c, e, b, d])
+    E.set_lazy(False)
+    yield "mul", [E._raw_mul(a, b)]
+    yield "mul_squared", [E._raw_mul(a, a)]
+    yield "mul_level_down", [E._raw_mul(a, low)]
+    yield "mul_pending", [E._raw_mul(a, p)]
+    yield "mul_stack3", [E._raw_mul(st3, st3)]                           # one key-switch chunk where the level allows
+    yield "mul_stack10", [E._raw_mul(st10, st10)]                        # more than a chunk: the tensor first
+    yield "mul_tensor", [E._raw_mul(a, b, relin=False)]                  # three polynomials
+    E.set_lazy(True)
+    yield "mul_lazy_add", [E._raw_add(E._raw_mul(a, b), c)]              # the add settles the product (normalize)
+    yield "many1", E.multiply_many([(a, b)])
+    yield "many3", E.multiply_many([(a, b), (b, c), (c, d)])
+    yield "many10", E.multiply_many([(a, b), (a, c), (a, d), (a, e), (b, c), (b, d), (b, e), (c, d), (c, e), (d, e)])
+    yield "many_two_levels", E.multiply_many([(a, b), (low, c), (d, e)])
+    yield "many_level_down", E.multiply_many([(low, a), (low, b), (c, low)])  # three drops to one level: convert_many
+    yield "many_squared", E.multiply_many([(a, a), (b, c)])
+    yield "many_with_stack", E.multiply_many([(st3, st3), (a, b)])       # a stacked operand: one mul per pair
+    yield "power_basis5", E.make_power_basis(a, 5)
+    if boot:
+        yield "bootstrap", [E.bootstrap(E.encrypt(0.5 * zs[0]))]
+        yield "bootstrap_sparse32", [E.bootstrap_sparse(E.encrypt(np.tile(zs[1][:32], sc // 32)), 32)]
+        limbs = E.level_limbs
+        double = [l for l in range(1, len(limbs)) if limbs[l] - limbs[l - 1] == 2]
+        if double:  # the first double-prime level: a product of operands there is formed one level below
+            lv = double[0]                   # (nothing encrypts that high: uniform residues imported there)
+            q = E.moduli()[:E.nl(lv)]
+            x = E.import_ct(np.array([[rng.integers(0, int(m), E.n) for m in q] for _ in range(2)], np.uint32), lv)
+            E.set_lazy(False)
+            yield "mul_squared_boundary", [E._raw_mul(x, x)]
 
 
 def exported(E, results):

@@ -14,7 +14,14 @@ the second list, hoisted_operations, against tests/golden/hoisted_digests.json: 
 and a repeat, one galois_multi call over shared, stacked, gathered and lower-level sources, rot_pt_sum / rot_pt_affine,
 and the full-slot, sparse and paired sparse bootstraps -- by default and with each of AESFHE_S2D_TRACE,
 AESFHE_GIANT_BATCH, AESFHE_FUSED_GIANT, AESFHE_FUSED_BABY, AESFHE_DOUBLE_HOIST off (log N 13), and the log N 16
-bootstraps whose groups take the fused-core giant steps."""
+bootstraps whose groups take the fused-core giant steps.
+
+The ciphertext x ciphertext products (csrc/engine.hip mul, mul_many) are the third list, product_operations, against
+tests/golden/product_digests.json: single, squared, level-dropped, deferred and stacked operands (within and beyond one
+key-switch chunk), the unrelinearised and the lazy product, multiply_many of one pair, several, more than a group, two
+levels, shared level drops, a squared pair and a stacked operand, the power basis, and on the bootstrappable engine
+the full-slot and sparse bootstraps (EvalMod's 2 P - 1) and a square at the first double-prime level -- by default and
+with each of AESFHE_FUSED_TENSOR, AESFHE_FUSED_RESCALE, AESFHE_BATCH_OPS, AESFHE_FUSED_AFFINE off."""
 import json
 import sys
 from pathlib import Path
@@ -26,10 +33,11 @@ if str(ROOT / "tools") not in sys.path:
     sys.path.insert(0, str(ROOT / "tools"))
 
 import keyswitch_digest as ksd  # noqa: E402
-from keyswitch_ops import hoisted_operations, operations  # noqa: E402  (tests/helpers: the tool put it on the path)
+from keyswitch_ops import hoisted_operations, operations, product_operations  # noqa: E402  (tests/helpers: the tool put it on the path)
 
 GOLDEN = json.loads((ROOT / "tests" / "golden" / "keyswitch_digests.json").read_text())
 HOISTED = json.loads((ROOT / "tests" / "golden" / "hoisted_digests.json").read_text())
+PRODUCTS = json.loads((ROOT / "tests" / "golden" / "product_digests.json").read_text())
 
 
 def test_golden_covers_every_case():
@@ -85,3 +93,33 @@ def test_hoisted_bit_identical(case):
     assert sorted(got) == sorted(want)
     for name in got:  # in the order the operations ran: the first difference is the one to look at
         assert got[name] == want[name], f"first differing operation: {name} (golden of {HOISTED['parent']})"
+
+
+def test_product_golden_covers_every_case():
+    """no GPU: the third golden file holds every case of the product list, each case every operation its engine runs
+    (the bootstraps and the double-prime square only on the bootstrappable engine), and the record itself shows that
+    each switch reaches a path of its own: its case differs from its engine's default in a launch count"""
+    import inspect
+    import re
+    assert PRODUCTS["parent"] == "6534c24" and sorted(PRODUCTS["cases"]) == sorted(ksd.PRODUCT_CASES)
+    ops = re.findall(r'yield "(\w+)"', inspect.getsource(product_operations))
+    assert len(ops) == 19 and ops[16:] == ["bootstrap", "bootstrap_sparse32", "mul_squared_boundary"]
+    for case, (_, boot, _) in ksd.PRODUCT_CASES.items():
+        rec = PRODUCTS["cases"][case]
+        assert sorted(rec) == sorted(ops if boot else ops[:16]), case
+        for name, r in rec.items():
+            assert sorted(r) == ["counters", "launches", "level", "sha256"] and r["launches"] > 0, (case, name)
+    launches = {c: {n: r["launches"] for n, r in rec.items()} for c, rec in PRODUCTS["cases"].items()}
+    for case in ksd.PRODUCT_CASES:
+        default = case[:len("n13_deep")]  # n13_deep / n13_boot
+        assert case == default or launches[case] != launches[default], case
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(ksd.PRODUCT_CASES))
+def test_product_bit_identical(case):
+    want = PRODUCTS["cases"][case]
+    got = ksd.case_digests(case, "products")
+    assert sorted(got) == sorted(want)
+    for name in got:  # in the order the operations ran: the first difference is the one to look at
+        assert got[name] == want[name], f"first differing operation: {name} (golden of {PRODUCTS['parent']})"

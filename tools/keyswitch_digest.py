@@ -8,6 +8,9 @@ that commit).  tests/test_gpu_keyswitch_digest.py compares the result with that 
 --list hoisted: the same record of the second list, hoisted_operations -- the hoisted and accumulating key switches
 (Hoist, giant_accumulate_many) -- over HOISTED_CASES, in the form of tests/golden/hoisted_digests.json.
 
+--list products: the third list, product_operations -- the ciphertext x ciphertext products (mul, mul_many, the power
+basis, EvalMod) -- over PRODUCT_CASES, in the form of tests/golden/product_digests.json.
+
 An operation is measured together with the export of its results: calls are deferred by default, and an export
 settles what a result still owes (a lazy product's relinearisation runs there).
 
@@ -73,9 +76,25 @@ for _k in HOISTED_SWITCHES:
 HOISTED_CASES["n16_boot"] = (_ring16, "only", _henv())
 HOISTED_CASES["n16_boot_fused_giant0"] = (_ring16, "only", _henv("AESFHE_FUSED_GIANT"))
 
+# the third list, the products: the default, and each switch of the product path on the engine where it reaches a path of
+# its own -- the tensor first, relinearisation and rescale apart, one mul per pair, EvalMod's 2 P - 1 as a lincomb
+PRODUCT_SWITCHES = ("AESFHE_FUSED_TENSOR", "AESFHE_FUSED_RESCALE", "AESFHE_BATCH_OPS", "AESFHE_FUSED_AFFINE")
+
+
+def _penv(off=None):
+    return {**_env(), **{k: "0" if k == off else "1" for k in PRODUCT_SWITCHES}}
+
+
+PRODUCT_CASES = {"n13_deep": (_deep13, False, _penv()), "n13_boot": (_boot13, True, _penv())}
+for _k in PRODUCT_SWITCHES[:3]:
+    PRODUCT_CASES["n13_deep_" + _k[len("AESFHE_"):].lower() + "0"] = (_deep13, False, _penv(_k))
+for _k in ("AESFHE_FUSED_AFFINE", "AESFHE_FUSED_TENSOR"):
+    PRODUCT_CASES["n13_boot_" + _k[len("AESFHE_"):].lower() + "0"] = (_boot13, True, _penv(_k))
+
 # list -> (cases, the generator's name in tests/helpers/keyswitch_ops.py: looked up when a list is run, so the tool
 # loads beside a helper that has only the first list)
-LISTS = {"keyswitch": (CASES, "operations"), "hoisted": (HOISTED_CASES, "hoisted_operations")}
+LISTS = {"keyswitch": (CASES, "operations"), "hoisted": (HOISTED_CASES, "hoisted_operations"),
+         "products": (PRODUCT_CASES, "product_operations")}
 
 
 def case_digests(case: str, which: str = "keyswitch") -> dict:
@@ -112,7 +131,7 @@ def case_digests(case: str, which: str = "keyswitch") -> dict:
 
 
 def main():
-    """[LIB.so] [--list keyswitch|hoisted] [--golden COMMIT] [--cases A,B]: the golden file's form, naming the commit
+    """[LIB.so] [--list keyswitch|hoisted|products] [--golden COMMIT] [--cases A,B]: the golden file's form, naming the commit
     the library was built from"""
     args = sys.argv[1:]
     opt = {}
