@@ -529,7 +529,22 @@ public:
     bool fused_conv(bool up) const { return (ntt_conv_fused_mask(T_) >> (up ? 0 : 1)) & 1; }
 
     // ------------------------------------------------------------------ keys
+    // An evaluation-only context (aesfhe_create_eval) holds the public key and the switching keys
+    // it was given (import_pk / import_ksk) and no secret: d_s_ and d_ssp_ stay null for its whole life.  Every path
+    // that would read the secret refuses (need_secret), a key it was not given is an error, never a generation
+    // (key_missing); both are thrown before the path allocates, or inside a scope that releases what it took
+    bool eval_only_ = false;
+    void set_eval_only() { eval_only_ = true; }
+    bool has_secret() const { return !eval_only_; }
+    void need_secret(const char* who) const {
+        if (eval_only_) throw std::runtime_error(std::string(who) + ": no secret key (this is an evaluation-only context)");
+    }
+    [[noreturn]] void key_missing(u64 g, int level) const {
+        throw std::runtime_error("evaluation key missing: galois " + std::to_string(g) + ", level " + std::to_string(level) +
+                                 " (-1: the full key); export it from the keyed context and import it");
+    }
     void keygen() {
+        need_secret("keygen");
         const int n = hp_.n, nt = hp_.n_tot();
         if (!d_s_) {
             d_s_ = dev_alloc((size_t)nt * n);
@@ -588,6 +603,7 @@ public:
     }
     const u32* ksk_d2s() {
         const u64 g = tag_d2s();
+        if (eval_only_) key_missing(g, -1);
         const int n = hp_.n, ne = kD2sQ + d2s_np();
         void* raw = nullptr;
         HIP_OK(hipMalloc(&raw, ksk_words(g) * sizeof(u32)));
@@ -608,6 +624,7 @@ public:
     const u32* ksk(u64 g) {
         auto it = ksk_.find(g);
         if (it != ksk_.end()) return it->second;
+        if (eval_only_) key_missing(g, -1);
         if (!d_s_) throw std::runtime_error("keys not generated");
         if (g == tag_d2s()) return ksk_d2s();
         const int n = hp_.n, nks = hp_.n_ks, np = hp_.n_p, nkey = nks + np;
@@ -643,6 +660,7 @@ public:
         const auto id = std::make_pair(g, level);
         auto it = ksk_low_.find(id);
         if (it != ksk_low_.end()) return it->second;
+        if (eval_only_) key_missing(g, level);
         if (!d_s_) throw std::runtime_error("keys not generated");
         if (g == tag_d2s()) throw std::runtime_error("ksk_at: the dense -> sparse key has its own basis");
         const KsBasis& B = kb(level);
@@ -667,6 +685,7 @@ public:
     std::map<std::pair<u64, int>, u32*> ksk_low_;
     // source secret s' of the key of tag g on Q limbs 0..n_ks-1 (tmp; the caller untmps n_ks rows)
     u32* key_source(u64 g) {
+        need_secret("key_source");
         const int n = hp_.n, nks = hp_.n_ks;
         u32* sp = tmp(nks);
         if (g == 0) {
@@ -801,6 +820,7 @@ public:
     // and owed rescales are folded into the returned scale raw_scale(level, pend); the CRT
     // uses the fewest limbs (2..4) whose product exceeds that scale by 2^26
     double decrypt_coeffs(const Ct& c_in, std::vector<double>& m) {
+        need_secret("decrypt");
         const int n = hp_.n;
         Ct c = ensure_ntt(c_in);
         const int nl = hp_.nl(c.level);
@@ -3073,51 +3093,60 @@ public:
         //    stacked and rescaled together
         std::map<int, std::vector<const Ct*>> lazy1;
         std::vector<bool> done(n, false);
-        for (int i = 0; i < n; ++i) {
-            const Ct& c = *C[i];
-            if (vis_npoly(c) != 2) throw std::runtime_error("rotation/conjugation expects a 2-polynomial ciphertext");
-            // conjugations of deferred tensors stay deferred, exactly as conjugate() does them (§3.14)
-            if (G[i] == conj_galois() && lazy_galois_ok(c)) {
-                out[i] = galois_lazy(c, G[i]);
-                done[i] = true;
-                continue;
-            }
-            if (src_of.count(c.data)) continue;
-            if (c.lazy && c.pend == 1 && pm(c) == 2 && c.nb == 1 && c.ntt && !c.zero) {
-                auto& v = lazy1[c.level];
-                if (std::find(v.begin(), v.end(), &c) == v.end()) v.push_back(&c);
-                src_of[c.data] = KsSrc{nullptr, nullptr, -1};  // filled below
-                continue;
-            }
-            Ct cn = normalize(c);
-            if (cn.data != c.data) owned.push_back(cn);
-            src_of[c.data] = KsSrc{cn.data, cn.data + (size_t)hp_.nl(cn.level) * nn, cn.level};
-        }
-        for (auto& kv : lazy1) {
-            const auto& v = kv.second;
-            for (size_t m0 = 0; m0 < v.size(); m0 += kMaxMembers) {
-                const int cnt = (int)std::min<size_t>(kMaxMembers, v.size() - m0), l = kv.first, nl = hp_.nl(l);
-                if (cnt == 1) {
-                    Ct cn = normalize(*v[m0]);
-                    owned.push_back(cn);
-                    src_of[v[m0]->data] = KsSrc{cn.data, cn.data + (size_t)hp_.nl(cn.level) * nn, cn.level};
+        try {
+            for (int i = 0; i < n; ++i) {
+                const Ct& c = *C[i];
+                if (vis_npoly(c) != 2) throw std::runtime_error("rotation/conjugation expects a 2-polynomial ciphertext");
+                // conjugations of deferred tensors stay deferred, exactly as conjugate() does them (§3.14)
+                if (G[i] == conj_galois() && lazy_galois_ok(c)) {
+                    out[i] = galois_lazy(c, G[i]);
+                    done[i] = true;
                     continue;
                 }
-                Ct st = alloc_ct(l, 2 * cnt, cnt);
-                MemberPtrs mp;
-                for (int m = 0; m < cnt; ++m) mp.src[m] = v[m0 + m]->data, mp.dst[m] = st.data + (size_t)m * 2 * nl * nn;
-                launch_copy_members(S(), T_, mp, cnt, 2 * nl);
-                st.pend = 1;
-                st.lazy = true;
-                Ct rs = rescale(st);  // one rescale of all members (rescale handles npoly = 2 cnt)
-                release(st);
-                owned.push_back(rs);
-                const int nlo = hp_.nl(rs.level);
-                for (int m = 0; m < cnt; ++m) {
-                    const u32* c0 = rs.data + (size_t)m * 2 * nlo * nn;
-                    src_of[v[m0 + m]->data] = KsSrc{c0, c0 + (size_t)nlo * nn, rs.level};
+                if (src_of.count(c.data)) continue;
+                if (c.lazy && c.pend == 1 && pm(c) == 2 && c.nb == 1 && c.ntt && !c.zero) {
+                    auto& v = lazy1[c.level];
+                    if (std::find(v.begin(), v.end(), &c) == v.end()) v.push_back(&c);
+                    src_of[c.data] = KsSrc{nullptr, nullptr, -1};  // filled below
+                    continue;
+                }
+                Ct cn = normalize(c);
+                if (cn.data != c.data) owned.push_back(cn);
+                src_of[c.data] = KsSrc{cn.data, cn.data + (size_t)hp_.nl(cn.level) * nn, cn.level};
+            }
+            for (auto& kv : lazy1) {
+                const auto& v = kv.second;
+                for (size_t m0 = 0; m0 < v.size(); m0 += kMaxMembers) {
+                    const int cnt = (int)std::min<size_t>(kMaxMembers, v.size() - m0), l = kv.first, nl = hp_.nl(l);
+                    if (cnt == 1) {
+                        Ct cn = normalize(*v[m0]);
+                        owned.push_back(cn);
+                        src_of[v[m0]->data] = KsSrc{cn.data, cn.data + (size_t)hp_.nl(cn.level) * nn, cn.level};
+                        continue;
+                    }
+                    Ct st = alloc_ct(l, 2 * cnt, cnt);
+                    MemberPtrs mp;
+                    for (int m = 0; m < cnt; ++m) mp.src[m] = v[m0 + m]->data, mp.dst[m] = st.data + (size_t)m * 2 * nl * nn;
+                    launch_copy_members(S(), T_, mp, cnt, 2 * nl);
+                    st.pend = 1;
+                    st.lazy = true;
+                    Ct rs = rescale(st);  // one rescale of all members (rescale handles npoly = 2 cnt)
+                    release(st);
+                    owned.push_back(rs);
+                    const int nlo = hp_.nl(rs.level);
+                    for (int m = 0; m < cnt; ++m) {
+                        const u32* c0 = rs.data + (size_t)m * 2 * nlo * nn;
+                        src_of[v[m0 + m]->data] = KsSrc{c0, c0 + (size_t)nlo * nn, rs.level};
+                    }
                 }
             }
+            // every key of part 2 before its first output exists (an evaluation-only context may lack one)
+            for (int i = 0; i < n; ++i)
+                if (!done[i] && G[i] != 1) (void)ksk_at(G[i], src_of.at(C[i]->data).level);
+        } catch (...) {  // so far `owned` and the deferred conjugations' outputs are whole: back to the pool
+            for (const Ct& c : owned) release(c);
+            for (const Ct& c : out) release(c);
+            throw;
         }
         // 2. items by level, chunked: members <= kMaxMembers, sources x digits <= kMaxConvGroups
         std::map<int, std::vector<int>> by_level;
@@ -3236,6 +3265,8 @@ public:
         const int l = c.level, k = pm(c);
         const size_t rn = (size_t)hp_.nl(l) * hp_.n;
         const bool rev = conj_reversed(g);
+        const u32* key1 = ksk_at(g, l);  // both keys before anything is taken: a miss leaves nothing behind
+        const u32* key2 = k == 3 ? ksk_at(tag_sq(g), l) : nullptr;
         u32* perm = nullptr;
         if (!rev) {
             perm = tmp((size_t)k * hp_.nl(l));
@@ -3243,8 +3274,8 @@ public:
         }
         const u32* t = rev ? c.data : perm;
         KsJob j;
-        j.level = l, j.nsrc = k - 1, j.d[0] = t + rn, j.key[0] = ksk_at(g, l);
-        if (k == 3) j.d[1] = t + 2 * rn, j.key[1] = ksk_at(tag_sq(g), l);
+        j.level = l, j.nsrc = k - 1, j.d[0] = t + rn, j.key[0] = key1;
+        if (k == 3) j.d[1] = t + 2 * rn, j.key[1] = key2;
         j.rev = j.add_rev = rev, j.fold.rev_d = rev, j.separate = !rev;
         j.add0 = t;
         Ct o = run_ks(j);
@@ -3269,7 +3300,13 @@ public:
         Ct c = normalize(c_in);
         const int nl = hp_.nl(c.level);
         const size_t rn = (size_t)nl * hp_.n, ms = 2 * rn;  // ms: member stride of a batched ciphertext
-        const u32* key = ksk_at(g, c.level);
+        const u32* key = nullptr;
+        try {
+            key = ksk_at(g, c.level);
+        } catch (...) {
+            if (c.data != c_in.data) release(c);
+            throw;
+        }
         const bool rev = c.nb == 1 && conj_reversed(g);      // the conjugation as reversed reads (galois_lazy): no permuted copy
         u32* perm = nullptr;
         if (!rev) {
@@ -3297,6 +3334,8 @@ public:
         if (c.data != c_in.data) H.own(c);
         int nrot = 0;
         for (int st : steps) nrot += rot_mod(st) != 0;
+        for (int st : steps)  // every step's key before the first output exists: a miss leaves nothing behind
+            if (rot_mod(st) != 0) (void)ksk_at(rot_galois(st), c.level);
         if (c.nb != 1 || nrot < 2 || !batch_ops_) {
             for (size_t i = 0; i < steps.size(); ++i) out[i] = rotate(c, steps[i]);
             return out;
@@ -3603,6 +3642,7 @@ public:
     }
     // s^2 on the first four limbs (NTT form), for decrypting deferred 3-polynomial tensors
     const u32* s_sq4() {
+        need_secret("s_sq4");
         if (!d_s2_) {
             d_s2_ = dev_alloc((size_t)4 * hp_.n);
             launch_square(S(), T_, d_s2_, d_s_, std::min(4, hp_.n_tot()), 4, qmap());
@@ -3705,6 +3745,7 @@ public:
     // every validation, before any allocation or launch
     void renorm_check(const RenormSpec& sp) {
         using Shape = RenormSpec::Shape;
+        need_secret("renorm");
         if (!d_pk_) throw std::runtime_error("keys not generated");
         const bool one = sp.shape != Shape::Pair;
         const Ct &hi = ct(sp.in[0]), &lo = ct(sp.in[one ? 0 : 1]);
@@ -4027,6 +4068,7 @@ public:
         return gtab_[D] = d;
     }
     const u32* zero_enc(int f) {
+        need_secret("renorm_pool");  // the pooled zeros serve the secret-key renorm alone
         ZPool& zp = zpool_[t_sidx][f];
         if (!zp.slab.data || zp.next >= zp.slab.nb) {
             if (zp.slab.data) zretired_[t_sidx].push_back(zp.slab);  // released after this renorm's launches
@@ -4116,6 +4158,7 @@ public:
         return s;
     }
     const u32* sparse_secret() {
+        need_secret("sparse_secret");
         if (d_ssp_) return d_ssp_;
         const int n = hp_.n, nt = hp_.n_tot();
         const std::vector<int> s = sparse_coeffs();
@@ -5354,12 +5397,109 @@ public:
         HIP_OK(hipStreamSynchronize(S()));
     }
     void export_secret(u32* out) {
+        need_secret("export_secret");
         if (!d_s_) throw std::runtime_error("keys not generated");
         export_dev(d_s_, (size_t)hp_.n_tot() * hp_.n, out);
     }
     void export_pk(u32* out) {
         if (!d_pk_) throw std::runtime_error("keys not generated");
         export_dev(d_pk_, (size_t)2 * hp_.n_q * hp_.n, out);
+    }
+    // ---- imports into an evaluation-only context.  The data is untrusted input to kernels that assume residues
+    // below q (the lazy NTT's [0, 4q) bound, Barrett and Shoup reduction): k_check_residues reads it once on the
+    // device before it is stored, and a residue >= its row's modulus refuses the import, naming the row
+    // the lowest row of d ([rows][N], row r on limb r % nl of map) with a residue >= its modulus, or -1
+    long bad_row(const u32* d, size_t rows, int nl, LimbMap map) {
+        if (!d_bad_) d_bad_ = dev_alloc(4);
+        u32 h = ~0u;
+        HIP_OK(hipMemsetAsync(d_bad_, 0xff, sizeof(u32), S()));
+        launch_check_residues(S(), T_, d, rows, nl, map, d_bad_);
+        HIP_OK(hipMemcpyAsync(&h, d_bad_, sizeof(u32), hipMemcpyDeviceToHost, S()));
+        HIP_OK(hipStreamSynchronize(S()));
+        return h == ~0u ? -1 : (long)h;
+    }
+    long check_ct(aesfhe_handle h) {
+        const Ct& c = ct(h);
+        return bad_row(c.data, c.words / hp_.n, hp_.nl(c.level), qmap());
+    }
+    // a checked device copy of `words` host words laid out as rows of nl limbs under map; the caller owns it
+    u32* import_rows(const char* who, const u32* data, size_t words, int nl, LimbMap map) {
+        void* raw = nullptr;
+        HIP_OK(hipMalloc(&raw, words * sizeof(u32)));
+        try {
+            HIP_OK(hipMemcpyAsync(raw, data, words * sizeof(u32), hipMemcpyHostToDevice, S()));
+            const long bad = bad_row((const u32*)raw, words / hp_.n, nl, map);
+            if (bad >= 0)
+                throw std::runtime_error(std::string(who) + ": residue not below its modulus in row " + std::to_string(bad) + " (nothing stored)");
+        } catch (...) {
+            (void)hipStreamSynchronize(S());
+            (void)hipFree(raw);
+            throw;
+        }
+        return (u32*)raw;
+    }
+    void import_target(const char* who, const u32* data) const {
+        if (!eval_only_) throw std::runtime_error(std::string(who) + ": this context has a secret key; keys are imported into an evaluation-only context");
+        if (!data) throw std::runtime_error(std::string(who) + ": no data");
+    }
+    void import_pk(const u32* data, u64 words) {
+        import_target("import_pk", data);
+        if (d_pk_) throw std::runtime_error("import_pk: the public key is already present");
+        const size_t want = (size_t)2 * hp_.n_q * hp_.n;
+        if (words != want) throw std::runtime_error("import_pk: wrong word count (" + std::to_string(words) + ", the public key has " + std::to_string(want) + ")");
+        d_pk_ = import_rows("import_pk", data, want, hp_.n_q, qmap());
+        owned_.push_back(d_pk_);
+    }
+    bool reduced_level(int level) const { return low_p_ && level >= 0 && level <= hp_.L && hp_.nl(level) < hp_.alpha; }
+    // rows per polynomial of the key of tag g at `level` (-1: the full key) and the map of its rows
+    int key_rows(u64 g, int level, LimbMap& em) const {
+        if (level >= 0) {
+            if (!reduced_level(level)) throw std::runtime_error("switching key: level " + std::to_string(level) + " is not a reduced level (low-P off, or the level has a full digit)");
+            if (g == tag_d2s()) throw std::runtime_error("switching key: the dense -> sparse key has its own basis and no reduced-level form");
+            em = extmap(hp_.nl(level));
+            return 2 * hp_.nl(level) + 1;  // nl + np, np = nl + 1 (build_low_basis)
+        }
+        if (g == tag_d2s()) return em = extmap(kD2sQ), kD2sQ + d2s_np();
+        return em = extmap(hp_.n_ks), hp_.n_ks + hp_.n_p;
+    }
+    u64 ksk_words_at(u64 g, int level) const {
+        LimbMap em;
+        const int rows = key_rows(g, level, em);
+        return level >= 0 ? (u64)2 * rows * hp_.n : (u64)ksk_words(g);
+    }
+    void import_ksk(u64 g, int level, const u32* data, u64 words) {
+        import_target("import_ksk", data);
+        if (level < -1) throw std::runtime_error("import_ksk: bad level");
+        LimbMap em;
+        const int rows = key_rows(g, level, em);
+        const u64 want = ksk_words_at(g, level);
+        if (words != want) throw std::runtime_error("import_ksk: wrong word count (" + std::to_string(words) + ", this key has " + std::to_string(want) + ")");
+        const auto id = std::make_pair(g, level);
+        if (level < 0 ? ksk_.count(g) != 0 : ksk_low_.count(id) != 0)
+            throw std::runtime_error("import_ksk: key already present (galois " + std::to_string(g) + ", level " + std::to_string(level) + ")");
+        u32* key = import_rows("import_ksk", data, want, rows, em);
+        if (level < 0) ksk_[g] = key;
+        else ksk_low_[id] = key;
+    }
+    // the keys present, as (tag, level) pairs, level -1: a full key; returns their count (the first `cap` are written)
+    int eval_keys(u64* g, int32_t* level, int cap) const {
+        int k = 0;
+        for (const auto& kv : ksk_) {
+            if (k < cap) g[k] = kv.first, level[k] = -1;
+            ++k;
+        }
+        for (const auto& kv : ksk_low_) {
+            if (k < cap) g[k] = kv.first.first, level[k] = kv.first.second;
+            ++k;
+        }
+        return k;
+    }
+    // generate (keyed context) or look up the key a key switch of tag g uses; level -1: the full key
+    void ensure_key(u64 g, int level) {
+        if (level < -1 || level > hp_.L) throw std::runtime_error("ensure_key: bad level");
+        if (level >= 0 && !reduced_level(level)) throw std::runtime_error("ensure_key: level " + std::to_string(level) + " is not a reduced level");
+        if (level < 0) (void)ksk(g);
+        else (void)ksk_at(g, level);
     }
     void export_ksk(u64 g, u32* out) { export_dev(ksk(g), ksk_words(g), out); }
     // the key a key switch at `level` uses (ksk_at): the reduced level's own [2][nl + np][N] key, else the full key
@@ -5830,6 +5970,7 @@ private:
     double* d_fft_[kStreams] = {};  // slot-packed renorm: [2 buffers][2 cts][N] complex double
     u32* d_slot_pos_ = nullptr;     // (5^j mod 2N - 1) / 2 for slot j < N/2
     u32* d_s2_ = nullptr;
+    u32* d_bad_ = nullptr;  // bad_row: the lowest offending row of the last residue check
     bool lazy_ = true;  // defer relinearisation / rescales of API-level products
 
 public:
@@ -5902,6 +6043,49 @@ int aesfhe_create_keyed(aesfhe_ctx** out, int log_n, int max_level, int dnum, in
     for (int i = 0; i < 8; ++i)
         k[i] = (u32)key[4 * i] | ((u32)key[4 * i + 1] << 8) | ((u32)key[4 * i + 2] << 16) | ((u32)key[4 * i + 3] << 24);
     return create_keyed(out, log_n, max_level, dnum, device_id, k, bootstrappable);
+}
+int aesfhe_create_eval(aesfhe_ctx** out, int log_n, int max_level, int dnum, int device_id, int bootstrappable, const uint8_t* prng_key) {
+    if (!out) return -2;
+    if (!prng_key) {
+        *out = nullptr;
+        t_err = "create_eval: no PRNG key (32 bytes of the caller's own randomness)";
+        return -1;
+    }
+    const int rc = aesfhe_create_keyed(out, log_n, max_level, dnum, device_id, prng_key, bootstrappable);
+    if (rc == 0) (*out)->eng->set_eval_only();
+    return rc;
+}
+int aesfhe_has_secret(aesfhe_ctx* ctx) { return ctx && ctx->eng ? (ctx->eng->has_secret() ? 1 : 0) : -1; }
+int aesfhe_eval_keys(aesfhe_ctx* ctx, uint64_t* galois, int32_t* level, int cap) {
+    if (!ctx || !ctx->eng) return -2;
+    std::lock_guard<std::recursive_mutex> lock_(ctx->mu);
+    if (cap > 0 && (!galois || !level)) {
+        t_err = "eval_keys: no output arrays";
+        return -1;
+    }
+    return ctx->eng->eval_keys((u64*)galois, level, cap < 0 ? 0 : cap);
+}
+int aesfhe_ksk_words(aesfhe_ctx* ctx, uint64_t galois, int level, uint64_t* words) {
+    API_BEGIN if (!words || level < -1) throw std::runtime_error("ksk_words: bad arguments");
+    *words = ctx->eng->ksk_words_at(galois, level);
+    API_END
+}
+int aesfhe_import_pk(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words) {
+    API_BEGIN ctx->eng->import_pk(data, words);
+    API_END
+}
+int aesfhe_import_ksk(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words) {
+    API_BEGIN ctx->eng->import_ksk(galois, level, data, words);
+    API_END
+}
+int aesfhe_ensure_key(aesfhe_ctx* ctx, uint64_t galois, int level) {
+    API_BEGIN ctx->eng->ensure_key(galois, level);
+    API_END
+}
+int aesfhe_check(aesfhe_ctx* ctx, aesfhe_handle handle, int32_t* bad_row) {
+    API_BEGIN if (!bad_row) throw std::runtime_error("check: no output");
+    *bad_row = (int32_t)ctx->eng->check_ct(handle);
+    API_END
 }
 int aesfhe_level_limbs(aesfhe_ctx* ctx, int32_t* out) {
     API_BEGIN const HostParams& p = ctx->eng->hp();
@@ -6327,6 +6511,7 @@ int aesfhe_debug_lin_group_plain(aesfhe_ctx* ctx, int which, const double* re, c
 }
 int aesfhe_export_sparse(aesfhe_ctx* ctx, uint32_t* out) {
     API_BEGIN Engine& e = *ctx->eng;
+    e.need_secret("export_sparse");
     e.export_dev(e.sparse_secret(), (size_t)e.hp().n_tot() * e.hp().n, out);
     API_END
 }

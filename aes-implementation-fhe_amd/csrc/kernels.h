@@ -153,6 +153,9 @@ void launch_sub(hipStream_t st, const DevTables& T, u32* out, const u32* a, cons
 void launch_neg(hipStream_t st, const DevTables& T, u32* out, const u32* a, int rows, int nl, LimbMap map);
 // out = in over `rows` rows of N words (device to device)
 void launch_copy_rows(hipStream_t st, const DevTables& T, u32* out, const u32* in, size_t rows);
+// *bad = min(*bad, r) over the rows r of `in` ([rows][N]) that hold a word >= the modulus of limb r % nl of `map`;
+// the caller sets *bad to ~0u first and reads it after the stream (an import's check: one read of the data)
+void launch_check_residues(hipStream_t st, const DevTables& T, const u32* in, size_t rows, int nl, LimbMap map, u32* bad);
 // n (<= kMaxMembers) independent copies of `rows` rows each: dst[m] = src[m] (one launch;
 // stacking / unstacking batched ciphertexts)
 constexpr int kMaxMembers = 8;

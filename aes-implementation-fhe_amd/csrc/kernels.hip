@@ -62,6 +62,16 @@ __global__ void k_copy_rows(uint4* out, const uint4* in, int logn) {
     const size_t i = ((size_t)blockIdx.y << (logn - 2)) + (size_t)blockIdx.x * kBlock + threadIdx.x;
     out[i] = in[i];
 }
+// imported residues checked against their row's modulus (row r holds limb r % nl of `map`, as the sampling kernels
+// address rows): 16 B per lane, the modulus block-uniform, one wave vote, then at most one lane per wave lowers *bad
+// to the row index.  No early exit and no per-element atomic: one read of the data either way
+__global__ void __launch_bounds__(kBlock) k_check_residues(const uint4* in, int nl, LimbMap map, const PrimeConst* pc, int logn, u32* bad) {
+    const u32 row = blockIdx.y;
+    const u32 q = pc[map.prime((int)(row % (u32)nl))].q;
+    const uint4 v = in[((size_t)row << (logn - 2)) + (size_t)blockIdx.x * kBlock + threadIdx.x];
+    const int over = v.x >= q || v.y >= q || v.z >= q || v.w >= q;
+    if (__any(over) && (threadIdx.x & 63) == 0) atomicMin(bad, row);
+}
 __global__ void k_copy_members(MemberPtrs mp, int logn) {
     const size_t i = ((size_t)blockIdx.y << (logn - 2)) + (size_t)blockIdx.x * kBlock + threadIdx.x;
     reinterpret_cast<uint4*>(mp.dst[blockIdx.z])[i] = reinterpret_cast<const uint4*>(mp.src[blockIdx.z])[i];
@@ -1588,6 +1598,12 @@ void launch_copy_rows(hipStream_t st, const DevTables& T, u32* out, const u32* i
     if (rows > 65535) throw std::runtime_error("launch_copy_rows: too many rows");
     prof_launch(KID_ELEMENTWISE, EW_BYTES(2.0 * rows), k_copy_rows, dim3((1u << T.logn) / (4 * kBlock), (unsigned)rows), dim3(kBlock), 0, st,
                 reinterpret_cast<uint4*>(out), reinterpret_cast<const uint4*>(in), T.logn);
+}
+void launch_check_residues(hipStream_t st, const DevTables& T, const u32* in, size_t rows, int nl, LimbMap map, u32* bad) {
+    if (rows == 0) return;
+    if (rows > 65535 || nl < 1 || T.logn < 10) throw std::runtime_error("launch_check_residues: row count or ring out of range");
+    prof_launch(KID_ELEMENTWISE, EW_BYTES(1.0 * rows), k_check_residues, dim3((1u << T.logn) / (4 * kBlock), (unsigned)rows), dim3(kBlock), 0, st,
+                reinterpret_cast<const uint4*>(in), nl, map, T.pc, T.logn, bad);
 }
 void launch_copy_members(hipStream_t st, const DevTables& T, const MemberPtrs& mp, int n, int rows) {
     if (n <= 0 || rows <= 0) return;

@@ -50,6 +50,7 @@ class EngineContext:
                              device_id=device_id, log_n=log_n, dnum=dnum, seed=seed, lazy=lazy,
                              concurrent=concurrent, allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls, **kw)
         eng = self.engine
+        self.evaluation_only = False
         # the bootstrappable sets sized by boot_fresh_level carry alpha + 1 special primes for the top
         # of the bootstrap, while the AES rounds key-switch at levels of fewer than alpha limbs: those
         # run over nl + 1 special primes (AESFHE_LOW_P=0 keeps the full basis)
@@ -62,11 +63,71 @@ class EngineContext:
         self.conjugation_key = eng.create_conjugation_key(self.secret_key)
         self.rotation_key = eng.create_rotation_key(self.secret_key)
         self.bootstrap_key = eng.create_bootstrap_key(self.secret_key)
+        self._init_state(fused_luts)
+
+    def _init_state(self, fused_luts: bool):
         self._bs_count = 0  # ciphertexts refreshed
         self._bs_calls = 0  # bootstrap calls (a pair / quad call on periodic messages: one packed bootstrap)
         self._bs_total_s = 0.0
         self.fused_luts = bool(fused_luts)
         self._init_lut_cache()
+
+    # -------------------------------------------------------------- client / server
+    def export_evaluation_keys(self, stream: bool = False):
+        """EvaluationKeys of this (keyed) context: the public key and every switching key currently present.
+
+        Keys are generated on first use, so run the workload once as a warm-up and then export: which keys an
+        operation touches depends on levels and steps only, never on data, so a warm-up on any input of the same
+        shape generates exactly the keys every later run uses (Engine.ensure_key adds single keys without running
+        an operation).  stream=True: the keys are read out one at a time through one reused host buffer as the
+        bundle is saved or imported (evaluation_keys.stream_keys), never all held at once.  The bundle holds no
+        secret key, no sparse secret and no PRNG key or seed."""
+        from evaluation_keys import EvaluationKeys, make_header, stream_keys
+        eng = self.engine
+        if not eng.has_secret:
+            raise RuntimeError("export_evaluation_keys: no secret key (an evaluation-only context exports nothing; keep the client's bundle)")
+        header = make_header(log_n=eng.log_n, max_level=eng.fresh_level, dnum=eng.dnum, bootstrappable=eng.use_bootstrap,
+                             low_p=eng.low_p, n_q=eng.n_q, n_p=eng.n_p, moduli=eng.moduli())
+        pk = eng.export_pk().reshape(-1)
+        ids = eng.key_ids()
+        if stream:
+            return EvaluationKeys(header, pk, stream_keys(eng, ids))
+        return EvaluationKeys(header, pk, {k: eng.export_key(*k) for k in ids})
+
+    @classmethod
+    def from_evaluation_keys(cls, keys, device_id: int = 0, prng_key: bytes | None = None, *, lazy: bool = True,
+                             concurrent: bool = False, fused_luts: bool = True, allow_insecure: bool = False,
+                             enc_nonce: int | None = None, defer_calls: bool | None = None):
+        """The server's context: built from an EvaluationKeys bundle alone, it never holds the secret.  secret_key is
+        None; decrypt and every renorm_* raise the engine's "no secret key" error, a key switch whose key the
+        bundle lacks raises "evaluation key missing"; every other method is unchanged.  prng_key: 32 bytes for this
+        context's own encryption samples (os.urandom unless given), never the client's.  A bundle whose moduli
+        differ from the chain its header parameters build is refused.  Keys are imported one at a time as
+        keys.items() produces them (each is checked on the device: residues below their moduli)."""
+        h = keys.header
+        eng = Engine.evaluation_only(prng_key=prng_key, device_id=device_id, log_n=h["log_n"], max_level=h["max_level"],
+                                     dnum=h["dnum"], use_bootstrap=h["bootstrappable"], lazy=lazy, concurrent=concurrent,
+                                     allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls)
+        mod = [int(m) for m in eng.moduli()]
+        if (eng.n_q, eng.n_p) != (h["n_q"], h["n_p"]) or mod != [int(m) for m in h["moduli"]]:
+            raise ValueError("evaluation keys: the bundle's moduli differ from the chain its parameters build here "
+                             "(another parameter set, or another engine version)")
+        eng.set_low_p(bool(h["low_p"]))
+        eng.import_pk(keys.pk)
+        for (g, level), arr in keys.items():
+            eng.import_ksk(g, level, arr)
+        self = cls.__new__(cls)
+        self.signature = 1 if h["bootstrappable"] else 2
+        self.engine = eng
+        self.evaluation_only = True
+        self.secret_key = None
+        self.public_key = eng.create_public_key()
+        self.relinearization_key = eng.create_relinearization_key()
+        self.conjugation_key = eng.create_conjugation_key()
+        self.rotation_key = eng.create_rotation_key()
+        self.bootstrap_key = eng.create_bootstrap_key()
+        self._init_state(fused_luts)
+        return self
 
     # -------------------------------------------------------------- codec
     def encrypt(self, data: np.ndarray):

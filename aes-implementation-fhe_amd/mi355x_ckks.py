@@ -55,6 +55,8 @@ EXPORTED = [
     "aesfhe_xor_value_typed", "aesfhe_debug_xor_value_typed_pt",
     "aesfhe_xor_value_groups", "aesfhe_debug_xor_value_groups_pt",
     "aesfhe_byte_lut_create", "aesfhe_byte_lut_public", "aesfhe_debug_byte_lut_pt", "aesfhe_byte_lut_free",
+    "aesfhe_create_eval", "aesfhe_has_secret", "aesfhe_eval_keys", "aesfhe_ksk_words", "aesfhe_import_pk", "aesfhe_import_ksk",
+    "aesfhe_ensure_key", "aesfhe_check",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -186,6 +188,14 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_renorm_unpack_perm"] = [vp, _H, _H, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), c_int, c_int, _Hp, _Hp]
     sig["aesfhe_renorm_periodic_perm"] = [vp, _H, _H, _H, _H, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), c_int, c_int, c_int, _Hp, _Hp]
     sig["aesfhe_renorm_unpack_conj"] = [vp, _H, _H, c_int, c_int, _Hp, _Hp]
+    sig["aesfhe_create_eval"] = [pp, c_int, c_int, c_int, c_int, c_int, ctypes.c_char_p]
+    sig["aesfhe_has_secret"] = [vp]
+    sig["aesfhe_eval_keys"] = [vp, np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS"), np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), c_int]
+    sig["aesfhe_ksk_words"] = [vp, ctypes.c_uint64, c_int, ctypes.POINTER(ctypes.c_uint64)]
+    sig["aesfhe_import_pk"] = [vp, _up, ctypes.c_uint64]
+    sig["aesfhe_import_ksk"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
+    sig["aesfhe_ensure_key"] = [vp, ctypes.c_uint64, c_int]
+    sig["aesfhe_check"] = [vp, _H, ctypes.POINTER(ctypes.c_int32)]
     for name in EXPORTED:
         fn = getattr(L, name)
         fn.restype = (ctypes.c_char_p if name == "aesfhe_last_error"
@@ -198,10 +208,14 @@ def load_library(path: Optional[Path] = None):
 class _Context:
     """Owns one aesfhe_ctx; destroyed when the last object referring to it dies."""
 
-    def __init__(self, log_n, max_level, dnum, device_id, seed, bootstrappable=False):
+    def __init__(self, log_n, max_level, dnum, device_id, seed, bootstrappable=False, eval_only=False):
         self.lib = load_library()
         ptr = ctypes.c_void_p()
-        if isinstance(seed, (bytes, bytearray)):  # the full 256-bit ChaCha20 key
+        if eval_only:  # no secret, ever: `seed` is the 32-byte key of this context's own encryption samples
+            if not isinstance(seed, (bytes, bytearray)) or len(seed) != 32:
+                raise ValueError("an evaluation-only context takes a 32-byte prng_key")
+            rc = self.lib.aesfhe_create_eval(ctypes.byref(ptr), log_n, max_level, dnum, device_id, int(bootstrappable), bytes(seed))
+        elif isinstance(seed, (bytes, bytearray)):  # the full 256-bit ChaCha20 key
             if len(seed) != 32:
                 raise ValueError("a key must be 32 bytes")
             rc = self.lib.aesfhe_create_keyed(ctypes.byref(ptr), log_n, max_level, dnum, device_id, bytes(seed),
@@ -344,7 +358,8 @@ class Engine:
     def __init__(self, *, mode: str = "gpu", use_bootstrap: bool = False, use_multiparty: bool = False,
                  thread_count: int = 0, device_id: int = 0, max_level: int = 17, log_n: int = 16,
                  dnum: int | None = None, seed: int | None = None, lazy: bool = True, concurrent: bool = False,
-                 allow_insecure: bool = False, enc_nonce: int | None = None, defer_calls: bool | None = None):
+                 allow_insecure: bool = False, enc_nonce: int | None = None, defer_calls: bool | None = None,
+                 _eval_only: bool = False):
         if use_multiparty:
             raise ValueError("multiparty key generation is not supported")
         self.mode = mode
@@ -363,7 +378,8 @@ class Engine:
         if seed is None:
             seed = os.urandom(32)
         self.seed = bytes(seed) if isinstance(seed, (bytes, bytearray)) else int(seed) & 0xFFFFFFFFFFFFFFFF
-        self._ctx = _Context(log_n, max_level, dnum, device_id, self.seed, bootstrappable=use_bootstrap)
+        self.eval_only = bool(_eval_only)
+        self._ctx = _Context(log_n, max_level, dnum, device_id, self.seed, bootstrappable=use_bootstrap, eval_only=self.eval_only)
         L = self._ctx.lib
         # encryption randomness has its own per-process nonce (aesfhe_set_enc_nonce): processes
         # that share the key set (multi-rank jobs) never reuse (v, e); pinned only for tests and
@@ -491,6 +507,25 @@ class Engine:
         self._ctx.check(fn(self._ctx.ptr, *args, ctypes.byref(h)))
         return cls(self._ctx, h.value)
 
+    @classmethod
+    def evaluation_only(cls, *, prng_key: bytes | None = None, **params) -> "Engine":
+        """An engine that never holds the secret (aesfhe_create_eval): the server side.  `params` are
+        Engine's own (log_n, max_level, dnum, use_bootstrap, device_id, allow_insecure, enc_nonce, ...) and must be
+        the client's; the security-bound refusal and set_low_p behave as on a keyed engine.  prng_key: 32 bytes for
+        this engine's own encryption samples, os.urandom unless given -- never the client's key or seed.  The public
+        key and the switching keys come in through import_pk / import_ksk; decrypt, the renorms, the secret exports
+        and create_secret_key raise "no secret key", a key switch without its key "evaluation key missing"."""
+        if "seed" in params:
+            raise ValueError("an evaluation-only engine has no key seed: prng_key seeds its own encryption samples only")
+        key = os.urandom(32) if prng_key is None else bytes(prng_key)
+        if len(key) != 32:
+            raise ValueError("prng_key must be 32 bytes")
+        return cls(seed=key, _eval_only=True, **params)
+
+    @property
+    def has_secret(self) -> bool:
+        return int(self._lib.aesfhe_has_secret(self._ctx.ptr)) == 1
+
     def _ensure_keys(self):
         if not self._keys_ready:
             self._ctx.check(self._lib.aesfhe_keygen(self._ctx.ptr))
@@ -498,6 +533,8 @@ class Engine:
 
     # ------------------------------------------------------------------ keys
     def create_secret_key(self):
+        if self.eval_only:
+            raise RuntimeError("create_secret_key: no secret key (this is an evaluation-only engine)")
         self._ensure_keys()
         return SecretKey("secret")
 
@@ -1358,6 +1395,60 @@ class Engine:
             out = np.zeros((self.dnum, 2, self.n_ks + self.n_p, self.n), np.uint32)
         self._ctx.check(self._lib.aesfhe_export_ksk_at(self._ctx.ptr, int(galois), int(level), out))
         return out
+
+    # ------------------------------------------------------------------ evaluation keys (client -> server)
+    def key_ids(self) -> list:
+        """(galois tag, level) of every switching key present, generated or imported (aesfhe_eval_keys); level -1: a
+        full key, level >= 0: that reduced level's own key (set_low_p)"""
+        n = int(self._lib.aesfhe_eval_keys(self._ctx.ptr, np.zeros(1, np.uint64), np.zeros(1, np.int32), 0))
+        if n < 0:
+            raise RuntimeError(self._lib.aesfhe_last_error(self._ctx.ptr).decode())
+        g, lv = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.int32)
+        n = min(n, int(self._lib.aesfhe_eval_keys(self._ctx.ptr, g, lv, n)))
+        return [(int(g[i]), int(lv[i])) for i in range(n)]
+
+    def ksk_words(self, galois: int, level: int = -1) -> int:
+        """uint32 words of the key (galois, level) (aesfhe_ksk_words)"""
+        w = ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_ksk_words(self._ctx.ptr, int(galois), int(level), ctypes.byref(w)))
+        return int(w.value)
+
+    def export_key(self, galois: int, level: int = -1, out: np.ndarray | None = None) -> np.ndarray:
+        """the key (galois, level) as key_ids names it, flat uint32; `out`: a reused host buffer of at least its size"""
+        if not self.eval_only:
+            self._ensure_keys()
+        words = self.ksk_words(galois, level)
+        buf = np.empty(words, np.uint32) if out is None else out.reshape(-1)[:words]
+        if level < 0:
+            self._ctx.check(self._lib.aesfhe_export_ksk(self._ctx.ptr, int(galois), buf))
+        else:
+            self._ctx.check(self._lib.aesfhe_export_ksk_at(self._ctx.ptr, int(galois), int(level), buf))
+        return buf
+
+    def ensure_key(self, galois: int, level: int = -1):
+        """make the key (galois, level) resident without running an operation (aesfhe_ensure_key): generated on a
+        keyed engine, looked up on an evaluation-only one"""
+        self._ensure_keys()
+        self._ctx.check(self._lib.aesfhe_ensure_key(self._ctx.ptr, int(galois), int(level)))
+
+    def import_pk(self, data: np.ndarray):
+        """the client's public key [2][n_q][N] into an evaluation-only engine; encrypt and import_ct work from here"""
+        d = np.ascontiguousarray(data, np.uint32).reshape(-1)
+        self._ctx.check(self._lib.aesfhe_import_pk(self._ctx.ptr, d, d.size))
+        self._keys_ready = True
+
+    def import_ksk(self, galois: int, level: int, data: np.ndarray):
+        """one switching key into an evaluation-only engine, in the layout export_key wrote (aesfhe_import_ksk):
+        every residue is checked against its row's modulus on the device; a refused key stores nothing"""
+        d = np.ascontiguousarray(data, np.uint32).reshape(-1)
+        self._ctx.check(self._lib.aesfhe_import_ksk(self._ctx.ptr, int(galois), int(level), d, d.size))
+
+    def check(self, ct: Ciphertext):
+        """the import check of a ciphertext (aesfhe_check): the first row, in [npoly][limbs] order, with a residue
+        not below its modulus, or None when every residue is reduced"""
+        bad = ctypes.c_int32()
+        self._ctx.check(self._lib.aesfhe_check(self._ctx.ptr, ct.handle, ctypes.byref(bad)))
+        return None if bad.value < 0 else int(bad.value)
 
     def debug_ntt(self, rows: np.ndarray, first_prime: int, inverse: bool = False) -> np.ndarray:
         d = np.ascontiguousarray(rows, np.uint32).copy()

@@ -100,6 +100,11 @@ class AESPipeline:
         self.fips = bool(fips)
         if fips and (fuse_sub_ark or fuse_sr_mc or pairs > 1):
             raise ValueError("fips=True does not combine with fuse_sub_ark, fuse_sr_mc or pairs > 1")
+        # an evaluation-only context (EngineContext.from_evaluation_keys) holds no secret: the secret-key renorm is
+        # refused here, not deep inside the first round; true_fhe=True (bootstrap + snap) is its renorm
+        if getattr(ctx, "evaluation_only", False) and use_hard_renorm_between_steps:
+            raise ValueError("use_hard_renorm_between_steps=True needs the secret key: an evaluation-only context "
+                             "renormalises with true_fhe=True (bootstrap + snap) only")
         self.states = states
         # pairs > 1: a multi-pair batch -- `pairs` ciphertext pairs of `states` states each, run as
         # ONE stacked pair through every step (state_encoder.StateEncoder)

@@ -104,6 +104,34 @@ def tag_layout(layout: SlotLayout, *cts):
     return cts
 
 
+def dump_ct(ctx, ct):
+    """(array, level, layout) of a ciphertext for the wire between a client and a server context:
+    its residues [npoly][limbs][N] uint32, its level, and its slot-layout tag as a plain dict (None: untagged), so a
+    pipeline pair keeps ct.layout across the transport"""
+    lay = getattr(ct, "layout", None)
+    tag = None if lay is None else dict(sc=int(lay.sc), states=int(lay.states), periodic=bool(lay.periodic),
+                                        byte_order=str(getattr(lay, "byte_order", "plain")))
+    return ctx.engine.export(ct), int(ct.level), tag
+
+
+def load_ct(ctx, array, level: int, layout=None, check: bool = True):
+    """the ciphertext dump_ct wrote, imported into `ctx` and tagged with its layout again.  check=True (the default
+    for anything that crossed a wire) runs the engine's residue check first: a word not below its limb's modulus is
+    refused with ValueError before any arithmetic kernel sees the data"""
+    if layout is not None and int(layout["sc"]) != ctx.engine.slot_count:
+        raise ValueError(f"load_ct: a layout of {layout['sc']} slots into a context of {ctx.engine.slot_count}")
+    ct = ctx.engine.import_ct(np.asarray(array), int(level))
+    if check:
+        bad = ctx.engine.check(ct)
+        if bad is not None:
+            raise ValueError(f"load_ct: residue not below its modulus in row {bad}")
+    if layout is not None:
+        lay = SlotLayout(int(layout["sc"]), int(layout["states"]), bool(layout["periodic"]))
+        lay.byte_order = str(layout.get("byte_order", "plain"))
+        tag_layout(lay, ct)
+    return ct
+
+
 def check_layout(layout: SlotLayout, *cts) -> None:
     """raise if a ciphertext was tagged with another slot layout (a pair made by an encoder with
     the reference layout decrypts to wrong bytes under the periodic one, and vice versa);

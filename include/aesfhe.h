@@ -44,6 +44,37 @@ int aesfhe_create_boot(aesfhe_ctx** out, int log_n, int fresh_level, int dnum, i
  * bootstrappable != 0: max_level is the fresh level of a bootstrappable set (aesfhe_create_boot). */
 int aesfhe_create_keyed(aesfhe_ctx** out, int log_n, int max_level, int dnum, int device_id, const uint8_t* key,
                         int bootstrappable);
+/* Evaluation-only context: the server side of the client/server protocol.  It never holds the
+ * secret: the public key and the switching keys come in through aesfhe_import_pk / aesfhe_import_ksk, and prng_key
+ * (32 bytes of the caller's OWN randomness, never the client's key) seeds only its encryption samples.  Every call
+ * that needs the secret -- aesfhe_keygen, aesfhe_decrypt, every aesfhe_renorm_* entry, aesfhe_export_secret,
+ * aesfhe_export_sparse -- fails with "no secret key" in aesfhe_last_error; a key switch whose key was not imported
+ * fails with "evaluation key missing: galois <tag>, level <l>" (level -1: the full key) instead of generating it.
+ * The context stays usable after either error.  Every other call behaves as on a keyed context. */
+int aesfhe_create_eval(aesfhe_ctx** out, int log_n, int max_level, int dnum, int device_id, int bootstrappable,
+                       const uint8_t* prng_key);
+/* 1: a keyed context, 0: an evaluation-only one (negative: no context) */
+int aesfhe_has_secret(aesfhe_ctx* ctx);
+/* The switching keys present, generated or imported, as (galois tag, level) pairs; level -1: a full key
+ * [dnum][2][n_ks + n_p][N] (the dense -> sparse key of the bootstrap: [2][2 + np'][N]), level >= 0: that reduced
+ * level's own key (aesfhe_export_ksk_at).  Writes the first `cap` pairs and returns the count of all (negative on
+ * error): call with cap 0 for the count.  A client exports exactly these after a warm-up run of its workload. */
+int aesfhe_eval_keys(aesfhe_ctx* ctx, uint64_t* galois, int32_t* level, int cap);
+/* uint32 words of the key (galois, level), level -1: the full key; a level >= 0 must be a reduced one */
+int aesfhe_ksk_words(aesfhe_ctx* ctx, uint64_t galois, int level, uint64_t* words);
+/* Imports into an evaluation-only context: the public key [2][n_q][N] and the key (galois, level) in the layout
+ * aesfhe_export_pk / aesfhe_export_ksk / aesfhe_export_ksk_at wrote.  Refused with a message: a wrong word count, a
+ * level >= 0 that is not a reduced level under the current aesfhe_set_low_p setting, a key already present, a
+ * keyed context, and any residue not below its row's modulus (the device checks every word once; the message
+ * names the first such row and nothing is stored). */
+int aesfhe_import_pk(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words);
+int aesfhe_import_ksk(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words);
+/* the key (galois, level) made resident without running an operation: generated on a keyed context if absent;
+ * on an evaluation-only context a lookup ("evaluation key missing" if absent) */
+int aesfhe_ensure_key(aesfhe_ctx* ctx, uint64_t galois, int level);
+/* The import check for a ciphertext handle (aesfhe_import itself checks nothing): *bad_row = the first row
+ * ([npoly][limbs] order) holding a residue not below its modulus, or -1 when every residue is reduced. */
+int aesfhe_check(aesfhe_ctx* ctx, aesfhe_handle handle, int32_t* bad_row);
 /* Encryption randomness (v, e0, e1 of every encryption, the renorms' re-encryptions included)
  * is drawn under the context key with `nonce` folded into key words 6-7; key material is not
  * affected.  Processes sharing one context key (the ranks of a multi-GPU job) must
