@@ -184,6 +184,27 @@ public:
         for (int i = 0; i < 8; ++i) k.w[i] = hp_.key[i];
         return k;
     }
+    // The mask key (aesfhe_set_mask_key): a second, PUBLIC 256-bit key.  Once set, the uniform `a`
+    // halves of the public key and of every switching key are drawn under it (akey) at their usual stream ids, so a
+    // key travels as its b half and the receiver regenerates a.  The secret, every error polynomial and the encryption
+    // samples stay under the context key, which therefore must never equal the mask key.  Unset: akey() is pkey()
+    PrngKey mask_{};
+    bool has_mask_ = false;
+    bool has_mask_key() const { return has_mask_; }
+    PrngKey akey() const { return has_mask_ ? mask_ : pkey(); }
+    void set_mask_key(const u32 k[8]) {
+        if (has_mask_) throw std::runtime_error("set_mask_key: the mask key is already set");
+        if (std::equal(k, k + 8, hp_.key)) throw std::runtime_error("set_mask_key: the mask key equals the context key (publishing it would publish the secret)");
+        if (!eval_only_ && (d_pk_ || !ksk_.empty() || !ksk_low_.empty()))
+            throw std::runtime_error("set_mask_key: keys already exist (the mask key is set before key generation)");
+        for (int i = 0; i < 8; ++i) mask_.w[i] = k[i];
+        has_mask_ = true;
+    }
+    void need_mask(const char* who) const {
+        if (!has_mask_)
+            throw std::runtime_error(std::string(who) + ": no mask key (keys made under the context key cannot be compressed: their a halves "
+                                     "are not public)");
+    }
     Engine(int logn, int L1, int n_double, int dnum, int device, const u32 key[8]) : emb_(logn) {
         std::string err = hp_.build(logn, L1, n_double, dnum, key);
         if (!err.empty()) throw std::runtime_error(err);
@@ -555,7 +576,7 @@ public:
             const int nq = hp_.n_q;
             d_pk_ = dev_alloc((size_t)2 * nq * n);
             u32* e = tmp(nq);
-            launch_sample_uniform(S(), T_, d_pk_ + (size_t)nq * n, nq, qmap(), pkey(), stream_id(2, 0, 0));
+            launch_sample_uniform(S(), T_, d_pk_ + (size_t)nq * n, nq, qmap(), akey(), stream_id(2, 0, 0));
             launch_sample_small(S(), T_, e, nq, qmap(), pkey(), stream_id(3, 0, 0), 1);
             ntt(e, nq, nq, qmap());
             launch_keygen_combine(S(), T_, d_pk_, d_pk_ + (size_t)nq * n, d_s_, e, nullptr, nullptr, nq, qmap(), 0, 0);
@@ -611,7 +632,7 @@ public:
         u32* a = b + (size_t)ne * n;
         const LimbMap em = extmap(kD2sQ);  // rows 0, 1: q0, q1; then the first special primes
         u32* e = tmp(ne);
-        launch_sample_uniform(S(), T_, a, ne, em, pkey(), stream_id(4, g, 0));
+        launch_sample_uniform(S(), T_, a, ne, em, akey(), stream_id(4, g, 0));
         launch_sample_small(S(), T_, e, ne, em, pkey(), stream_id(5, g, 0), 1);
         ntt(e, ne, ne, em);
         // b = -a s_sp + e + (P' mod q_t) s on the q0, q1 rows
@@ -639,7 +660,7 @@ public:
         for (int j = 0; j < hp_.dnum; ++j) {
             u32* b = key + (size_t)j * 2 * nkey * n;
             u32* a = b + (size_t)nkey * n;
-            launch_sample_uniform(S(), T_, a, nkey, em, pkey(), stream_id(4, g, j));
+            launch_sample_uniform(S(), T_, a, nkey, em, akey(), stream_id(4, g, j));
             launch_sample_small(S(), T_, e, nkey, em, pkey(), stream_id(5, g, j), 1);
             ntt(e, nkey, nkey, em);
             const int lo = j * hp_.alpha, hi = std::min(nks, lo + hp_.alpha);
@@ -672,7 +693,7 @@ public:
         u32* sp = key_source(g);
         u32* e = tmp(nkey);
         const LimbMap em = extmap(nl);
-        launch_sample_uniform(S(), T_, a, nkey, em, pkey(), stream_id(10, g, level));
+        launch_sample_uniform(S(), T_, a, nkey, em, akey(), stream_id(10, g, level));
         launch_sample_small(S(), T_, e, nkey, em, pkey(), stream_id(11, g, level), 1);
         ntt(e, nkey, nkey, em);
         launch_keygen_combine(S(), T_, b, a, d_s_, e, sp, B.gadget, nkey, em, 0, nl);
@@ -5481,6 +5502,97 @@ public:
         if (level < 0) ksk_[g] = key;
         else ksk_low_[id] = key;
     }
+    // ---- seed-compressed keys.  With a mask key the a half of a key is a public function of
+    // (mask key, stream id, prime, coefficient), so a key travels as its b rows: [n_q][N] for the public key,
+    // [dnum][nkey][N] for a full switching key, [nkey][N] for the dense -> sparse key and a reduced level's key
+    struct HalfGeom {
+        int digits, nkey;  // the whole key: [digits][2][nkey][N]
+        LimbMap map;
+        u64 stream0;       // the a rows' stream id of digit 0 (digit j: stream0 + j)
+        size_t rows() const { return (size_t)digits * nkey; }  // rows of the half ([digits][nkey][N])
+    };
+    HalfGeom pk_half_geom() const { return HalfGeom{1, hp_.n_q, qmap(), stream_id(2, 0, 0)}; }
+    HalfGeom ksk_half_geom(u64 g, int level) const {
+        LimbMap em;
+        const int rows = key_rows(g, level, em);
+        if (level >= 0) return HalfGeom{1, rows, em, stream_id(10, g, level)};
+        return HalfGeom{g == tag_d2s() ? 1 : hp_.dnum, rows, em, stream_id(4, g, 0)};
+    }
+    // the b rows of `key` to the host: one copy per digit (a digit's b rows are contiguous, digits 2 nkey rows apart)
+    void export_half(const char* who, const u32* key, const HalfGeom& G, u32* out, u64 words) {
+        if (!out) throw std::runtime_error(std::string(who) + ": no output");
+        const size_t row = (size_t)G.nkey * hp_.n * sizeof(u32);
+        if (words != G.rows() * hp_.n)
+            throw std::runtime_error(std::string(who) + ": wrong word count (" + std::to_string(words) + ", this half has " + std::to_string(G.rows() * hp_.n) + ")");
+        for (int j = 0; j < G.digits; ++j)
+            HIP_OK(hipMemcpyAsync((char*)out + j * row, (const char*)key + 2 * j * row, row, hipMemcpyDeviceToHost, S()));
+        HIP_OK(hipStreamSynchronize(S()));
+    }
+    void export_target(const char* who) const {
+        need_mask(who);
+        if (eval_only_) throw std::runtime_error(std::string(who) + ": an evaluation-only context exports no halves (keep the client's bundle)");
+    }
+    void export_pk_half(u32* out, u64 words) {
+        export_target("export_pk_half");
+        if (!d_pk_) throw std::runtime_error("keys not generated");
+        export_half("export_pk_half", d_pk_, pk_half_geom(), out, words);
+    }
+    void export_ksk_half(u64 g, int level, u32* out, u64 words) {
+        export_target("export_ksk_half");
+        if (level < -1) throw std::runtime_error("export_ksk_half: bad level");
+        const HalfGeom G = ksk_half_geom(g, level);
+        export_half("export_ksk_half", level < 0 ? ksk(g) : ksk_at(g, level), G, out, words);
+    }
+    // the whole key from its b rows: allocate, copy the b rows into place, one k_complete_key launch checks them and
+    // writes every a row.  The caller owns the result; a refusal frees it and stores nothing
+    u32* import_half(const char* who, const u32* data, u64 words, const HalfGeom& G) {
+        if (words != G.rows() * hp_.n)
+            throw std::runtime_error(std::string(who) + ": wrong word count (" + std::to_string(words) + ", this half has " + std::to_string(G.rows() * hp_.n) + ")");
+        const size_t row = (size_t)G.nkey * hp_.n * sizeof(u32);
+        if (!d_bad_) d_bad_ = dev_alloc(4);
+        void* raw = nullptr;
+        HIP_OK(hipMalloc(&raw, 2 * row * G.digits));
+        try {
+            u32 h = ~0u;
+            for (int j = 0; j < G.digits; ++j)
+                HIP_OK(hipMemcpyAsync((char*)raw + 2 * j * row, (const char*)data + j * row, row, hipMemcpyHostToDevice, S()));
+            HIP_OK(hipMemsetAsync(d_bad_, 0xff, sizeof(u32), S()));
+            launch_complete_key(S(), T_, (u32*)raw, G.digits, G.nkey, G.map, mask_, G.stream0, d_bad_);
+            HIP_OK(hipMemcpyAsync(&h, d_bad_, sizeof(u32), hipMemcpyDeviceToHost, S()));
+            HIP_OK(hipStreamSynchronize(S()));
+            if (h != ~0u)
+                throw std::runtime_error(std::string(who) + ": residue not below its modulus in row " + std::to_string(h) + " (nothing stored)");
+        } catch (...) {
+            (void)hipStreamSynchronize(S());
+            (void)hipFree(raw);
+            throw;
+        }
+        return (u32*)raw;
+    }
+    void import_pk_half(const u32* data, u64 words) {
+        import_target("import_pk_half", data);
+        need_mask("import_pk_half");
+        if (d_pk_) throw std::runtime_error("import_pk_half: the public key is already present");
+        d_pk_ = import_half("import_pk_half", data, words, pk_half_geom());
+        owned_.push_back(d_pk_);
+    }
+    void import_ksk_half(u64 g, int level, const u32* data, u64 words) {
+        import_target("import_ksk_half", data);
+        need_mask("import_ksk_half");
+        if (level < -1) throw std::runtime_error("import_ksk_half: bad level");
+        const HalfGeom G = ksk_half_geom(g, level);
+        const auto id = std::make_pair(g, level);
+        if (level < 0 ? ksk_.count(g) != 0 : ksk_low_.count(id) != 0)
+            throw std::runtime_error("import_ksk_half: key already present (galois " + std::to_string(g) + ", level " + std::to_string(level) + ")");
+        u32* key = import_half("import_ksk_half", data, words, G);
+        if (level < 0) ksk_[g] = key;
+        else ksk_low_[id] = key;
+    }
+    void mask_key_bytes(uint8_t out[32]) const {
+        need_mask("mask_key");
+        for (int i = 0; i < 8; ++i)
+            for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(mask_.w[i] >> (8 * b));
+    }
     // the keys present, as (tag, level) pairs, level -1: a full key; returns their count (the first `cap` are written)
     int eval_keys(u64* g, int32_t* level, int cap) const {
         int k = 0;
@@ -6085,6 +6197,36 @@ int aesfhe_ensure_key(aesfhe_ctx* ctx, uint64_t galois, int level) {
 int aesfhe_check(aesfhe_ctx* ctx, aesfhe_handle handle, int32_t* bad_row) {
     API_BEGIN if (!bad_row) throw std::runtime_error("check: no output");
     *bad_row = (int32_t)ctx->eng->check_ct(handle);
+    API_END
+}
+int aesfhe_set_mask_key(aesfhe_ctx* ctx, const uint8_t* key) {
+    API_BEGIN if (!key) throw std::runtime_error("set_mask_key: no key (32 bytes)");
+    u32 k[8];
+    for (int i = 0; i < 8; ++i)
+        k[i] = (u32)key[4 * i] | ((u32)key[4 * i + 1] << 8) | ((u32)key[4 * i + 2] << 16) | ((u32)key[4 * i + 3] << 24);
+    ctx->eng->set_mask_key(k);
+    API_END
+}
+int aesfhe_has_mask_key(aesfhe_ctx* ctx) { return ctx && ctx->eng ? (ctx->eng->has_mask_key() ? 1 : 0) : -1; }
+int aesfhe_mask_key(aesfhe_ctx* ctx, uint8_t* out) {
+    API_BEGIN if (!out) throw std::runtime_error("mask_key: no output");
+    ctx->eng->mask_key_bytes(out);
+    API_END
+}
+int aesfhe_export_pk_half(aesfhe_ctx* ctx, uint32_t* out, uint64_t words) {
+    API_BEGIN ctx->eng->export_pk_half(out, words);
+    API_END
+}
+int aesfhe_export_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, uint32_t* out, uint64_t words) {
+    API_BEGIN ctx->eng->export_ksk_half(galois, level, out, words);
+    API_END
+}
+int aesfhe_import_pk_half(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words) {
+    API_BEGIN ctx->eng->import_pk_half(data, words);
+    API_END
+}
+int aesfhe_import_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words) {
+    API_BEGIN ctx->eng->import_ksk_half(galois, level, data, words);
     API_END
 }
 int aesfhe_level_limbs(aesfhe_ctx* ctx, int32_t* out) {

@@ -156,6 +156,10 @@ void launch_copy_rows(hipStream_t st, const DevTables& T, u32* out, const u32* i
 // *bad = min(*bad, r) over the rows r of `in` ([rows][N]) that hold a word >= the modulus of limb r % nl of `map`;
 // the caller sets *bad to ~0u first and reads it after the stream (an import's check: one read of the data)
 void launch_check_residues(hipStream_t st, const DevTables& T, const u32* in, size_t rows, int nl, LimbMap map, u32* bad);
+// an imported key half completed in one launch: key [digits][2][nkey][N] with the b rows in place; every b row is
+// checked as launch_check_residues checks it (*bad = min(*bad, digit * nkey + row), set to ~0u by the caller) and every
+// a row is written: launch_sample_uniform's values under `mask`, stream stream0 + digit
+void launch_complete_key(hipStream_t st, const DevTables& T, u32* key, int digits, int nkey, LimbMap map, const PrngKey& mask, u64 stream0, u32* bad);
 // n (<= kMaxMembers) independent copies of `rows` rows each: dst[m] = src[m] (one launch;
 // stacking / unstacking batched ciphertexts)
 constexpr int kMaxMembers = 8;

@@ -72,6 +72,27 @@ __global__ void __launch_bounds__(kBlock) k_check_residues(const uint4* in, int 
     const int over = v.x >= q || v.y >= q || v.z >= q || v.w >= q;
     if (__any(over) && (threadIdx.x & 63) == 0) atomicMin(bad, row);
 }
+// an imported key HALF completed in place.  key: [digits][2][nkey][N], rows 0..nkey-1 of each digit the
+// imported b rows, rows nkey..2 nkey-1 the a rows still to be made; grid (N / kBlock, 2 nkey, digits), the branch
+// block-uniform on the row.  A b row is checked as k_check_residues checks it (the row's modulus, one wave vote, at
+// most one lane per wave lowers *bad to the row's index in the half, digit * nkey + row; no early exit).  An a row
+// is k_sample_uniform's value under the public mask key, stream stream0 + digit (stream_id's low field): the word
+// the client's key generation wrote.  ~10^3 integer operations per word stored: ALU-bound, one residue per thread
+__global__ void __launch_bounds__(kBlock) k_complete_key(u32* key, int nkey, LimbMap map, PrngKey mask, u64 stream0, const PrimeConst* pc, int logn,
+                                                         u32* bad) {
+    const u32 y = blockIdx.y, z = blockIdx.z;
+    const bool a_row = y >= (u32)nkey;
+    const u32 l = a_row ? y - (u32)nkey : y;
+    const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const int prime = map.prime((int)l);
+    const u32 q = pc[prime].q;
+    u32* p = key + ((((size_t)z * 2 * nkey) + y) << logn) + k;
+    if (a_row) {
+        *p = (u32)(chacha_u64(mask, stream0 + z, ((u64)prime << logn) + k) % q);
+    } else {
+        if (__any(*p >= q) && (threadIdx.x & 63) == 0) atomicMin(bad, z * (u32)nkey + l);
+    }
+}
 __global__ void k_copy_members(MemberPtrs mp, int logn) {
     const size_t i = ((size_t)blockIdx.y << (logn - 2)) + (size_t)blockIdx.x * kBlock + threadIdx.x;
     reinterpret_cast<uint4*>(mp.dst[blockIdx.z])[i] = reinterpret_cast<const uint4*>(mp.src[blockIdx.z])[i];
@@ -1604,6 +1625,11 @@ void launch_check_residues(hipStream_t st, const DevTables& T, const u32* in, si
     if (rows > 65535 || nl < 1 || T.logn < 10) throw std::runtime_error("launch_check_residues: row count or ring out of range");
     prof_launch(KID_ELEMENTWISE, EW_BYTES(1.0 * rows), k_check_residues, dim3((1u << T.logn) / (4 * kBlock), (unsigned)rows), dim3(kBlock), 0, st,
                 reinterpret_cast<const uint4*>(in), nl, map, T.pc, T.logn, bad);
+}
+void launch_complete_key(hipStream_t st, const DevTables& T, u32* key, int digits, int nkey, LimbMap map, const PrngKey& mask, u64 stream0, u32* bad) {
+    if (digits < 1 || digits > 65535 || nkey < 1 || 2 * nkey > 65535 || T.logn < 8) throw std::runtime_error("launch_complete_key: key shape or ring out of range");
+    prof_launch(KID_SAMPLE, words(2.0 * digits * nkey * (1u << T.logn)), k_complete_key, dim3((1u << T.logn) / kBlock, 2u * nkey, (unsigned)digits),
+                dim3(kBlock), 0, st, key, nkey, map, mask, stream0, T.pc, T.logn, bad);
 }
 void launch_copy_members(hipStream_t st, const DevTables& T, const MemberPtrs& mp, int n, int rows) {
     if (n <= 0 || rows <= 0) return;

@@ -32,7 +32,8 @@ class EngineContext:
                  use_multiparty: bool = False, mode: str = "cpu", device_id: int = 0,
                  thread_count: int | None = None, log_n: int = 16, dnum: int | None = None, seed: int | bytes | None = None,
                  lazy: bool = True, concurrent: bool = False, fused_luts: bool = True, allow_insecure: bool = False,
-                 enc_nonce: int | None = None, defer_calls: bool | None = None, boot_fresh_level: int | None = None):
+                 enc_nonce: int | None = None, defer_calls: bool | None = None, boot_fresh_level: int | None = None,
+                 mask_key: bytes | bool | None = None):
         # REF/engine_context.py:17-42: signature selects the engine constructor form.  boot_fresh_level
         # (an extension; REF's signature 1 takes the engine's default, 17): the fresh level of the
         # bootstrappable set -- the bootstrap's double-prime region sits above it, so a pipeline that never
@@ -46,9 +47,17 @@ class EngineContext:
         else:
             raise ValueError(f"Unsupported signature: {signature}")
         self.signature = signature
+        # mask_key: the PUBLIC second key the a halves of every key are drawn under, so that
+        # export_evaluation_keys(compressed=True) ships b halves only.  True: os.urandom(32); None: every draw under
+        # the context key, as before.  The engine sets it before the lazy key generation below
+        if mask_key is True:
+            mask_key = os.urandom(32)
+        elif mask_key is False:
+            mask_key = None
         self.engine = Engine(mode=mode, use_multiparty=use_multiparty, thread_count=thread_count or 0,
                              device_id=device_id, log_n=log_n, dnum=dnum, seed=seed, lazy=lazy,
-                             concurrent=concurrent, allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls, **kw)
+                             concurrent=concurrent, allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls,
+                             mask_key=mask_key, **kw)
         eng = self.engine
         self.evaluation_only = False
         # the bootstrappable sets sized by boot_fresh_level carry alpha + 1 special primes for the top
@@ -73,7 +82,7 @@ class EngineContext:
         self._init_lut_cache()
 
     # -------------------------------------------------------------- client / server
-    def export_evaluation_keys(self, stream: bool = False):
+    def export_evaluation_keys(self, stream: bool = False, compressed: bool = False):
         """EvaluationKeys of this (keyed) context: the public key and every switching key currently present.
 
         Keys are generated on first use, so run the workload once as a warm-up and then export: which keys an
@@ -81,11 +90,27 @@ class EngineContext:
         shape generates exactly the keys every later run uses (Engine.ensure_key adds single keys without running
         an operation).  stream=True: the keys are read out one at a time through one reused host buffer as the
         bundle is saved or imported (evaluation_keys.stream_keys), never all held at once.  The bundle holds no
-        secret key, no sparse secret and no PRNG key or seed."""
-        from evaluation_keys import EvaluationKeys, make_header, stream_keys
+        secret key, no sparse secret and no PRNG key or seed.  compressed=True (a context built with mask_key,
+        DESIGN.md §3.25): a CompressedEvaluationKeys bundle of the b halves plus the public mask key, half the bytes;
+        compressed=False on such a context is still a valid EvaluationKeys bundle, its keys are ordinary keys."""
+        from evaluation_keys import (CompressedEvaluationKeys, EvaluationKeys, make_compressed_header, make_header,
+                                     stream_key_halves, stream_keys)
         eng = self.engine
         if not eng.has_secret:
             raise RuntimeError("export_evaluation_keys: no secret key (an evaluation-only context exports nothing; keep the client's bundle)")
+        if compressed:
+            mk = eng.mask_key()
+            if mk is None:
+                raise RuntimeError("export_evaluation_keys: no mask key (keys made under the context key cannot be compressed: "
+                                   "their a halves are not public; build the context with mask_key=True)")
+            header = make_compressed_header(mask_key=mk, log_n=eng.log_n, max_level=eng.fresh_level, dnum=eng.dnum,
+                                            bootstrappable=eng.use_bootstrap, low_p=eng.low_p, n_q=eng.n_q, n_p=eng.n_p,
+                                            moduli=eng.moduli())
+            pk = eng.export_pk_half().reshape(-1)
+            ids = eng.key_ids()
+            if stream:
+                return CompressedEvaluationKeys(header, pk, stream_key_halves(eng, ids))
+            return CompressedEvaluationKeys(header, pk, {k: eng.export_key_half(*k) for k in ids})
         header = make_header(log_n=eng.log_n, max_level=eng.fresh_level, dnum=eng.dnum, bootstrappable=eng.use_bootstrap,
                              low_p=eng.low_p, n_q=eng.n_q, n_p=eng.n_p, moduli=eng.moduli())
         pk = eng.export_pk().reshape(-1)
@@ -103,9 +128,13 @@ class EngineContext:
         bundle lacks raises "evaluation key missing"; every other method is unchanged.  prng_key: 32 bytes for this
         context's own encryption samples (os.urandom unless given), never the client's.  A bundle whose moduli
         differ from the chain its header parameters build is refused.  Keys are imported one at a time as
-        keys.items() produces them (each is checked on the device: residues below their moduli)."""
+        keys.items() produces them (each is checked on the device: residues below their moduli).  A
+        CompressedEvaluationKeys bundle sets its mask key on the engine and imports halves: the a
+        half of each key is regenerated on the device and the key is word for word the client's."""
+        from evaluation_keys import CompressedEvaluationKeys
         h = keys.header
-        eng = Engine.evaluation_only(prng_key=prng_key, device_id=device_id, log_n=h["log_n"], max_level=h["max_level"],
+        halves = isinstance(keys, CompressedEvaluationKeys)
+        eng = Engine.evaluation_only(prng_key=prng_key, mask_key=keys.mask_key if halves else None, device_id=device_id, log_n=h["log_n"], max_level=h["max_level"],
                                      dnum=h["dnum"], use_bootstrap=h["bootstrappable"], lazy=lazy, concurrent=concurrent,
                                      allow_insecure=allow_insecure, enc_nonce=enc_nonce, defer_calls=defer_calls)
         mod = [int(m) for m in eng.moduli()]
@@ -113,9 +142,10 @@ class EngineContext:
             raise ValueError("evaluation keys: the bundle's moduli differ from the chain its parameters build here "
                              "(another parameter set, or another engine version)")
         eng.set_low_p(bool(h["low_p"]))
-        eng.import_pk(keys.pk)
+        (eng.import_pk_half if halves else eng.import_pk)(keys.pk)
+        import_key = eng.import_ksk_half if halves else eng.import_ksk
         for (g, level), arr in keys.items():
-            eng.import_ksk(g, level, arr)
+            import_key(g, level, arr)
         self = cls.__new__(cls)
         self.signature = 1 if h["bootstrappable"] else 2
         self.engine = eng

@@ -57,6 +57,8 @@ EXPORTED = [
     "aesfhe_byte_lut_create", "aesfhe_byte_lut_public", "aesfhe_debug_byte_lut_pt", "aesfhe_byte_lut_free",
     "aesfhe_create_eval", "aesfhe_has_secret", "aesfhe_eval_keys", "aesfhe_ksk_words", "aesfhe_import_pk", "aesfhe_import_ksk",
     "aesfhe_ensure_key", "aesfhe_check",
+    "aesfhe_set_mask_key", "aesfhe_has_mask_key", "aesfhe_mask_key", "aesfhe_export_pk_half", "aesfhe_export_ksk_half",
+    "aesfhe_import_pk_half", "aesfhe_import_ksk_half",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -196,6 +198,13 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_import_ksk"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
     sig["aesfhe_ensure_key"] = [vp, ctypes.c_uint64, c_int]
     sig["aesfhe_check"] = [vp, _H, ctypes.POINTER(ctypes.c_int32)]
+    sig["aesfhe_set_mask_key"] = [vp, ctypes.c_char_p]
+    sig["aesfhe_has_mask_key"] = [vp]
+    sig["aesfhe_mask_key"] = [vp, ctypes.c_char_p]
+    sig["aesfhe_export_pk_half"] = [vp, _up, ctypes.c_uint64]
+    sig["aesfhe_export_ksk_half"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
+    sig["aesfhe_import_pk_half"] = [vp, _up, ctypes.c_uint64]
+    sig["aesfhe_import_ksk_half"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
     for name in EXPORTED:
         fn = getattr(L, name)
         fn.restype = (ctypes.c_char_p if name == "aesfhe_last_error"
@@ -359,7 +368,7 @@ class Engine:
                  thread_count: int = 0, device_id: int = 0, max_level: int = 17, log_n: int = 16,
                  dnum: int | None = None, seed: int | None = None, lazy: bool = True, concurrent: bool = False,
                  allow_insecure: bool = False, enc_nonce: int | None = None, defer_calls: bool | None = None,
-                 _eval_only: bool = False):
+                 mask_key: bytes | None = None, _eval_only: bool = False):
         if use_multiparty:
             raise ValueError("multiparty key generation is not supported")
         self.mode = mode
@@ -381,6 +390,12 @@ class Engine:
         self.eval_only = bool(_eval_only)
         self._ctx = _Context(log_n, max_level, dnum, device_id, self.seed, bootstrappable=use_bootstrap, eval_only=self.eval_only)
         L = self._ctx.lib
+        # the public mask key of seed-compressed keys, set before any key exists: the a halves of
+        # the keys are then drawn under it and a key travels as its b half.  None: every draw under the context key
+        if mask_key is not None:
+            if not isinstance(mask_key, (bytes, bytearray)) or len(mask_key) != 32:
+                raise ValueError("mask_key must be 32 bytes")
+            self.set_mask_key(bytes(mask_key))
         # encryption randomness has its own per-process nonce (aesfhe_set_enc_nonce): processes
         # that share the key set (multi-rank jobs) never reuse (v, e); pinned only for tests and
         # bit-exact A/B digests (AESFHE_ENC_NONCE)
@@ -521,6 +536,21 @@ class Engine:
         if len(key) != 32:
             raise ValueError("prng_key must be 32 bytes")
         return cls(seed=key, _eval_only=True, **params)
+
+    def set_mask_key(self, key: bytes):
+        """the public mask key (aesfhe_set_mask_key): 32 bytes, once, before the first key exists (a keyed engine) or
+        before the first half import (an evaluation-only one); never the engine's own key"""
+        if len(key) != 32:
+            raise ValueError("mask_key must be 32 bytes")
+        self._ctx.check(self._lib.aesfhe_set_mask_key(self._ctx.ptr, bytes(key)))
+
+    def mask_key(self) -> bytes | None:
+        """the mask key this engine's a halves are drawn under, or None (aesfhe_mask_key)"""
+        if int(self._lib.aesfhe_has_mask_key(self._ctx.ptr)) != 1:
+            return None
+        out = ctypes.create_string_buffer(32)
+        self._ctx.check(self._lib.aesfhe_mask_key(self._ctx.ptr, out))
+        return out.raw
 
     @property
     def has_secret(self) -> bool:
@@ -1442,6 +1472,36 @@ class Engine:
         every residue is checked against its row's modulus on the device; a refused key stores nothing"""
         d = np.ascontiguousarray(data, np.uint32).reshape(-1)
         self._ctx.check(self._lib.aesfhe_import_ksk(self._ctx.ptr, int(galois), int(level), d, d.size))
+
+    # seed-compressed keys (DESIGN.md §3.25): the b halves alone; the receiver regenerates a from the mask key
+    def export_pk_half(self) -> np.ndarray:
+        """the b half [n_q][N] of the public key (aesfhe_export_pk_half); needs a mask key"""
+        self._ensure_keys()
+        out = np.empty((self.n_q, self.n), np.uint32)
+        self._ctx.check(self._lib.aesfhe_export_pk_half(self._ctx.ptr, out, out.size))
+        return out
+
+    def export_key_half(self, galois: int, level: int = -1, out: np.ndarray | None = None) -> np.ndarray:
+        """the b half of the key (galois, level), flat uint32, half of ksk_words: [dnum][nkey][N] for a full key,
+        [nkey][N] for the dense -> sparse key and a reduced level's (aesfhe_export_ksk_half); `out`: a reused host
+        buffer of at least its size.  Needs a mask key"""
+        self._ensure_keys()
+        words = self.ksk_words(galois, level) // 2
+        buf = np.empty(words, np.uint32) if out is None else out.reshape(-1)[:words]
+        self._ctx.check(self._lib.aesfhe_export_ksk_half(self._ctx.ptr, int(galois), int(level), buf, words))
+        return buf
+
+    def import_pk_half(self, data: np.ndarray):
+        """the client's public-key b half into an evaluation-only engine that holds the client's mask key"""
+        d = np.ascontiguousarray(data, np.uint32).reshape(-1)
+        self._ctx.check(self._lib.aesfhe_import_pk_half(self._ctx.ptr, d, d.size))
+        self._keys_ready = True
+
+    def import_ksk_half(self, galois: int, level: int, data: np.ndarray):
+        """one switching key from its b half, in the layout export_key_half wrote (aesfhe_import_ksk_half): the b
+        rows are checked and the a rows regenerated in one kernel launch; a refused half stores nothing"""
+        d = np.ascontiguousarray(data, np.uint32).reshape(-1)
+        self._ctx.check(self._lib.aesfhe_import_ksk_half(self._ctx.ptr, int(galois), int(level), d, d.size))
 
     def check(self, ct: Ciphertext):
         """the import check of a ciphertext (aesfhe_check): the first row, in [npoly][limbs] order, with a residue

@@ -75,6 +75,31 @@ int aesfhe_ensure_key(aesfhe_ctx* ctx, uint64_t galois, int level);
 /* The import check for a ciphertext handle (aesfhe_import itself checks nothing): *bad_row = the first row
  * ([npoly][limbs] order) holding a residue not below its modulus, or -1 when every residue is reduced. */
 int aesfhe_check(aesfhe_ctx* ctx, aesfhe_handle handle, int32_t* bad_row);
+/* Seed-compressed keys.  The MASK KEY is a second, PUBLIC 256-bit key: once set, the uniform `a`
+ * half of the public key and of every switching key is drawn under it (the secret, every error polynomial and the
+ * encryption samples stay under the context key), so a key travels as its `b` half and the receiver regenerates `a`
+ * on the device.  Without a mask key nothing changes.  aesfhe_set_mask_key is refused with a message: on a keyed
+ * context once any key exists (set it before aesfhe_keygen), when it equals the context's own key (publishing that
+ * key would publish the secret), and when a mask key is already set.  On an evaluation-only context it is set
+ * before the first half import.  aesfhe_has_mask_key: 1 / 0 (negative: no context); aesfhe_mask_key writes its 32
+ * bytes. */
+int aesfhe_set_mask_key(aesfhe_ctx* ctx, const uint8_t* key);
+int aesfhe_has_mask_key(aesfhe_ctx* ctx);
+int aesfhe_mask_key(aesfhe_ctx* ctx, uint8_t* out);
+/* The `b` halves of a keyed context's keys: [n_q][N] for the public key, [dnum][n_ks + n_p][N] for a full switching
+ * key (level -1), [nkey][N] for the dense -> sparse key and for a reduced level's key (level >= 0); `words` is the
+ * size of `out` and must be half of aesfhe_ksk_words (of 2 n_q N for the public key).  A switching key that is
+ * absent is generated, as by aesfhe_export_ksk.  Refused on a context without a mask key: keys made under the
+ * context key cannot be compressed, their `a` halves are not public. */
+int aesfhe_export_pk_half(aesfhe_ctx* ctx, uint32_t* out, uint64_t words);
+int aesfhe_export_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, uint32_t* out, uint64_t words);
+/* The same halves into an evaluation-only context that holds the exporter's mask key: the whole key is allocated,
+ * the `b` rows are copied into place and one kernel launch checks them and writes every `a` row; the key is then
+ * word for word the exporter's (aesfhe_export_ksk on both sides agrees).  Refused as aesfhe_import_pk /
+ * aesfhe_import_ksk refuse, and without a mask key; a residue not below its modulus names its row in the half
+ * (digit * nkey + row) and stores nothing. */
+int aesfhe_import_pk_half(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words);
+int aesfhe_import_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words);
 /* Encryption randomness (v, e0, e1 of every encryption, the renorms' re-encryptions included)
  * is drawn under the context key with `nonce` folded into key words 6-7; key material is not
  * affected.  Processes sharing one context key (the ranks of a multi-GPU job) must
