@@ -161,10 +161,12 @@ struct ValueTab {
     double mag_t = 0.0, mag_r = 0.0;  // sum over T's / R's channels of max_b |E_p[b]|
 };
 
-// the byte-table decode's coefficient table: K[p][q + 7][b], [9][16][256] complex double on the device
+// the byte-table decode's coefficient tables: a bank of n_tables tables K[p][q + 7][b],
+// [n_tables][9][16][256] complex double on the device; a single table is the bank of one
 struct ByteTab {
     std::pair<u32*, size_t> tab{nullptr, 0};
-    double mag[kByteLutGroups] = {};  // per group q: sum_p max_b |K_pq[b]|
+    int n_tables = 1;
+    double mag[kByteLutGroups] = {};  // per group q: max over the tables of sum_p max_b |K_pq[b]|
 };
 
 struct Pt {
@@ -2102,23 +2104,31 @@ public:
     // f(x ^ b) = C_00 + T + conj(T), T = sum_{q = -7..8} y_q U_q, U_q = sum_{p = 0..8} K_pq[b] a^p: the engine forms the
     // 16 sums U_q (ciphertext x per-slot plaintext, the p = 0 column a plaintext added inside the sum); the ct x ct
     // products with the lo-side operands y_q and the conjugation are the caller's.  K (made by Python,
-    // coeffgen.byte_value_table) is uploaded once, waiting for its copy once as value_create does
-    aesfhe_handle byte_lut_create(const double* re, const double* im) {
-        if (!re || !im) throw std::runtime_error("byte_lut_create: missing table");
+    // coeffgen.byte_value_table) is uploaded once, waiting for its copy once as value_create does.  A bank (DESIGN.md
+    // §3.26) is n_tables of them back to back, the slot's table chosen by a selector byte; the owed rescale's magnitude
+    // bound is the largest of the tables'.  byte_lut_create is the bank of one
+    aesfhe_handle byte_lut_bank_create(const std::string& who, const double* re, const double* im, int n_tables) {
+        if (n_tables < 1 || n_tables > kByteLutBankMax) throw std::runtime_error(who + ": n_tables must be 1..64");
+        if (!re || !im) throw std::runtime_error(who + ": missing table");
         ByteTab B;
+        B.n_tables = n_tables;
         const size_t n = (size_t)kByteLutRows * kByteLutGroups * 256;
-        std::vector<double> h(2 * n);
-        for (int p = 0; p < kByteLutRows; ++p)
-            for (int q = 0; q < kByteLutGroups; ++q) {
-                double top = 0.0;
-                for (int b = 0; b < 256; ++b) {
-                    const size_t c = ((size_t)p * kByteLutGroups + q) * 256 + b;
-                    if (!std::isfinite(re[c]) || !std::isfinite(im[c])) throw std::runtime_error("byte_lut_create: table entry not finite");
-                    h[2 * c] = re[c], h[2 * c + 1] = im[c];
-                    top = std::max(top, std::hypot(re[c], im[c]));
+        std::vector<double> h(2 * n * n_tables);
+        for (int t = 0; t < n_tables; ++t) {
+            double mag[kByteLutGroups] = {};
+            for (int p = 0; p < kByteLutRows; ++p)
+                for (int q = 0; q < kByteLutGroups; ++q) {
+                    double top = 0.0;
+                    for (int b = 0; b < 256; ++b) {
+                        const size_t c = t * n + ((size_t)p * kByteLutGroups + q) * 256 + b;
+                        if (!std::isfinite(re[c]) || !std::isfinite(im[c])) throw std::runtime_error(who + ": table entry not finite");
+                        h[2 * c] = re[c], h[2 * c + 1] = im[c];
+                        top = std::max(top, std::hypot(re[c], im[c]));
+                    }
+                    mag[q] += top;
                 }
-                B.mag[q] += top;
-            }
+            for (int q = 0; q < kByteLutGroups; ++q) B.mag[q] = std::max(B.mag[q], mag[q]);
+        }
         ensure_slot_pos();
         const size_t words = (2 * h.size() + (size_t)hp_.n - 1) / hp_.n * hp_.n;
         u32* d = alloc_words(words);
@@ -2141,17 +2151,20 @@ public:
     struct ByteStage {
         const uint8_t* nib = nullptr;  // both nibble arrays, hi then lo
         const double* wt = nullptr;    // [slots]
+        const uint8_t* sel = nullptr;  // [slots] the slot's table of a bank; null: table 0 everywhere
         double top = 0.0;              // max |w|
     };
     // nibbles and weights checked and copied into this stream's staging buffer (its own) in ONE copy: s doubles, then
-    // 2 s nibble bytes
-    ByteStage stage_byte_lut(const std::string& who, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, const double* weights) {
+    // 2 s nibble bytes.  A bank's selector (sel, every entry < n_tables) follows them in the same buffer, with one
+    // more copy on the stream
+    ByteStage stage_byte_lut(const std::string& who, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, const double* weights,
+                             const uint8_t* sel = nullptr, int n_tables = 1) {
         const int s = slot_count();
         need_slots(who, nib_hi && nib_lo && n_slots == s);
         if (!weights) throw std::runtime_error(who + ": missing weights");
         const size_t o_nib = (size_t)s * sizeof(double), bytes = o_nib + (size_t)2 * s;
         std::vector<uint8_t>& h = h_blut_[t_sidx];
-        h.resize(bytes);
+        h.resize(bytes + s);
         ByteStage st;
         for (int j = 0; j < s; ++j) {
             if (!std::isfinite(weights[j])) throw std::runtime_error(who + ": weight not finite at slot " + std::to_string(j));
@@ -2160,11 +2173,21 @@ public:
         std::memcpy(h.data(), weights, o_nib);
         copy_nibbles(who, nib_hi, h.data() + o_nib);
         copy_nibbles(who, nib_lo, h.data() + o_nib + s);
-        if (!d_blut_[t_sidx]) d_blut_[t_sidx] = (uint8_t*)dev_alloc((bytes + 3) / 4);
+        if (sel)
+            for (int j = 0; j < s; ++j) {
+                if (sel[j] >= n_tables)
+                    throw std::runtime_error(who + ": table index out of range (>= " + std::to_string(n_tables) + ") at slot " + std::to_string(j));
+                h[bytes + j] = sel[j];
+            }
+        if (!d_blut_[t_sidx]) d_blut_[t_sidx] = (uint8_t*)dev_alloc((bytes + s + 3) / 4);
         uint8_t* d = d_blut_[t_sidx];
         HIP_OK(hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, S()));
         st.wt = (const double*)d;
         st.nib = d + o_nib;
+        if (sel) {
+            HIP_OK(hipMemcpyAsync(d + bytes, h.data() + bytes, s, hipMemcpyHostToDevice, S()));
+            st.sel = d + bytes;
+        }
         return st;
     }
     // one chunk's product plaintexts: channel g kByteLutTerms + (p - 1) holds w K_pq[b] for group q index g0 + g and
@@ -2175,7 +2198,8 @@ public:
         return encode_channels(gc / 2, kValueCh, scale, nl, [&](int pass, double* w) {
             ByteLutSlotArgs ch;
             for (int c = 0; c < kValueCh; ++c) ch.row[c] = ((c % kByteLutTerms) + 1) * kByteLutGroups + g0 + 2 * pass + c / kByteLutTerms;
-            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, kValueCh, st.nib, st.wt, d_slot_pos_);
+            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, kValueCh, st.nib, st.wt, st.sel, B.n_tables,
+                                  d_slot_pos_);
         });
     }
     // one chunk's fills: channel g holds w K_0q[b] for group q index g0 + g at `scale` (the product scale of the sum
@@ -2184,23 +2208,24 @@ public:
         return encode_channels(1, gc, scale, nl, [&](int, double* w) {
             ByteLutSlotArgs ch;
             for (int c = 0; c < gc; ++c) ch.row[c] = g0 + c;
-            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, gc, st.nib, st.wt, d_slot_pos_);
+            launch_byte_lut_slots(S(), T_, w, (const double*)B.tab.first, kByteLutRows * kByteLutGroups, ch, gc, st.nib, st.wt, st.sel, B.n_tables,
+                                  d_slot_pos_);
         });
     }
     // out[q + 7] = U_q = sum_{p = 1..8} w K_pq[b] (.) a^p + (w K_0q[b] as a plaintext) for q = -7..8.  A_hi is indexed by
     // the power p (entry 0 unused), the operands canonical and dropped exactly to their common lowest logical level l
     // as value_decode's; the 16 groups are walked in chunks of kByteLutChunk: one bounded codec buffer and ONE
     // k_byte_lut_mac launch per chunk, every chunk reading the same canonical operands.  The fill is encoded at
-    // ct scale x ptscale[l] = raw_scale(l, 1), the scale of the sums before their owed rescale
-    void byte_lut_public(aesfhe_handle hb, const aesfhe_handle* A_hi, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
-                         const double* weights, Ct* oU) {
-        const std::string who = "byte_lut_public";
+    // ct scale x ptscale[l] = raw_scale(l, 1), the scale of the sums before their owed rescale.  sel:
+    // the slot's table of the bank hb, K = K^(sel[j]); null: table 0 everywhere, which is byte_lut_public
+    void byte_lut_decode(const std::string& who, aesfhe_handle hb, const aesfhe_handle* A_hi, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                         const uint8_t* sel, int n_slots, const double* weights, Ct* oU) {
         const ByteTab& B = btab(hb);
         if (!A_hi) throw std::runtime_error(who + ": missing element handles");
         aesfhe_handle A[kByteLutTerms];
         for (int t = 0; t < kByteLutTerms; ++t) A[t] = A_hi[t + 1];
         const int l = public_operands(who, "byte table decode", A, kByteLutTerms);
-        const ByteStage st = stage_byte_lut(who, nib_hi, nib_lo, n_slots, weights);
+        const ByteStage st = stage_byte_lut(who, nib_hi, nib_lo, n_slots, weights, sel, B.n_tables);
         const int nl = hp_.nl(l);
         Ct out[kByteLutGroups];
         public_op([&](PubTemps& s) {
@@ -2228,13 +2253,26 @@ public:
         });
         for (int g = 0; g < kByteLutGroups; ++g) oU[g] = out[g];
     }
+    void byte_lut_public(aesfhe_handle hb, const aesfhe_handle* A_hi, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
+                         const double* weights, Ct* oU) {
+        byte_lut_decode("byte_lut_public", hb, A_hi, nib_hi, nib_lo, nullptr, n_slots, weights, oU);
+    }
+    // byte_lut_public with a table per slot: a missing selector is refused here, an index past the bank by the staging
+    static void need_sel(const std::string& who, const uint8_t* sel) {
+        if (!sel) throw std::runtime_error(who + ": missing table index (sel)");
+    }
+    void byte_lut_bank_public(aesfhe_handle hb, const aesfhe_handle* A_hi, const uint8_t* nib_hi, const uint8_t* nib_lo, const uint8_t* sel,
+                              int n_slots, const double* weights, Ct* oU) {
+        need_sel("byte_lut_bank_public", sel);
+        byte_lut_decode("byte_lut_bank_public", hb, A_hi, nib_hi, nib_lo, sel, n_slots, weights, oU);
+    }
     // tests: the 16 x 9 encoded rows -- group q index g, then p = 0 (the fill, at scales[1]) and p = 1..8 (at
-    // scales[0]) -- of nl(level) limbs each, encoded chunk by chunk as byte_lut_public does
-    void debug_byte_lut_pt(aesfhe_handle hb, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots, const double* weights, int level,
-                           u32* out, double* scales) {
+    // scales[0]) -- of nl(level) limbs each, encoded chunk by chunk as byte_lut_public does; sel as byte_lut_decode's
+    void debug_byte_lut_pt(const std::string& who, const std::string& op, aesfhe_handle hb, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                           const uint8_t* sel, int n_slots, const double* weights, int level, u32* out, double* scales) {
         const ByteTab& B = btab(hb);
-        debug_args("debug_byte_lut_pt", level, out, scales);
-        const ByteStage st = stage_byte_lut("byte_lut_public", nib_hi, nib_lo, n_slots, weights);
+        debug_args(who, level, out, scales);
+        const ByteStage st = stage_byte_lut(op, nib_hi, nib_lo, n_slots, weights, sel, B.n_tables);
         const int nl = hp_.nl(level);
         const size_t row = (size_t)nl * hp_.n;
         std::vector<u32> hf((size_t)kByteLutChunk * row), hp((size_t)kByteLutChunk * kByteLutTerms * row);
@@ -6418,7 +6456,13 @@ int aesfhe_xor_value_free(aesfhe_ctx* ctx, aesfhe_handle table) {
 int aesfhe_byte_lut_create(aesfhe_ctx* ctx, const double* re, const double* im, aesfhe_handle* out) {
     API_BEGIN
     if (!out) throw std::runtime_error("byte_lut_create: missing output handle");
-    *out = ctx->eng->byte_lut_create(re, im);
+    *out = ctx->eng->byte_lut_bank_create("byte_lut_create", re, im, 1);
+    API_END
+}
+int aesfhe_byte_lut_bank_create(aesfhe_ctx* ctx, const double* re, const double* im, int n_tables, aesfhe_handle* out) {
+    API_BEGIN
+    if (!out) throw std::runtime_error("byte_lut_bank_create: missing output handle");
+    *out = ctx->eng->byte_lut_bank_create("byte_lut_bank_create", re, im, n_tables);
     API_END
 }
 int aesfhe_byte_lut_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_handle* a_hi, const uint8_t* nib_hi, const uint8_t* nib_lo,
@@ -6432,7 +6476,22 @@ int aesfhe_byte_lut_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_ha
 }
 int aesfhe_debug_byte_lut_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
                              const double* weights, int level, uint32_t* out, double* scales) {
-    API_BEGIN ctx->eng->debug_byte_lut_pt(table, nib_hi, nib_lo, n_slots, weights, level, out, scales);
+    API_BEGIN ctx->eng->debug_byte_lut_pt("debug_byte_lut_pt", "byte_lut_public", table, nib_hi, nib_lo, nullptr, n_slots, weights, level, out, scales);
+    API_END
+}
+int aesfhe_byte_lut_bank_public(aesfhe_ctx* ctx, aesfhe_handle bank, const aesfhe_handle* a_hi, const uint8_t* nib_hi, const uint8_t* nib_lo,
+                                const uint8_t* sel, int n_slots, const double* weights, aesfhe_handle* out) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out) throw std::runtime_error("byte_lut_bank_public: missing output handles");
+    Ct u[kByteLutGroups];
+    e.byte_lut_bank_public(bank, a_hi, nib_hi, nib_lo, sel, n_slots, weights, u);
+    for (int g = 0; g < kByteLutGroups; ++g) out[g] = e.put_ct(u[g]);
+    API_END
+}
+int aesfhe_debug_byte_lut_bank_pt(aesfhe_ctx* ctx, aesfhe_handle bank, const uint8_t* nib_hi, const uint8_t* nib_lo, const uint8_t* sel,
+                                  int n_slots, const double* weights, int level, uint32_t* out, double* scales) {
+    API_BEGIN Engine::need_sel("debug_byte_lut_bank_pt", sel);
+    ctx->eng->debug_byte_lut_pt("debug_byte_lut_bank_pt", "byte_lut_bank_public", bank, nib_hi, nib_lo, sel, n_slots, weights, level, out, scales);
     API_END
 }
 int aesfhe_byte_lut_free(aesfhe_ctx* ctx, aesfhe_handle table) {

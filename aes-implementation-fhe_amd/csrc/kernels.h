@@ -669,15 +669,19 @@ void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunk
 // kByteLutRows x 16 rows of 256 complex doubles at the slot's public BYTE.  launch_byte_lut_slots writes the codec's
 // FFT input: channel c takes row row[c] of the table,  w[c][slot j] = wt[j] * tab[row[c]][16 nib[j] + nib[N/2 + j]],
 // in launch_value_slots_typed's output order (nib: the hi array, then the lo array).
+// A BANK is n_tables such tables back to back and one selector byte per slot: slot j reads table
+// sel[j] (< n_tables, the caller's check), i.e. tab[(sel[j] tab_rows + row[c]) 256 + byte]; sel null: table 0
+// for every slot, uniform over the launch.
 constexpr int kByteLutRows = 9;    // p = 0..8
 constexpr int kByteLutGroups = 16;  // q = -7..8
 constexpr int kByteLutTerms = 8;    // the ciphertext powers a^1..a^8 of one sum
 constexpr int kByteLutChunk = 8;    // groups per MAC launch and codec buffer
+constexpr int kByteLutBankMax = 64; // tables per bank: 64 x 9 x 16 x 256 complex doubles = 36 MiB
 struct ByteLutSlotArgs {
     int row[kValueCh] = {};
 };
 void launch_byte_lut_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ByteLutSlotArgs& ch, int nch,
-                           const uint8_t* nib, const double* wt, const u32* slot_pos);
+                           const uint8_t* nib, const double* wt, const uint8_t* sel, int n_tables, const u32* slot_pos);
 // out[g] = sum_{t < n} a[t] (.) pt[g kByteLutTerms + t] + fill[g] (c0 only) for `groups` sums in ONE launch: every
 // ciphertext word is read once and multiplied into all groups, `groups` 64-bit sums in registers, the fill word (a
 // residue, < 2^30) added before the one reduction.  pt: groups x kByteLutTerms channels of nl limbs, fill: groups

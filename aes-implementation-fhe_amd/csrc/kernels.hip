@@ -1457,15 +1457,18 @@ __global__ void __launch_bounds__(kBlock) k_value_slots_typed(double2* w, const 
 // 256-column rows.  Channel c takes row a.row[c] at the slot's public byte 16 nib_hi + nib_lo (the two nibble arrays
 // of N/2 bytes back to back), times the slot's weight.  The map is a kernel argument: uniform per block, read by the
 // scalar unit.  One lane per slot, both nibbles and the weight read coalesced; the 4 KiB rows are gathered through
-// L1 / L2 (a launch reads at most 16 of them)
-__global__ void __launch_bounds__(kBlock) k_byte_lut_slots(double2* w, const double2* tab, ByteLutSlotArgs a, const uint8_t* nib,
-                                                           const double* wt, const u32* slot_pos, int logn) {
+// L1 / L2 (a launch reads at most 16 of them per table).  sel: the slot's table of a bank of
+// tab_rows-row tables stored back to back, one byte per slot read coalesced next to the nibbles; null: table 0 for
+// every slot -- uniform over the launch, like k_value_slots_typed's wt / flags
+__global__ void __launch_bounds__(kBlock) k_byte_lut_slots(double2* w, const double2* tab, ByteLutSlotArgs a, int tab_rows, const uint8_t* nib,
+                                                           const double* wt, const uint8_t* sel, const u32* slot_pos, int logn) {
     const int c = blockIdx.y;
     const int j = blockIdx.x * kBlock + threadIdx.x;  // slot < N/2
     const int n = 1 << logn;
     if (j >= n / 2) return;
     const u32 b = ((u32)(nib[j] & 15) << 4) | (u32)(nib[(size_t)(n / 2) + j] & 15);
-    const double2 e = tab[(size_t)a.row[c] * 256 + b];
+    const size_t t0 = sel ? (size_t)sel[j] * tab_rows : 0;
+    const double2 e = tab[(t0 + a.row[c]) * 256 + b];
     const double wj = wt[j];
     const double2 v = make_double2(e.x * wj, e.y * wj);
     const u32 t = slot_pos[j];
@@ -2449,15 +2452,16 @@ void launch_value_chunk_mac(hipStream_t st, const DevTables& T, const ValueChunk
     value_chunk_mac<kValueChunk>(st, T, 2.0 * nl * (n + 2 * groups) + (double)groups * n * nl, out, groups, a, n, pt, nl, map);
 }
 void launch_byte_lut_slots(hipStream_t st, const DevTables& T, double* w, const double* tab, int tab_rows, const ByteLutSlotArgs& ch, int nch,
-                           const uint8_t* nib, const double* wt, const u32* slot_pos) {
+                           const uint8_t* nib, const double* wt, const uint8_t* sel, int n_tables, const u32* slot_pos) {
     if (nch < 1 || nch > kValueCh || !w || !tab || !nib || !wt || !slot_pos) throw std::runtime_error("launch_byte_lut_slots: 1..16 channels");
+    if (n_tables < 1 || n_tables > kByteLutBankMax) throw std::runtime_error("launch_byte_lut_slots: 1..64 tables");
     for (int c = 0; c < nch; ++c)
         if (ch.row[c] < 0 || ch.row[c] >= tab_rows) throw std::runtime_error("launch_byte_lut_slots: bad channel map");
     const double s = (double)(1u << (T.logn - 1));
     const unsigned gx = ((1u << (T.logn - 1)) + kBlock - 1) / kBlock;
-    // reads: two nibbles, the weight, the slot position and one table entry; writes: two complex doubles
-    prof_launch(KID_ELEMENTWISE, nch * (2.0 * s + 8.0 * s + 4.0 * s + 16.0 * s + 32.0 * s), k_byte_lut_slots, dim3(gx, nch), dim3(kBlock), 0, st,
-                (double2*)w, (const double2*)tab, ch, nib, wt, slot_pos, T.logn);
+    // reads: two nibbles (and the selector byte), the weight, the slot position and one table entry; writes: two complex doubles
+    prof_launch(KID_ELEMENTWISE, nch * ((sel ? 3.0 : 2.0) * s + 8.0 * s + 4.0 * s + 16.0 * s + 32.0 * s), k_byte_lut_slots, dim3(gx, nch),
+                dim3(kBlock), 0, st, (double2*)w, (const double2*)tab, ch, tab_rows, nib, wt, sel, slot_pos, T.logn);
 }
 void launch_byte_lut_mac(hipStream_t st, const DevTables& T, const ByteLutMacArgs& a, int groups, int n, const u32* pt, const u32* fill, int nl,
                          LimbMap map) {

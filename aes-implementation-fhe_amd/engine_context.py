@@ -542,3 +542,9 @@ class EngineContext:
         the p = 0 column added as a plaintext inside each sum -- one engine call (DESIGN.md §3.23;
         Engine.byte_lut_public).  Modules test for it with getattr(ctx, "byte_lut_public", None)."""
         return self.engine.byte_lut_public(a_hi, nib_hi, nib_lo, K, weights)
+
+    def byte_lut_bank_public(self, a_hi, nib_hi, nib_lo, K, sel, weights):
+        """[U_q for q = -7..8]: byte_lut_public with a bank of tables K (T, 9, 16, 256) and a table index per slot
+        (sel, uint8) -- one engine call per output (Engine.byte_lut_bank_public).  Modules test for
+        it with getattr(ctx, "byte_lut_bank_public", None)."""
+        return self.engine.byte_lut_bank_public(a_hi, nib_hi, nib_lo, K, sel, weights)

@@ -55,6 +55,7 @@ EXPORTED = [
     "aesfhe_xor_value_typed", "aesfhe_debug_xor_value_typed_pt",
     "aesfhe_xor_value_groups", "aesfhe_debug_xor_value_groups_pt",
     "aesfhe_byte_lut_create", "aesfhe_byte_lut_public", "aesfhe_debug_byte_lut_pt", "aesfhe_byte_lut_free",
+    "aesfhe_byte_lut_bank_create", "aesfhe_byte_lut_bank_public", "aesfhe_debug_byte_lut_bank_pt",
     "aesfhe_create_eval", "aesfhe_has_secret", "aesfhe_eval_keys", "aesfhe_ksk_words", "aesfhe_import_pk", "aesfhe_import_ksk",
     "aesfhe_ensure_key", "aesfhe_check",
     "aesfhe_set_mask_key", "aesfhe_has_mask_key", "aesfhe_mask_key", "aesfhe_export_pk_half", "aesfhe_export_ksk_half",
@@ -167,6 +168,9 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_byte_lut_public"] = [vp, _H, _Hp, _bp, _bp, c_int, vp, _Hp]
     sig["aesfhe_debug_byte_lut_pt"] = [vp, _H, _bp, _bp, c_int, vp, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_byte_lut_free"] = [vp, _H]
+    sig["aesfhe_byte_lut_bank_create"] = sig["aesfhe_byte_lut_create"][:3] + [c_int] + sig["aesfhe_byte_lut_create"][3:]
+    sig["aesfhe_byte_lut_bank_public"] = [vp, _H, _Hp, _bp, _bp, vp, c_int, vp, _Hp]
+    sig["aesfhe_debug_byte_lut_bank_pt"] = [vp, _H, _bp, _bp, vp, c_int, vp, c_int, _up, ctypes.POINTER(c_dbl)]
     sig["aesfhe_level_limbs"] = [vp, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     sig["aesfhe_set_enc_nonce"] = [vp, ctypes.c_uint64]
     sig["aesfhe_set_low_p"] = [vp, c_int]
@@ -309,7 +313,8 @@ class ValueTable(_Handle):
 
 
 class ByteTable(_Handle):
-    """The 9 x 16 x 256 coefficient table of the byte-table decode on the device (aesfhe_byte_lut_create)."""
+    """The 9 x 16 x 256 coefficient table of the byte-table decode on the device (aesfhe_byte_lut_create), or a bank of
+    up to 64 of them (aesfhe_byte_lut_bank_create)."""
 
     __slots__ = ()
 
@@ -1361,6 +1366,55 @@ class Engine:
         out = np.zeros((16, 9, self.nl(level), self.n), np.uint32)
         scales = (ctypes.c_double * 2)()
         self._ctx.check(self._lib.aesfhe_debug_byte_lut_pt(self._ctx.ptr, tab.handle, nh, nl_, int(nh.size), w, int(level), out, scales))
+        return out, scales[0], scales[1]
+
+    def _byte_bank(self, K) -> ByteTable:
+        """the device copy of a bank of byte-table decodes' K, (T, 9, 16, 256), uploaded once per bank"""
+        t = np.ascontiguousarray(np.asarray(K, np.complex128))
+        if t.ndim != 4 or t.shape[1:] != (9, 16, 256):
+            raise ValueError(f"byte_lut_bank_public: a (T, 9, 16, 256) complex table bank, got {t.shape}")
+        cache, key = self._byte_tables, hashlib.sha256(b"bank" + t.tobytes()).digest()
+        if key not in cache:
+            h = ctypes.c_uint64()
+            self._ctx.check(self._lib.aesfhe_byte_lut_bank_create(self._ctx.ptr, np.ascontiguousarray(t.real), np.ascontiguousarray(t.imag),
+                                                                  int(t.shape[0]), ctypes.byref(h)))
+            cache[key] = ByteTable(self._ctx, h.value)
+        return cache[key]
+
+    @staticmethod
+    def _sel_arg(sel):
+        """(pointer, keep-alive) of a selector: contiguous uint8, or None (the engine refuses a null pointer)"""
+        if sel is None:
+            return None, None
+        s = np.ascontiguousarray(np.asarray(sel))
+        if s.dtype != np.uint8 or s.ndim != 1:
+            raise ValueError(f"byte table selector: a one-dimensional uint8 array, got {s.dtype} {s.shape}")
+        return s.ctypes.data_as(ctypes.c_void_p), s
+
+    def byte_lut_bank_public(self, a_hi, nib_hi, nib_lo, K, sel, weights):
+        """byte_lut_public with a table per slot (aesfhe_byte_lut_bank_public): slot j's coefficients
+        come from K[sel[j]].  K: (T, 9, 16, 256) complex, 1 <= T <= 64 (uploaded once per bank); sel: uint8, one table
+        index < T per slot, checked by the engine against the slot count ("slot_count") and T ("table index").
+        Everything else as byte_lut_public's"""
+        nh, nl_, w, _keep = self._byte_lut_args(nib_hi, nib_lo, weights, "byte_lut_bank_public")
+        sp, _skeep = self._sel_arg(sel)
+        self._ensure_keys()
+        tab = self._byte_bank(K)
+        out = (ctypes.c_uint64 * 16)()
+        n = int(nh.size) if _skeep is None or _skeep.size == nh.size else -1  # a selector of another length: not one per slot
+        self._ctx.check(self._lib.aesfhe_byte_lut_bank_public(self._ctx.ptr, tab.handle, self._power_handles(a_hi), nh, nl_, sp, n, w, out))
+        return [Ciphertext(self._ctx, out[g]) for g in range(16)]
+
+    def debug_byte_lut_bank_pt(self, nib_hi, nib_lo, K, sel, weights, level: int):
+        """tests: debug_byte_lut_pt for byte_lut_bank_public -- (rows, scale, fill_scale), the same order"""
+        nh, nl_, w, _keep = self._byte_lut_args(nib_hi, nib_lo, weights, "debug_byte_lut_bank_pt")
+        sp, _skeep = self._sel_arg(sel)
+        self._ensure_keys()
+        tab = self._byte_bank(K)
+        out = np.zeros((16, 9, self.nl(level), self.n), np.uint32)
+        scales = (ctypes.c_double * 2)()
+        n = int(nh.size) if _skeep is None or _skeep.size == nh.size else -1
+        self._ctx.check(self._lib.aesfhe_debug_byte_lut_bank_pt(self._ctx.ptr, tab.handle, nh, nl_, sp, n, w, int(level), out, scales))
         return out, scales[0], scales[1]
 
     @staticmethod

@@ -52,7 +52,8 @@ last public XOR of counter mode fused with the value decode, no renorm after the
 gains and offsets, for no further level.  ``transcipher_linear`` / ``to_linear`` apply a 16 x 16 matrix
 per state to the decoded bytes inside the same step: the matrix's cyclic diagonals as weight groups of the decode.
 ``transcipher_lut`` / ``to_lut`` put an arbitrary 256-entry table of the byte in the slots instead, for
-one ct x ct level more.
+one ct x ct level more; ``transcipher_lut_bank`` / ``to_lut_bank`` take a bank of such tables, a table
+per byte, and return several outputs of one keystream.
 
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
 11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
@@ -704,6 +705,52 @@ class AESPipeline:
         check_layout(self.layout, ct_hi, ct_lo)
         lut = self._byte_lut(table, gain)
         return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+
+    # ---------------------------------------------------------------- a bank of byte tables: a table per slot, several outputs
+    def _byte_bank(self, tables, select, gain):
+        from xor_value_lut import ByteValueBank, bank_coefficients
+        t, _, c00s = bank_coefficients(tables)  # ValueError: not (T, 256) with 1 <= T <= 64, or a non-finite entry
+        try:
+            select = list(select)
+        except TypeError:
+            raise ValueError("byte table bank: select is a sequence of selectors, one per output") from None
+        if not select:
+            raise ValueError("byte table bank: select is empty (at least one output)")
+        scalar = np.isscalar(gain) or (isinstance(gain, np.ndarray) and gain.ndim == 0)
+        gains = [gain] * len(select) if scalar else list(gain)
+        if len(gains) != len(select):
+            raise ValueError(f"byte table bank: gain is one number or a sequence of {len(select)} (one per output), got {len(gains)}")
+        return ByteValueBank(self.ctx, t, [self.encoder.lut_bank_slots(s, g, c00s) for s, g in zip(select, gains)])
+
+    def _tag_bank(self, outs):
+        return [tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, ct)[0]) for ct in outs]
+
+    def transcipher_lut_bank(self, aes_ct: np.ndarray, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys, tables,
+                             select, gain=1.0):
+        """transcipher_lut with a BANK of tables, a table per byte and SEVERAL OUTPUTS from one keystream: a list of K
+        layout-tagged ciphertexts, output k's slot of byte i of state b holding
+            gain_k[b, i] * tables[select[k][b, i]][m[b, i]]
+        -- relu(q - zp_c) or clip(q - zp_c, lo_c, hi_c) with a zero point per channel, a codebook per field of a record,
+        or several numbers of one byte (eight flag bits, two int4 values, (sin, cos) of a phase byte).  tables:
+        (T, 256) finite reals, 1 <= T <= 64; select: a sequence of K >= 1 selectors, each integers in [0, T)
+        broadcastable to (16,) or (states, 16); gain: one gain for all outputs (a scalar) or a sequence of K, each a
+        scalar or broadcastable like a selector.  The keystream, the power bases and the seven conjugates are computed
+        once for all outputs (xor_value_lut.ByteValueBank); every output sits utils.BYTE_LUT_DEPTH = 5 levels below the
+        keystream, as transcipher_lut's.  Slots that hold no state hold 0; encoder.decode_values reads each output as
+        (states, 16)."""
+        self._no_pairs("transcipher_lut_bank")
+        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
+        bank = self._byte_bank(tables, select, gain)
+        ks = self.ctr_keystream(nonce12, counter0, round_keys)
+        return self._tag_bank(bank.apply_public(*ks, *nib))
+
+    def to_lut_bank(self, ct_hi, ct_lo, tables, select, gain=1.0):
+        """a clean layout-tagged (hi, lo) pair as K ciphertexts of gain_k * tables[select[k]][byte] per state slot
+        (ByteValueBank.apply; utils.BYTE_LUT_DEPTH levels below the pair); tables, select and gain as
+        transcipher_lut_bank's"""
+        self._no_pairs("to_lut_bank")
+        check_layout(self.layout, ct_hi, ct_lo)
+        return self._tag_bank(self._byte_bank(tables, select, gain).apply(ct_hi, ct_lo))
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):

@@ -430,6 +430,30 @@ class StateEncoder:
         weights = self._float_slots(g)
         return weights, weights * float(c00)
 
+    def lut_bank_slots(self, select, gain=1.0, c00s=(0.0,)):
+        """(sel, weights, const): lut_slots for a BANK of byte tables (xor_value_lut.ByteValueBank).
+        select: the table of each byte -- integers in [0, T), T = len(c00s), broadcastable to (16,) or (states, 16) in
+        the caller's byte order; sel: uint8 per slot, the slot's table index and 0 in every slot that holds no state;
+        weights as lut_slots'; const = weights * c00s[sel] (each slot's own table's mean).  _float_slots places the
+        indices as it places the gains, so both layouts and the transposed byte order work"""
+        if self.pairs > 1:
+            raise ValueError("lut_bank_slots: multi-pair batches (pairs > 1) are not supported")
+        c = np.asarray(c00s, np.float64)
+        if c.ndim != 1 or not 1 <= c.size <= 256 or not np.all(np.isfinite(c)):
+            raise ValueError("lut_bank_slots: c00s must be 1..256 finite reals, one per table")
+        s = np.asarray(select)
+        if s.dtype == bool or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError(f"lut_bank_slots: select must be integers (table indices), got dtype {s.dtype}")
+        try:
+            s = np.broadcast_to(s, (self.states, 16))
+        except ValueError:
+            raise ValueError(f"lut_bank_slots: select must broadcast to (16,) or ({self.states}, 16)") from None
+        if s.min() < 0 or s.max() >= c.size:
+            raise ValueError(f"lut_bank_slots: select must lie in [0, {c.size})")
+        weights = self.lut_slots(gain)[0]
+        sel = np.ascontiguousarray(self._float_slots(s.astype(np.float64)).astype(np.uint8))
+        return sel, weights, weights * c[sel]
+
     def values_from_slots(self, slots: np.ndarray, dtype=None) -> np.ndarray:
         """the pure unpacking of decode_values: a slot vector whose word slots hold one real number per word
         (xor_value_lut's output) -> the (states, 16 // w) float array in the caller's byte order, (16 // w,) for one

@@ -21,7 +21,8 @@ in an XOR4, a renorm and a separate decode: AESPipeline.transcipher_values.
 
 TypedValueLUT (DESIGN.md §3.21) is the same sum with per-slot weights, a signed top nibble and 16-bit words;
 LinearValueLUT carries a 16 x 16 matrix per state in up to 16 weight groups.  ByteValueLUT
- decodes through an arbitrary 256-entry table of the byte instead, for one ct x ct level more.
+(DESIGN.md §3.23) decodes through an arbitrary 256-entry table of the byte instead, for one ct x ct level more;
+ByteValueBank through a bank of such tables, one per slot, into several outputs of one keystream.
 """
 from typing import Any, Dict
 
@@ -308,3 +309,102 @@ class ByteValueLUT(XorValueLUT):
         for t in mul_many(ctx, [(y[q], U[qi]) for qi, q in enumerate(BYTE_LUT_Q) if q != 0]):
             T = ctx.add(T, t)
         return ctx.add_plain(ctx.add(T, ctx.conjugate(T)), self.const)
+
+
+BYTE_LUT_BANK_MAX = 64  # tables per bank (the engine's kByteLutBankMax)
+
+
+def bank_coefficients(tables):
+    """(tables, K, c00) of a bank of byte tables: (T, 256) float64, (T, 9, 16, 256) complex and the T means
+    (coeffgen.byte_value_table per table).  ValueError: not (T, 256) with 1 <= T <= 64, or a non-finite entry"""
+    t = np.asarray(tables, np.float64)
+    if t.ndim != 2 or t.shape[1] != 256 or not 1 <= t.shape[0] <= BYTE_LUT_BANK_MAX:
+        raise ValueError(f"byte table bank: (T, 256) reals with 1 <= T <= {BYTE_LUT_BANK_MAX}, got shape {t.shape}")
+    made = [byte_value_table(f) for f in t]
+    return t.copy(), np.ascontiguousarray(np.stack([k for k, _ in made])), np.array([c for _, c in made], np.float64)
+
+
+class ByteValueBank(XorValueLUT):
+    """ByteValueLUT with a BANK of tables, a table per slot and several outputs per call: output k's
+    slot j holds weights_k[j] * tables[sel_k[j]][byte ^ public byte] -- a per-channel zero point inside a non-linearity,
+    a per-field codebook, eight flag bits or two int4 values of one byte.
+
+    The ciphertext side of ByteValueLUT does not change: f(x ^ b) = C_00 + T + conj(T), T = sum_q y_q U_q,
+    U_q = sum_p w K_pq[b] a^p; only the public per-slot coefficients do, slot j reading K^(sel[j]).  The power bases
+    a^1..a^8 / c^1..c^8 and the seven conjugates conj(c^1..c^7) are computed ONCE per call; every output has its own
+    16 sums U_q (one engine call each), its own 15 ct x ct products and its own conjugation, the products of all
+    outputs in one multiply_many batch and the conjugations in one conjugate_many.  DEPTH as ByteValueLUT's.
+
+    tables: (T, 256) finite reals, 1 <= T <= 64; outputs: K >= 1 triples (sel, weights, const) of per-slot vectors
+    (StateEncoder.lut_bank_slots: sel uint8 in [0, T))."""
+
+    DEPTH = BYTE_LUT_DEPTH
+
+    def __init__(self, ctx, tables, outputs):
+        self.ctx = ctx
+        self.sc = ctx.engine.slot_count
+        self.tables, self.K, self.c00 = bank_coefficients(tables)
+        t = self.tables
+        outputs = list(outputs)
+        if not outputs:
+            raise ValueError("byte table bank: at least one output (sel, weights, const)")
+        self.outputs = []
+        for sel, weights, const in outputs:
+            s, w, c = np.asarray(sel), np.asarray(weights, np.float64), np.asarray(const, np.float64)
+            if s.shape != (self.sc,) or s.dtype != np.uint8 or int(s.max()) >= len(t):
+                raise ValueError(f"byte table bank: one uint8 table index < {len(t)} per slot ({self.sc}), got {s.dtype} {s.shape}")
+            if w.shape != (self.sc,) or c.shape != (self.sc,) or not (np.all(np.isfinite(w)) and np.all(np.isfinite(c))):
+                raise ValueError(f"byte table bank: weights and const are one finite real per slot ({self.sc})")
+            self.outputs.append((np.ascontiguousarray(s), np.ascontiguousarray(w), np.ascontiguousarray(c)))
+
+    def _engine(self, A_hi, nib_hi, nib_lo, sel, weights):
+        """[U_q] of one output from Engine.byte_lut_bank_public, or None (_fused)"""
+        return self._fused("byte_lut_bank_public", A_hi, nib_hi, nib_lo, self.K, sel, weights)
+
+    def _loop(self, A_hi, nib_hi, nib_lo, sel, weights):
+        """[U_q] of one output as ByteValueLUT._loop's product loop, the coefficients gathered from the slot's table"""
+        ctx = self.ctx
+        b = 16 * nib_hi.astype(np.int64) + nib_lo.astype(np.int64)
+        t = sel.astype(np.int64)
+        out = []
+        for qi in range(len(BYTE_LUT_Q)):
+            U = None
+            for p in range(1, 9):
+                if not np.any(self.K[:, p, qi]):
+                    continue
+                term = ctx.multiply(A_hi[p], ctx.encode(weights * self.K[t, p, qi, b]))
+                U = term if U is None else ctx.add(U, term)
+            if U is None:
+                U = ctx.multiply(A_hi[1], ctx.encode(np.zeros(self.sc)))
+            if np.any(self.K[:, 0, qi]):
+                U = ctx.add_plain(U, weights * self.K[t, 0, qi, b])
+            out.append(U)
+        return out
+
+    def apply_public(self, hi, lo, nib_hi, nib_lo):
+        """[ciphertext k for k < K]: slot j of output k holds weights_k[j] * tables[sel_k[j]][(16 hi + lo) ^ (16 nib_hi +
+        nib_lo)], BYTE_LUT_DEPTH levels below the inputs (XorValueLUT.apply_public's operands)"""
+        ctx = self.ctx
+        nib_hi, nib_lo = self._nibbles(nib_hi), self._nibbles(nib_lo)
+        A_hi, A_lo = self._bases(hi, lo)
+        bars = conj_many(ctx, [A_lo[k] for k in range(1, 8)])  # conj(c^1..c^7): one batched conjugation for all outputs
+        y = {q: A_lo[q] if q > 0 else bars[-q - 1] for q in BYTE_LUT_Q if q != 0}
+        Us = []
+        for sel, weights, _ in self.outputs:
+            U = self._engine(A_hi, nib_hi, nib_lo, sel, weights)
+            Us.append(U if U is not None else self._loop(A_hi, nib_hi, nib_lo, sel, weights))
+        prods = iter(mul_many(ctx, [(y[q], U[qi]) for U in Us for qi, q in enumerate(BYTE_LUT_Q) if q != 0]))  # 15 K products
+        Ts = []
+        for U in Us:
+            T = U[BYTE_LUT_Q.index(0)]  # y_0 = 1
+            for _ in range(len(BYTE_LUT_Q) - 1):
+                T = ctx.add(T, next(prods))
+            Ts.append(T)
+        return [ctx.add_plain(ctx.add(T, bar), const) for T, bar, (_, _, const) in zip(Ts, conj_many(ctx, Ts), self.outputs)]
+
+    def apply(self, hi, lo):
+        """apply_public with zero nibbles: the tables of the bytes themselves"""
+        zero = np.zeros(self.sc, np.uint8)
+        return self.apply_public(hi, lo, zero, zero)
+
+    __call__ = apply

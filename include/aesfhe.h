@@ -309,8 +309,25 @@ int aesfhe_byte_lut_public(aesfhe_ctx* ctx, aesfhe_handle table, const aesfhe_ha
  * rows p >= 1, scales[1] (the product scale) of the fills */
 int aesfhe_debug_byte_lut_pt(aesfhe_ctx* ctx, aesfhe_handle table, const uint8_t* nib_hi, const uint8_t* nib_lo, int n_slots,
                              const double* weights, int level, uint32_t* out, double* scales);
-/* Releases a byte table; fails if `table` is not one.  aesfhe_free also accepts byte tables. */
+/* Releases a byte table or a bank of them; fails if `table` is not one.  aesfhe_free also accepts byte tables. */
 int aesfhe_byte_lut_free(aesfhe_ctx* ctx, aesfhe_handle table);
+/* A BANK of byte tables with one table per slot: n_tables coefficient tables K^(0..n_tables-1) of
+ * aesfhe_byte_lut_create's layout stored back to back -- re / im: [n_tables][9][16][256] doubles, 1 <= n_tables <= 64
+ * (576 KiB of device memory per table, 36 MiB at the cap) -- uploaded once (it waits for its copy once).  Refuses
+ * n_tables out of range ("n_tables") and a non-finite entry in any table.  The handle is a byte table handle: a bank
+ * of one is what aesfhe_byte_lut_create makes, aesfhe_byte_lut_public on a bank reads its table 0, and
+ * aesfhe_byte_lut_free releases it. */
+int aesfhe_byte_lut_bank_create(aesfhe_ctx* ctx, const double* re, const double* im, int n_tables, aesfhe_handle* out);
+/* aesfhe_byte_lut_public with a table per slot: out[q + 7] = U_q with slot j's coefficients taken from table sel[j] of
+ * `bank`, K_pq = K^(sel[j])_pq.  sel: one table index per slot (n_slots bytes), every entry < the bank's n_tables.
+ * Operands, outputs, levels and refusals as aesfhe_byte_lut_public's, plus: a missing sel or an entry >= n_tables
+ * ("table index"), checked like every other operand before any arithmetic kernel reads it.  One output (its own sel
+ * and weights) per call. */
+int aesfhe_byte_lut_bank_public(aesfhe_ctx* ctx, aesfhe_handle bank, const aesfhe_handle* a_hi, const uint8_t* nib_hi,
+                                const uint8_t* nib_lo, const uint8_t* sel, int n_slots, const double* weights, aesfhe_handle* out);
+/* tests only: aesfhe_debug_byte_lut_pt for aesfhe_byte_lut_bank_public (the same row order and scales) */
+int aesfhe_debug_byte_lut_bank_pt(aesfhe_ctx* ctx, aesfhe_handle bank, const uint8_t* nib_hi, const uint8_t* nib_lo, const uint8_t* sel,
+                                  int n_slots, const double* weights, int level, uint32_t* out, double* scales);
 /* Deferred evaluation switch, default on: API-level ct x ct products
  * leave relinearisation and their rescale to the first consumer that needs a
  * 2-polynomial canonical ciphertext (rotate, conjugate, ct x ct, power basis, bootstrap,
