@@ -342,6 +342,7 @@ public:
         if (it != cts_.end()) {
             give_back(it->second.data, it->second.words);
             cts_.erase(it);
+            sym_id_.erase(h);
             return;
         }
         auto il = luts_.find(h);
@@ -836,6 +837,123 @@ public:
         release(top);
         cnt_[C_ENC] += B;
         return out;
+    }
+
+    // ---- seeded symmetric encryption: c = (e + m - a s, a) at level f and scale delta_f, on exactly
+    // nl(f) limbs, no rescale.  a is the PRF under the PUBLIC mask key at stream_id(12, ctr, nonce16), so the
+    // ciphertext travels as its b rows plus the 56-bit id (ctr << 16) | nonce16; e is under enc_key() at
+    // stream_id(13, ctr, nonce16).  ctr comes from sym_ctr_, a counter of its own (enc_ctr_ and the public-key
+    // samples do not move); nonce16 = the low 16 bits of enc_nonce_ keeps ranks that share a context key apart.
+    // Three launches for all B members: the e samples (the coefficient-form messages ride in them), one NTT of
+    // B nl rows, k_sym_encrypt (per kSymMembers members).  The id stays with the handle for export_half_ct
+    static constexpr u64 kSymCtrEnd = 1ull << 40;
+    void sym_args(const char* who, int B, int level) const {
+        if (B < 1 || B > kEncMax) throw std::runtime_error(std::string(who) + ": batch size outside 1.." + std::to_string(kEncMax));
+        if (level < 0 || level > hp_.fresh)
+            throw std::runtime_error(std::string(who) + ": level out of range (0.." + std::to_string(hp_.fresh) + ", the fresh level)");
+    }
+    u64 encrypt_sym(const double* re, const double* im, int B, int level, aesfhe_handle* out) {
+        need_secret("encrypt_sym");
+        if (!has_mask_)
+            throw std::runtime_error("encrypt_sym: no mask key (a drawn under the context key cannot be published)");
+        if (!d_s_) throw std::runtime_error("keys not generated");
+        if (!re || !out) throw std::runtime_error("encrypt_sym: no data");
+        const int f = level == -1 ? hp_.fresh : level;
+        sym_args("encrypt_sym", B, f);
+        if (sym_ctr_ + (u64)B > kSymCtrEnd) throw std::runtime_error("encrypt_sym: the seed counter would reach 2^40");
+        const int n = hp_.n, nl = hp_.nl(f), sc = slot_count();
+        const size_t mw = (size_t)nl * n;
+        std::vector<std::vector<u32>> host(B);  // each member encoded where its copy reads it
+        std::vector<double> zero;
+        if (!im) zero.assign(sc, 0.0);
+        const u64 id0 = (sym_ctr_ << 16) | (enc_nonce_ & 0xFFFFull);
+        u32* em = tmp((size_t)B * nl);
+        std::vector<Ct> cts;
+        try {
+            for (int j = 0; j < B; ++j) {  // member j + 1 is encoded while member j's copy runs
+                encode_host(re + (size_t)j * sc, im ? im + (size_t)j * sc : zero.data(), hp_.delta[f], nl, host[j]);
+                HIP_OK(hipMemcpyAsync(em + j * mw, host[j].data(), mw * sizeof(u32), hipMemcpyHostToDevice, S()));
+            }
+            launch_sample_sym(S(), T_, em, nl, B, enc_key(), id0);
+            ntt(em, B * nl, nl, qmap());
+            for (int j = 0; j < B; ++j) cts.push_back(alloc_ct(f, 2));
+            for (int m0 = 0; m0 < B; m0 += kSymMembers) {
+                const int c = std::min(kSymMembers, B - m0);
+                SymPtrs sp;
+                for (int m = 0; m < c; ++m) sp.ct[m] = cts[m0 + m].data;
+                launch_sym_encrypt(S(), T_, sp, c, em + m0 * mw, d_s_, nl, qmap(), mask_, id0 + ((u64)m0 << 16));
+            }
+            HIP_OK(hipStreamSynchronize(S()));  // the host messages die with this call
+        } catch (...) {
+            (void)hipStreamSynchronize(S());
+            for (const Ct& c : cts) release(c);
+            untmp(em, (size_t)B * nl);
+            throw;
+        }
+        untmp(em, (size_t)B * nl);
+        sym_ctr_ += B;
+        cnt_[C_ENC] += B;
+        for (int j = 0; j < B; ++j) {
+            out[j] = put_ct(cts[j]);
+            sym_id_[out[j]] = id0 + ((u64)j << 16);
+        }
+        return id0;
+    }
+    // the b rows [nl][N] of a seeded fresh ciphertext and its id; any other handle (an operation's result, a
+    // public-key encryption, an import) is refused: its a rows are not the PRF's
+    void export_half_ct(aesfhe_handle h, u32* out, u64 words, u64* id) {
+        const Ct& c = ct(h);
+        auto it = sym_id_.find(h);
+        if (it == sym_id_.end()) throw std::runtime_error("export_half: not a seeded ciphertext");
+        if (!out || !id) throw std::runtime_error("export_half: no output");
+        const size_t want = c.words / 2;
+        if (words != want)
+            throw std::runtime_error("export_half: wrong word count (" + std::to_string(words) + ", this half has " + std::to_string(want) + ")");
+        HIP_OK(hipMemcpyAsync(out, c.data, want * sizeof(u32), hipMemcpyDeviceToHost, S()));
+        HIP_OK(hipStreamSynchronize(S()));
+        *id = it->second;
+    }
+    // B ciphertexts from their b rows (rows[j]: [nl][N], `words` words each) and B consecutive ids id0 + (j << 16): allocate, copy the
+    // b rows into place, one k_complete_ct launch (per kSymMembers members) checks them and writes every a row.  A
+    // refusal releases every allocation and stores nothing
+    void import_half_ct(const u32* const* rows, u64 words, int level, u64 id0, int B, aesfhe_handle* out) {
+        need_mask("import_half");
+        if (!rows || !out) throw std::runtime_error("import_half: no data");
+        sym_args("import_half", B, level);
+        if ((id0 >> 56) != 0 || (id0 >> 16) + (u64)B > kSymCtrEnd) throw std::runtime_error("import_half: id out of range (a counter below 2^40, a 16-bit nonce)");
+        const int n = hp_.n, nl = hp_.nl(level);
+        const size_t mw = (size_t)nl * n;
+        if (words != mw)
+            throw std::runtime_error("import_half: wrong word count (" + std::to_string(words) + ", a half at level " + std::to_string(level) +
+                                     " has " + std::to_string(mw) + ")");
+        for (int j = 0; j < B; ++j)
+            if (!rows[j]) throw std::runtime_error("import_half: no data");
+        if (!d_bad_) d_bad_ = dev_alloc(4);
+        std::vector<Ct> cts;
+        try {
+            u32 h = ~0u;
+            for (int j = 0; j < B; ++j) {
+                cts.push_back(alloc_ct(level, 2));
+                HIP_OK(hipMemcpyAsync(cts[j].data, rows[j], mw * sizeof(u32), hipMemcpyHostToDevice, S()));
+            }
+            HIP_OK(hipMemsetAsync(d_bad_, 0xff, sizeof(u32), S()));
+            for (int m0 = 0; m0 < B; m0 += kSymMembers) {
+                const int c = std::min(kSymMembers, B - m0);
+                SymPtrs sp;
+                for (int m = 0; m < c; ++m) sp.ct[m] = cts[m0 + m].data;
+                launch_complete_ct(S(), T_, sp, c, nl, qmap(), mask_, id0 + ((u64)m0 << 16), (u32)(m0 * nl), d_bad_);
+            }
+            HIP_OK(hipMemcpyAsync(&h, d_bad_, sizeof(u32), hipMemcpyDeviceToHost, S()));
+            HIP_OK(hipStreamSynchronize(S()));
+            if (h != ~0u)
+                throw std::runtime_error("import_half: residue not below its modulus in member " + std::to_string(h / (u32)nl) + ", row " +
+                                         std::to_string(h % (u32)nl) + " (nothing stored)");
+        } catch (...) {
+            (void)hipStreamSynchronize(S());
+            for (const Ct& c : cts) release(c);
+            throw;
+        }
+        for (int j = 0; j < B; ++j) out[j] = put_ct(cts[j]);
     }
 
     // decryption to real coefficients (message * delta_level)
@@ -6058,6 +6176,8 @@ private:
     std::map<u64, u32*> ksk_;
     u64 enc_ctr_ = 0;
     u64 enc_nonce_ = 0;  // see enc_key()
+    u64 sym_ctr_ = 0;    // seeded symmetric encryptions made (encrypt_sym): the next one's counter
+    std::unordered_map<aesfhe_handle, u64> sym_id_;  // handle of a seeded fresh ciphertext -> its 56-bit id
     std::vector<u32> im_;
     u32* d_rescale_qinv_ = nullptr;
     u32* d_rescale2_qinv_ = nullptr;
@@ -6265,6 +6385,19 @@ int aesfhe_import_pk_half(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words)
 }
 int aesfhe_import_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words) {
     API_BEGIN ctx->eng->import_ksk_half(galois, level, data, words);
+    API_END
+}
+int aesfhe_encrypt_sym(aesfhe_ctx* ctx, const double* re, const double* im, int count, int level, aesfhe_handle* out, uint64_t* id0) {
+    API_BEGIN const u64 id = ctx->eng->encrypt_sym(re, im, count, level, out);
+    if (id0) *id0 = id;
+    API_END
+}
+int aesfhe_export_half(aesfhe_ctx* ctx, aesfhe_handle handle, uint32_t* out, uint64_t words, uint64_t* id) {
+    API_BEGIN ctx->eng->export_half_ct(handle, out, words, (u64*)id);
+    API_END
+}
+int aesfhe_import_half(aesfhe_ctx* ctx, const uint32_t* const* rows, uint64_t words, int level, uint64_t id0, int count, aesfhe_handle* out) {
+    API_BEGIN ctx->eng->import_half_ct(rows, words, level, id0, count, out);
     API_END
 }
 int aesfhe_level_limbs(aesfhe_ctx* ctx, int32_t* out) {

@@ -457,6 +457,26 @@ void launch_sample_enc(hipStream_t st, const DevTables& T, u32* out, int nl, int
 // top: [m][2][nl]; vee: [m][3][nl] NTT form; msg: member m at msg + m msg_ms words; pk: [2][pk_rows][N]
 void launch_enc_combine(hipStream_t st, const DevTables& T, u32* top, const u32* vee, const u32* msg, size_t msg_ms, const u32* pk,
                         int pk_rows, int nl, int nm);
+// --- seeded symmetric encryption ---------------------------------------
+// c = (e + m - a s, a) with a the PRF under the public mask key: member j of a call has the 56-bit id
+// id0 + (j << 16) (stream_id's low part: counter << 16 | nonce16); its a rows are launch_sample_uniform's under
+// stream (12 << 56) | id, its e launch_sample_small's (kind 1) under stream (13 << 56) | id.  Members' outputs are
+// separate ciphertexts [2][nl][N], their pointers a by-value kernel argument: kSymMembers members per launch
+constexpr int kSymMembers = 32;
+constexpr u64 kSymStreamA = 12ull << 56, kSymStreamE = 13ull << 56;
+struct SymPtrs {
+    u32* ct[kSymMembers] = {};
+};
+// io: [nm][nl][N], on entry the coefficient-form messages, on return e + m (member j: stream kSymStreamE | id0 + (j << 16))
+void launch_sample_sym(hipStream_t st, const DevTables& T, u32* io, int nl, int nm, const PrngKey& key, u64 id0);
+// sp.ct[z][0][l] = em[z][l] - a s, sp.ct[z][1][l] = a for z < nm <= kSymMembers (em: NTT form, s: [primes][N] NTT form)
+void launch_sym_encrypt(hipStream_t st, const DevTables& T, const SymPtrs& sp, int nm, const u32* em, const u32* s, int nl, LimbMap map,
+                        const PrngKey& mask, u64 id0);
+// imported halves completed in one launch: sp.ct[z] holds its b rows in place; every b row is checked as
+// launch_check_residues checks it (*bad = min(*bad, bad0 + z nl + row), set to ~0u by the caller) and every a row is
+// written as launch_sym_encrypt wrote it
+void launch_complete_ct(hipStream_t st, const DevTables& T, const SymPtrs& sp, int nm, int nl, LimbMap map, const PrngKey& mask, u64 id0,
+                        u32 bad0, u32* bad);
 // raw decryption of up to 2 channels on their first kd[c] limbs: x[c][t] = c0 + c1 s (+ c2 s^2),
 // x: [2][4][N]; channel c reads ct[c] (npoly[c] polys of nlc[c] limbs); s, s2: NTT rows of s, s^2
 struct DecRaw {

@@ -807,6 +807,52 @@ __global__ void k_keygen_combine(u32* b, const u32* a, const u32* s, const u32* 
     if (l >= glo && l < ghi) v = add_mod(v, shoup_mul(sp[idx], gadget[2 * l], gadget[2 * l + 1], P.q), P.q);
     b[idx] = v;
 }
+// seeded symmetric encryption.  e of nm members added to their coefficient-form messages in place:
+// grid (N / kBlock, nm), k_sample_small's binomial value (kind 1) at stream kSymStreamE | id0 + (m << 16)
+__global__ void k_sample_sym(u32* io, int nl, PrngKey key, u64 id0, const PrimeConst* pc, int logn) {
+    const u32 m = blockIdx.y;
+    const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const u64 r = chacha_u64(key, kSymStreamE | (id0 + ((u64)m << 16)), k);
+    const int v = __popcll(r & 0x1FFFFFull) - __popcll((r >> 21) & 0x1FFFFFull);
+    u32* o = io + ((size_t)m * nl << logn) + k;
+    for (int l = 0; l < nl; ++l) {
+        const u32 q = pc[l].q;
+        o[(size_t)l << logn] = add_mod(v >= 0 ? (u32)v : q - (u32)(-v), o[(size_t)l << logn], q);
+    }
+}
+// grid (N / kBlock, nl, nm), one residue per thread: a = k_sample_uniform's word under the mask key at stream
+// kSymStreamA | id0 + (z << 16), formed in registers; b = (e + m) - a s with s at the row's prime index
+// (k_keygen_combine's read); a itself is the second polynomial.  ~10^3 integer operations per word: ALU-bound
+__global__ void __launch_bounds__(kBlock) k_sym_encrypt(SymPtrs sp, const u32* em, const u32* s, int nl, LimbMap map, PrngKey mask, u64 id0,
+                                                        const PrimeConst* pc, int logn) {
+    const u32 l = blockIdx.y, z = blockIdx.z;
+    const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const int prime = map.prime((int)l);
+    const PrimeConst P = pc[prime];
+    const u32 a = (u32)(chacha_u64(mask, kSymStreamA | (id0 + ((u64)z << 16)), ((u64)prime << logn) + k) % P.q);
+    const size_t idx = ((size_t)l << logn) + k;
+    u32* o = sp.ct[z];
+    o[idx] = sub_mod(em[((size_t)z * nl << logn) + idx], barrett_mul(a, s[((size_t)prime << logn) + k], P.q, P.mu), P.q);
+    o[((size_t)nl << logn) + idx] = a;
+}
+// imported halves completed in place: grid (N / kBlock, 2 nl, nm), the branch block-uniform on the row.  Rows
+// y < nl of member z are its b rows, checked as k_complete_key checks a key's (the row's modulus, one wave vote, at
+// most one lane per wave lowers *bad to bad0 + z nl + y, no early exit); rows y >= nl its a rows, k_sym_encrypt's words
+__global__ void __launch_bounds__(kBlock) k_complete_ct(SymPtrs sp, int nl, LimbMap map, PrngKey mask, u64 id0, const PrimeConst* pc, int logn,
+                                                        u32 bad0, u32* bad) {
+    const u32 y = blockIdx.y, z = blockIdx.z;
+    const bool a_row = y >= (u32)nl;
+    const u32 l = a_row ? y - (u32)nl : y;
+    const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const int prime = map.prime((int)l);
+    const u32 q = pc[prime].q;
+    u32* p = sp.ct[z] + ((size_t)y << logn) + k;
+    if (a_row) {
+        *p = (u32)(chacha_u64(mask, kSymStreamA | (id0 + ((u64)z << 16)), ((u64)prime << logn) + k) % q);
+    } else {
+        if (__any(*p >= q) && (threadIdx.x & 63) == 0) atomicMin(bad, bad0 + z * (u32)nl + l);
+    }
+}
 
 inline dim3 ew_grid(int logn, int rows) { return dim3((1u << logn) / kBlock, rows); }
 
@@ -2231,6 +2277,23 @@ void launch_keygen_combine(hipStream_t st, const DevTables& T, u32* b, const u32
                            const u32* gadget, int nl, LimbMap map, int glo, int ghi) {
     prof_launch(KID_ELEMENTWISE, EW_BYTES(4.0 * nl), k_keygen_combine, ew_grid(T.logn, nl), dim3(kBlock), 0, st, b, a, s, e, sp, gadget, nl, map, glo, ghi, T.pc,
                        T.logn);
+}
+void launch_sample_sym(hipStream_t st, const DevTables& T, u32* io, int nl, int nm, const PrngKey& key, u64 id0) {
+    if (nm < 1 || nm > kEncMax || nl < 1) throw std::runtime_error("launch_sample_sym: member or limb count out of range");
+    prof_launch(KID_SAMPLE, words(2.0 * nm * nl * (1u << T.logn)), k_sample_sym, dim3((1u << T.logn) / kBlock, (unsigned)nm), dim3(kBlock), 0, st, io, nl,
+                key, id0, T.pc, T.logn);
+}
+void launch_sym_encrypt(hipStream_t st, const DevTables& T, const SymPtrs& sp, int nm, const u32* em, const u32* s, int nl, LimbMap map,
+                        const PrngKey& mask, u64 id0) {
+    if (nm < 1 || nm > kSymMembers || nl < 1 || nl > 65535) throw std::runtime_error("launch_sym_encrypt: member or limb count out of range");
+    prof_launch(KID_SAMPLE, words(4.0 * nm * nl * (1u << T.logn)), k_sym_encrypt, dim3((1u << T.logn) / kBlock, (unsigned)nl, (unsigned)nm), dim3(kBlock), 0,
+                st, sp, em, s, nl, map, mask, id0, T.pc, T.logn);
+}
+void launch_complete_ct(hipStream_t st, const DevTables& T, const SymPtrs& sp, int nm, int nl, LimbMap map, const PrngKey& mask, u64 id0,
+                        u32 bad0, u32* bad) {
+    if (nm < 1 || nm > kSymMembers || nl < 1 || 2 * nl > 65535) throw std::runtime_error("launch_complete_ct: member or limb count out of range");
+    prof_launch(KID_SAMPLE, words(2.0 * nm * nl * (1u << T.logn)), k_complete_ct, dim3((1u << T.logn) / kBlock, 2u * nl, (unsigned)nm), dim3(kBlock), 0, st,
+                sp, nl, map, mask, id0, T.pc, T.logn, bad0, bad);
 }
 
 void launch_decode16(hipStream_t st, const DevTables& T, const u32* x, const int kd[2], const CrtConsts cc[2], const Slot16& sl,

@@ -163,6 +163,15 @@ class EngineContext:
     def encrypt(self, data: np.ndarray):
         return self.engine.encrypt(data, self.public_key)
 
+    def encrypt_seeded(self, data: np.ndarray, level: int | None = None):
+        """seeded symmetric encryption: the ciphertext travels as its b rows plus .seed_id
+        (state_encoder.dump_ct_seeded); needs the secret and a mask key"""
+        return self.engine.encrypt_seeded(data, level)
+
+    def encrypt_seeded_many(self, datas, level: int | None = None):
+        """encrypt_seeded of several messages in one set of launches; consecutive seed ids in call order"""
+        return self.engine.encrypt_seeded_many(datas, level)
+
     def decrypt(self, ct) -> np.ndarray:
         return self.engine.decrypt(ct, self.secret_key)
 

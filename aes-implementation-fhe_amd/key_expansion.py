@@ -183,6 +183,23 @@ class EncryptedRoundKeys:
         """round keys the client expanded and encrypted itself (StateEncoder.encode of each, in `layout`)"""
         return cls(pairs, layout)
 
+    def dump_seeded(self, ctx):
+        """the 22 ciphertexts as dump_ct_seeded records, in (round, hi / lo) order: every pair must
+        be a seeded fresh encryption (StateEncoder.encode_many(..., seeded=True)); half of the dump_ct bytes"""
+        from state_encoder import dump_ct_seeded
+        return [dump_ct_seeded(ctx, c) for pr in self.pairs for c in pr]
+
+    @classmethod
+    def load_seeded(cls, ctx, records, layout) -> "EncryptedRoundKeys":
+        """the inverse of dump_seeded on the receiving context: records with consecutive seed ids (one
+        encrypt_seeded_many call made them) go through one batched import"""
+        from state_encoder import load_cts_seeded
+        records = list(records)
+        if len(records) != 22:
+            raise ValueError("AES-128 takes 11 round keys: 22 seeded records, (hi, lo) per round")
+        cts = load_cts_seeded(ctx, records)
+        return cls([(cts[2 * r], cts[2 * r + 1]) for r in range(11)], layout)
+
     def __len__(self) -> int:
         return len(self.pairs)
 

@@ -60,6 +60,7 @@ EXPORTED = [
     "aesfhe_ensure_key", "aesfhe_check",
     "aesfhe_set_mask_key", "aesfhe_has_mask_key", "aesfhe_mask_key", "aesfhe_export_pk_half", "aesfhe_export_ksk_half",
     "aesfhe_import_pk_half", "aesfhe_import_ksk_half",
+    "aesfhe_encrypt_sym", "aesfhe_export_half", "aesfhe_import_half",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -209,6 +210,9 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_export_ksk_half"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
     sig["aesfhe_import_pk_half"] = [vp, _up, ctypes.c_uint64]
     sig["aesfhe_import_ksk_half"] = [vp, ctypes.c_uint64, c_int, _up, ctypes.c_uint64]
+    sig["aesfhe_encrypt_sym"] = [vp, _dp, _dp, c_int, c_int, _Hp, ctypes.POINTER(ctypes.c_uint64)]
+    sig["aesfhe_export_half"] = [vp, _H, _up, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    sig["aesfhe_import_half"] = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, c_int, ctypes.c_uint64, c_int, _Hp]
     for name in EXPORTED:
         fn = getattr(L, name)
         fn.restype = (ctypes.c_char_p if name == "aesfhe_last_error"
@@ -276,9 +280,14 @@ class _Handle:
 class Ciphertext(_Handle):
     """Device-resident RNS-CKKS ciphertext (opaque handle).  `layout`: the AES slot layout
     (state_encoder.SlotLayout) the state encoder tagged it with, unset for plain ciphertexts; `value_dtype`: the word
-    type a value ciphertext's slots hold (state_encoder.tag_value_dtype)"""
+    type a value ciphertext's slots hold (state_encoder.tag_value_dtype); `seed_id`: the 56-bit id of a seeded fresh
+    ciphertext (Engine.encrypt_seeded, DESIGN.md §3.27: counter << 16 | nonce16), None for every other ciphertext"""
 
-    __slots__ = ("layout", "value_dtype")
+    __slots__ = ("layout", "value_dtype", "_seed_id")
+
+    @property
+    def seed_id(self) -> Optional[int]:
+        return getattr(self, "_seed_id", None)
 
     @property
     def level(self) -> int:
@@ -605,6 +614,56 @@ class Engine:
         self._ensure_keys()
         re, im = _complex_vec(data, self.slot_count)
         return self._new(self._lib.aesfhe_encrypt, re, im, self.slot_count)
+
+    # seeded symmetric encryption: the client's upload path, b rows plus an id on the wire
+    def encrypt_seeded_many(self, datas, level: int | None = None) -> List[Ciphertext]:
+        """B messages encrypted under the secret with the `a` halves drawn under the mask key (aesfhe_encrypt_sym):
+        one sampling launch, one NTT and one fused kernel for all of them, at `level` (None: the fresh level) with
+        no extra limb and no rescale.  Each result carries .seed_id, consecutive counters in call order"""
+        self._ensure_keys()
+        vecs = [_complex_vec(d, self.slot_count) for d in datas]
+        if not vecs:
+            raise ValueError("encrypt_seeded_many: no messages")
+        re = np.ascontiguousarray(np.stack([v[0] for v in vecs]))
+        im = np.ascontiguousarray(np.stack([v[1] for v in vecs]))
+        out = (ctypes.c_uint64 * len(vecs))()
+        id0 = ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_encrypt_sym(self._ctx.ptr, re, im, len(vecs), -1 if level is None else int(level), out,
+                                                     ctypes.byref(id0)))
+        cts = [Ciphertext(self._ctx, h) for h in out]
+        for j, c in enumerate(cts):
+            c._seed_id = int(id0.value) + (j << 16)
+        return cts
+
+    def encrypt_seeded(self, data, level: int | None = None) -> Ciphertext:
+        """one seeded symmetric encryption (encrypt_seeded_many of one message)"""
+        return self.encrypt_seeded_many([data], level)[0]
+
+    def export_half(self, ct: Ciphertext):
+        """(b rows [limbs][N], id) of a seeded fresh ciphertext (aesfhe_export_half); any other ciphertext is
+        refused: "not a seeded ciphertext\""""
+        h = getattr(ct, "handle", None)
+        if not isinstance(h, int):  # a deferred result: an operation's output carries no id
+            raise RuntimeError("export_half: not a seeded ciphertext")
+        out = np.empty((self.nl(ct.level), self.n), np.uint32)
+        sid = ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_export_half(self._ctx.ptr, h, out, out.size, ctypes.byref(sid)))
+        return out, int(sid.value)
+
+    def import_half_many(self, b_rows, level: int, seed_id0: int) -> List[Ciphertext]:
+        """B ciphertexts from their b rows (B arrays [limbs][N], or one [B][limbs][N]) and the consecutive ids
+        seed_id0 + (j << 16) (aesfhe_import_half): one launch checks the rows and regenerates every a row under the
+        mask key.  The arrays are read where they lie: records that arrived separately are not gathered first"""
+        rows = [np.ascontiguousarray(r, np.uint32) for r in b_rows]
+        if not rows or any(r.ndim != 2 or r.shape != rows[0].shape for r in rows):
+            raise ValueError("import_half_many: b rows are B arrays [limbs][N] of one shape")
+        ptrs = (ctypes.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
+        out = (ctypes.c_uint64 * len(rows))()
+        self._ctx.check(self._lib.aesfhe_import_half(self._ctx.ptr, ptrs, rows[0].size, int(level), int(seed_id0), len(rows), out))
+        return [Ciphertext(self._ctx, h) for h in out]
+
+    def import_half(self, b_rows, level: int, seed_id: int) -> Ciphertext:
+        return self.import_half_many([b_rows], level, seed_id)[0]
 
     def decrypt(self, ct: Ciphertext, sk=None) -> np.ndarray:
         re = np.zeros(self.slot_count)

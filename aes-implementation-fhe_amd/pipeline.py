@@ -228,17 +228,21 @@ class AESPipeline:
             #                      the GF multipliers need 6 levels, MixColumns renormalises after them)
         return self._renorm_pair(*self._sub_apply(ct, defer_conj=True, lut=lut), level=level)
 
-    def _encode_key(self, key_bytes: np.ndarray):
+    def _encode_key(self, key_bytes: np.ndarray, seeded: bool = False):
         key_bytes = np.asarray(key_bytes, dtype=np.uint8)
         if self.states > 1 and key_bytes.shape == (16,):
             key_bytes = np.broadcast_to(key_bytes, (self.states, 16))
         assert key_bytes.shape == ((16,) if self.states == 1 else (self.states, 16))
-        return self.encoder.encode(key_bytes)
+        return self.encoder.encode(key_bytes, seeded=True) if seeded else self.encoder.encode(key_bytes)
 
-    def encrypt_key(self, master: np.ndarray):
+    def encrypt_key(self, master: np.ndarray, seeded: bool = False):
         """client side: the (hi, lo) encryption of a (16,) AES-128 key, or of a (states, 16) array with one key
-        per state (a (16,) key is shared by all states, as _encode_key broadcasts it) -- expand_key's input"""
-        return self._encode_key(master)
+        per state (a (16,) key is shared by all states, as _encode_key broadcasts it) -- expand_key's input.
+        seeded=True: one batched seeded symmetric encryption, the pair then crosses the wire as
+        halves (state_encoder.dump_ct_seeded / load_ct_seeded)"""
+        if seeded and self.pairs > 1:
+            raise ValueError("encrypt_key: seeded encryption of multi-pair batches (pairs > 1) is not supported")
+        return self._encode_key(master, seeded)
 
     def expand_key(self, key_hi, key_lo, debug: Dict[str, Any] | None = None) -> EncryptedRoundKeys:
         """the 11 round keys of an encrypted AES-128 key, derived homomorphically (key_expansion.KeyExpansion,

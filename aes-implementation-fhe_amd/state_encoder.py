@@ -132,6 +132,59 @@ def load_ct(ctx, array, level: int, layout=None, check: bool = True):
     return ct
 
 
+def _layout_tag(ct):
+    lay = getattr(ct, "layout", None)
+    return None if lay is None else dict(sc=int(lay.sc), states=int(lay.states), periodic=bool(lay.periodic),
+                                         byte_order=str(getattr(lay, "byte_order", "plain")))
+
+
+def _layout_of(ctx, layout, who: str):
+    if layout is None:
+        return None
+    if int(layout["sc"]) != ctx.engine.slot_count:
+        raise ValueError(f"{who}: a layout of {layout['sc']} slots into a context of {ctx.engine.slot_count}")
+    lay = SlotLayout(int(layout["sc"]), int(layout["states"]), bool(layout["periodic"]))
+    lay.byte_order = str(layout.get("byte_order", "plain"))
+    return lay
+
+
+def dump_ct_seeded(ctx, ct):
+    """(b_rows, level, layout, seed_id) of a seeded fresh ciphertext (ctx.encrypt_seeded): half of
+    dump_ct's bytes, the a rows being a public function of seed_id and the context's mask key.  Any other ciphertext
+    (an operation's result, a public-key encryption) is refused by the engine: "not a seeded ciphertext\""""
+    b, sid = ctx.engine.export_half(ct)
+    return b, int(ct.level), _layout_tag(ct), sid
+
+
+def load_ct_seeded(ctx, b_rows, level: int, seed_id: int, layout=None):
+    """the ciphertext dump_ct_seeded wrote, completed on `ctx`'s device (any context holding the sender's mask key, an
+    evaluation-only one included): the b rows are checked as load_ct(check=True) checks them, the a rows regenerated"""
+    return load_cts_seeded(ctx, [(b_rows, level, layout, seed_id)])[0]
+
+
+def load_cts_seeded(ctx, records):
+    """load_ct_seeded of several dump_ct_seeded records; runs of one level and consecutive seed ids (the members of
+    one encrypt_seeded_many call, in order) go through one batched import each"""
+    records = list(records)
+    lays = [_layout_of(ctx, r[2], "load_ct_seeded") for r in records]
+    for r in records:
+        if np.asarray(r[0]).ndim != 2:
+            raise ValueError("load_ct_seeded: b rows are [limbs][N]")
+    out, i = [], 0
+    while i < len(records):
+        j = i + 1
+        while (j < len(records) and int(records[j][1]) == int(records[i][1])
+               and int(records[j][3]) == int(records[i][3]) + ((j - i) << 16)
+               and np.asarray(records[j][0]).shape == np.asarray(records[i][0]).shape):
+            j += 1
+        out += ctx.engine.import_half_many([r[0] for r in records[i:j]], int(records[i][1]), int(records[i][3]))
+        i = j
+    for ct, lay in zip(out, lays):
+        if lay is not None:
+            tag_layout(lay, ct)
+    return out
+
+
 def check_layout(layout: SlotLayout, *cts) -> None:
     """raise if a ciphertext was tagged with another slot layout (a pair made by an encoder with
     the reference layout decrypts to wrong bytes under the periodic one, and vice versa);
@@ -285,11 +338,35 @@ class StateEncoder:
             raise ValueError(f"expected a {(self.pairs,) + one} uint8 state array, got {state.shape}")
         return list(state)
 
-    def encode(self, state: np.ndarray) -> Tuple[Any, Any]:
+    def encode(self, state: np.ndarray, seeded: bool = False) -> Tuple[Any, Any]:
+        """seeded=True: the pair is made by one batched seeded symmetric encryption
+        (ctx.encrypt_seeded_many) and travels through dump_ct_seeded as b rows plus ids; pairs > 1 is refused, a
+        stack being an operation's result"""
+        if seeded:
+            if self.pairs > 1:
+                raise ValueError("encode: seeded encryption of multi-pair batches (pairs > 1) is not supported")
+            if getattr(self.ctx, "encrypt_seeded_many", None) is None:
+                raise ValueError("encode: seeded encryption needs a context with encrypt_seeded_many (engine_context.EngineContext)")
+            st = self._as_batch(self._pair_states(state)[0])
+            return tag_layout(self.layout, *self.ctx.encrypt_seeded_many([self._pack(st >> 4), self._pack(st & 0x0F)]))
         if self.pairs > 1:
             his, los = zip(*[self._encode1(s) for s in self._pair_states(state)])
             return tag_layout(self.layout, self.ctx.stack(his), self.ctx.stack(los))
         return self._encode1(self._pair_states(state)[0])
+
+    def encode_many(self, states, seeded: bool = False):
+        """[(hi, lo)] of several states; seeded=True: ONE batched seeded encryption for all of them (the 22
+        ciphertexts of 11 round keys), consecutive seed ids in (state, hi / lo) order"""
+        if not seeded:
+            return [self.encode(s) for s in states]
+        if self.pairs > 1:
+            raise ValueError("encode_many: seeded encryption of multi-pair batches (pairs > 1) is not supported")
+        vecs = []
+        for s in states:
+            st = self._as_batch(self._pair_states(s)[0])
+            vecs += [self._pack(st >> 4), self._pack(st & 0x0F)]
+        cts = tag_layout(self.layout, *self.ctx.encrypt_seeded_many(vecs))
+        return [(cts[2 * i], cts[2 * i + 1]) for i in range(len(cts) // 2)]
 
     def _encode1(self, state):
         st = self._as_batch(state)

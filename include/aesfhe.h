@@ -100,6 +100,28 @@ int aesfhe_export_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, uint32_t
  * (digit * nkey + row) and stores nothing. */
 int aesfhe_import_pk_half(aesfhe_ctx* ctx, const uint32_t* data, uint64_t words);
 int aesfhe_import_ksk_half(aesfhe_ctx* ctx, uint64_t galois, int level, const uint32_t* data, uint64_t words);
+/* Seeded symmetric encryption, the upload path of the same protocol: c = (e + m - a s, a) at `level`
+ * (-1: the fresh level; 0..fresh otherwise) and that level's scale, on exactly its limbs, with no rescale: an ordinary
+ * two-polynomial ciphertext, fresher than aesfhe_encrypt's.  `a` is the PRF under the mask key at a 56-bit id
+ * (counter << 16) | (encryption nonce & 0xffff), so the ciphertext travels as its `b` rows plus the id.  The counter is
+ * the context's own: it starts at 0, advances by `count` per call and is never shared with aesfhe_encrypt's.
+ * re, im: `count` messages of slot_count doubles each (im null: real); out: `count` handles, member j's id is the first
+ * one's + (j << 16); *id0 (nullable): the first one's.  Refused with a message: without a mask key (an `a` drawn under the context key cannot be
+ * published), on an evaluation-only context (no secret key), for a level out of range, for count outside 1..16384 and
+ * when the counter would reach 2^40. */
+int aesfhe_encrypt_sym(aesfhe_ctx* ctx, const double* re, const double* im, int count, int level, aesfhe_handle* out, uint64_t* id0);
+/* The `b` rows [limbs][N] of a handle aesfhe_encrypt_sym returned, and its id; `words` is the size of `out`, half the
+ * ciphertext's.  Any other handle is refused ("not a seeded ciphertext"): handles are values, so the result of an
+ * operation on a seeded ciphertext, an import and a public-key encryption carry no id. */
+int aesfhe_export_half(aesfhe_ctx* ctx, aesfhe_handle handle, uint32_t* out, uint64_t words, uint64_t* id);
+/* `count` ciphertexts at `level` from their `b` rows (rows[j]: [limbs][N], `words` words each, wherever each arrived: no
+ * gathering copy) and the consecutive ids id0 + (j << 16),
+ * on any context that holds the exporter's mask key, an evaluation-only one included: each ciphertext is allocated, its
+ * `b` rows are copied into place and one kernel launch (per 32 members) checks them and writes every `a` row; an
+ * aesfhe_export of the handle then equals the exporter's word for word.  Refused without a mask key, for a wrong word
+ * count, a level out of range, count outside 1..16384 and an id whose counter part would reach 2^40; a residue not
+ * below its modulus names member and row and stores nothing. */
+int aesfhe_import_half(aesfhe_ctx* ctx, const uint32_t* const* rows, uint64_t words, int level, uint64_t id0, int count, aesfhe_handle* out);
 /* Encryption randomness (v, e0, e1 of every encryption, the renorms' re-encryptions included)
  * is drawn under the context key with `nonce` folded into key words 6-7; key material is not
  * affected.  Processes sharing one context key (the ranks of a multi-GPU job) must
