@@ -5354,6 +5354,97 @@ public:
         }
         return out;
     }
+    // Result pack: T <= 32 single ciphertexts, each `period`-periodic (the caller's assertion, as
+    // renorm_periodic's), as ONE level-0 ciphertext z = sum_j X^(j k') ct_j, k' = N / (2 period G), G the smallest
+    // power of two >= T: a G period-periodic message (the monomial pair packing of mono_pack applied log2 G times, in
+    // bit-reversed member order: G = 2 is mono_pack(a, b), G = 4 of [a, c, b, d] is mono_pack of the two pairs'
+    // packs).  Exact: no key switch, no level, the members' own noise.  Every member goes to canonical form and
+    // exactly to level 0 (mono_pack's normalize + level_down), the drops of members at one level batched
+    // (convert_many), then one k_pack_periodic launch reads them through their pointers.  A handle of 0: an absent
+    // member (zero).  Every argument is checked before the first launch; a failure further down releases what was made.
+    // A member in two-polynomial form touches no switching key (normalize relinearises one that still owes it)
+    Ct pack_periodic(int T, const aesfhe_handle* members, int period) {
+        if (T < 1 || T > kPackMembers || !members) throw std::runtime_error("pack_periodic: the member count must lie in 1..32");
+        int G = 1;
+        while (G < T) G *= 2;
+        if (period < 1 || (period & (period - 1))) throw std::runtime_error("pack_periodic: the period must be a power of two >= 1");
+        if ((i64)G * period > slot_count())
+            throw std::runtime_error("pack_periodic: group size x period exceeds the slot count (G = " + std::to_string(G) + ", period " +
+                                     std::to_string(period) + ", " + std::to_string(slot_count()) + " slots)");
+        int present = 0;
+        for (int j = 0; j < T; ++j) {
+            if (!members[j]) continue;
+            const Ct& c = ct(members[j]);
+            if (c.nb != 1) throw std::runtime_error("pack_periodic: members must be single ciphertexts (member " + std::to_string(j) + " is a stack)");
+            if (vis_npoly(c) != 2) throw std::runtime_error("pack_periodic: 2-polynomial ciphertexts expected");
+            ++present;
+        }
+        if (!present) throw std::runtime_error("pack_periodic: every member is absent");
+        const int n = hp_.n, nl0 = hp_.nl(0), kp = n / (2 * period * G);
+        Ct z[kPackMembers];
+        std::vector<Ct> owned;
+        owned.reserve(2 * kPackMembers);
+        try {
+            for (int j = 0; j < T; ++j) {
+                if (!members[j]) continue;
+                const Ct& c = canon(members[j]);
+                z[j] = normalize(c);
+                if (z[j].data != c.data) owned.push_back(z[j]);
+            }
+            std::vector<bool> done(T, false);
+            for (int j = 0; j < T; ++j) {
+                if (!members[j] || done[j] || z[j].level == 0) continue;
+                std::vector<int> grp;  // the members at this level, up to kMaxMembers: one batched drop
+                for (int i = j; i < T && (int)grp.size() < kMaxMembers; ++i)
+                    if (members[i] && !done[i] && z[i].level == z[j].level) grp.push_back(i), done[i] = true;
+                std::vector<const Ct*> srcs;
+                for (int i : grp) srcs.push_back(&z[i]);
+                Ct st;
+                if (grp.size() > 1 && convert_many(srcs, 0, 0, st)) {
+                    owned.push_back(st);
+                    const size_t per = st.words / grp.size();
+                    for (size_t m = 0; m < grp.size(); ++m) {
+                        Ct v = st;
+                        v.data = st.data + m * per, v.words = per, v.npoly = 2, v.nb = 1;
+                        z[grp[m]] = v;
+                    }
+                    continue;
+                }
+                for (int i : grp) {
+                    Ct d = level_down(z[i], 0);
+                    owned.push_back(d);
+                    z[i] = d;
+                }
+            }
+            PackPtrs pp;
+            for (int j = 0; j < T; ++j)
+                if (members[j]) pp.ct[j] = z[j].data;
+            Ct out = alloc_ct(0, 2);
+            owned.push_back(out);
+            const u32* m = G > 1 ? monomial(kp) : nullptr;
+            launch_pack_periodic(S(), T_, out.data, pp, G, m, G > 1 ? monomial_shoup(kp) : nullptr, nl0, qmap());
+            owned.pop_back();
+            for (const Ct& c : owned) release(c);  // stream-ordered: the launches that read them are queued
+            return out;
+        } catch (...) {
+            for (const Ct& c : owned) release(c);
+            throw;
+        }
+    }
+    // the Shoup companions floor(M 2^32 / q_l) of monomial(e) on the level-0 limbs, [nl(0)][N]
+    std::map<int, u32*> mono_shoup_;
+    const u32* monomial_shoup(int e) {
+        auto it = mono_shoup_.find(e);
+        if (it != mono_shoup_.end()) return it->second;
+        const int n = hp_.n, nl0 = hp_.nl(0);
+        std::vector<u32> h((size_t)nl0 * n);
+        HIP_OK(hipMemcpy(h.data(), monomial(e), h.size() * sizeof(u32), hipMemcpyDeviceToHost));
+        for (int t = 0; t < nl0; ++t)
+            for (int i = 0; i < n; ++i) h[(size_t)t * n + i] = shoup_pre(h[(size_t)t * n + i], hp_.mod[t]);
+        u32* d = dev_alloc(h.size());
+        HIP_OK(hipMemcpy(d, h.data(), h.size() * sizeof(u32), hipMemcpyHostToDevice));
+        return mono_shoup_[e] = d;
+    }
     // NTT form of the monomial X^e (X^N = -1, e in [0, 2N)) on every Q limb: the product by
     // it is exact (coefficients shifted, the wrapped ones negated; no level, no noise)
     std::map<int, u32*> mono_;
@@ -6833,6 +6924,12 @@ int aesfhe_debug_mono_split(aesfhe_ctx* ctx, aesfhe_handle m, int period, aesfhe
     e.mono_split(e.canon(m), period, hi, lo);
     *out_hi = e.put_ct(hi);
     *out_lo = e.put_ct(lo);
+    API_END
+}
+int aesfhe_pack_periodic(aesfhe_ctx* ctx, int n_members, const aesfhe_handle* members, int period, aesfhe_handle* out) {
+    API_BEGIN Engine& e = *ctx->eng;
+    if (!out) throw std::runtime_error("pack_periodic: no output handle");
+    *out = e.put_ct(e.pack_periodic(n_members, members, period));
     API_END
 }
 int aesfhe_debug_lin_group(aesfhe_ctx* ctx, aesfhe_handle c, int which, aesfhe_handle* out) {

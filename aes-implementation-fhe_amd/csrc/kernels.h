@@ -477,6 +477,16 @@ void launch_sym_encrypt(hipStream_t st, const DevTables& T, const SymPtrs& sp, i
 // written as launch_sym_encrypt wrote it
 void launch_complete_ct(hipStream_t st, const DevTables& T, const SymPtrs& sp, int nm, int nl, LimbMap map, const PrngKey& mask, u64 id0,
                         u32 bad0, u32* bad);
+// --- result pack ---------------------------------------------------------
+// out[p][l] = sum_{j < g} M^j[l] (.) pp.ct[j][p][l] mod q_l over the 2 nl rows of level-0-shaped ciphertexts [2][nl][N]:
+// g a power of two <= kPackMembers, a null pp.ct[j] an absent member (0; none at j >= g), mono / mono_p the NTT form of
+// the monomial and its Shoup companions ([>= nl][N] each; unread when g = 1).  Members below q give an output below q
+constexpr int kPackMembers = 32;
+struct PackPtrs {
+    const u32* ct[kPackMembers] = {};
+};
+void launch_pack_periodic(hipStream_t st, const DevTables& T, u32* out, const PackPtrs& pp, int g, const u32* mono, const u32* mono_p, int nl,
+                          LimbMap map);
 // raw decryption of up to 2 channels on their first kd[c] limbs: x[c][t] = c0 + c1 s (+ c2 s^2),
 // x: [2][4][N]; channel c reads ct[c] (npoly[c] polys of nlc[c] limbs); s, s2: NTT rows of s, s^2
 struct DecRaw {

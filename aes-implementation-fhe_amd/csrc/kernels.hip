@@ -853,6 +853,29 @@ __global__ void __launch_bounds__(kBlock) k_complete_ct(SymPtrs sp, int nl, Limb
         if (__any(*p >= q) && (threadIdx.x & 63) == 0) atomicMin(bad, bad0 + z * (u32)nl + l);
     }
 }
+// result pack: out[p][l] = sum_{j < G} M^j[l] (.) in_j[p][l] mod q_l by Horner's rule from the last
+// member down, M the NTT form of one monomial with its Shoup companion Mp -- one table for every G.  Grid
+// (N / kBlock, 2 nl), one residue per member per thread: G independent coalesced 4-byte loads issued before the chain
+// (a null pointer: an absent member, 0), the two table words, one store.  Every step ends below q (shoup_mul and
+// add_mod both reduce), so canonical members give a canonical output.  No LDS; the members sit in G registers
+template <int G>
+__global__ void __launch_bounds__(kBlock) k_pack_periodic(u32* out, PackPtrs pp, const u32* mono, const u32* mono_p, int nl, LimbMap map,
+                                                          const PrimeConst* pc, int logn) {
+    const int row = blockIdx.y, limb = row >= nl ? row - nl : row;
+    const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const size_t idx = ((size_t)row << logn) + k, midx = ((size_t)limb << logn) + k;
+    const u32 q = pc[map.prime(limb)].q;
+    u32 x[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) x[j] = pp.ct[j] ? pp.ct[j][idx] : 0u;
+    u32 acc = x[G - 1];
+    if (G > 1) {
+        const u32 w = mono[midx], wp = mono_p[midx];
+#pragma unroll
+        for (int j = G - 2; j >= 0; --j) acc = add_mod(x[j], shoup_mul(acc, w, wp, q), q);
+    }
+    out[idx] = acc;
+}
 
 inline dim3 ew_grid(int logn, int rows) { return dim3((1u << logn) / kBlock, rows); }
 
@@ -2294,6 +2317,28 @@ void launch_complete_ct(hipStream_t st, const DevTables& T, const SymPtrs& sp, i
     if (nm < 1 || nm > kSymMembers || nl < 1 || 2 * nl > 65535) throw std::runtime_error("launch_complete_ct: member or limb count out of range");
     prof_launch(KID_SAMPLE, words(2.0 * nm * nl * (1u << T.logn)), k_complete_ct, dim3((1u << T.logn) / kBlock, 2u * nl, (unsigned)nm), dim3(kBlock), 0, st,
                 sp, nl, map, mask, id0, T.pc, T.logn, bad0, bad);
+}
+void launch_pack_periodic(hipStream_t st, const DevTables& T, u32* out, const PackPtrs& pp, int g, const u32* mono, const u32* mono_p, int nl,
+                          LimbMap map) {
+    if (g < 1 || g > kPackMembers || (g & (g - 1)) || nl < 1 || 2 * nl > 65535)
+        throw std::runtime_error("launch_pack_periodic: the member count must be a power of two up to 32");
+    if (!out || (g > 1 && (!mono || !mono_p))) throw std::runtime_error("launch_pack_periodic: missing output or monomial table");
+    int present = 0;
+    for (int j = 0; j < kPackMembers; ++j) {
+        if (j >= g && pp.ct[j]) throw std::runtime_error("launch_pack_periodic: a member beyond the group");
+        present += pp.ct[j] != nullptr;
+    }
+    // every present member's rows and the output's once, the two table rows of a limb once per polynomial
+    const double bytes = words((2.0 * (present + 1) + (g > 1 ? 4.0 : 0.0)) * nl * (1u << T.logn));
+    const dim3 grid = ew_grid(T.logn, 2 * nl);
+    switch (g) {
+#define PACK_G(G) \
+    case G: \
+        prof_launch(KID_ELEMENTWISE, bytes, k_pack_periodic<G>, grid, dim3(kBlock), 0, st, out, pp, mono, mono_p, nl, map, T.pc, T.logn); \
+        break;
+        PACK_G(1) PACK_G(2) PACK_G(4) PACK_G(8) PACK_G(16) PACK_G(32)
+#undef PACK_G
+    }
 }
 
 void launch_decode16(hipStream_t st, const DevTables& T, const u32* x, const int kd[2], const CrtConsts cc[2], const Slot16& sl,

@@ -236,6 +236,11 @@ class EngineContext:
     def unstack(self, ct):
         return self.engine.unstack(ct)
 
+    def pack_periodic(self, cts, period: int):
+        """1..32 single `period`-periodic ciphertexts (None: absent) as one level-0 ciphertext, .pack = (G, period)
+        (include/aesfhe.h aesfhe_pack_periodic); result_pack.pack_results picks the period"""
+        return self.engine.pack_periodic(cts, period)
+
     def rotate_multi(self, items):
         """[rotate(ct, s) for ct, s in items] -- different ciphertexts, different steps -- as one
         heterogeneous batched key switch (include/aesfhe.h aesfhe_galois_multi)"""

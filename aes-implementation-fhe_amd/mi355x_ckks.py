@@ -61,6 +61,7 @@ EXPORTED = [
     "aesfhe_set_mask_key", "aesfhe_has_mask_key", "aesfhe_mask_key", "aesfhe_export_pk_half", "aesfhe_export_ksk_half",
     "aesfhe_import_pk_half", "aesfhe_import_ksk_half",
     "aesfhe_encrypt_sym", "aesfhe_export_half", "aesfhe_import_half",
+    "aesfhe_pack_periodic",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -213,6 +214,7 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_encrypt_sym"] = [vp, _dp, _dp, c_int, c_int, _Hp, ctypes.POINTER(ctypes.c_uint64)]
     sig["aesfhe_export_half"] = [vp, _H, _up, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     sig["aesfhe_import_half"] = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, c_int, ctypes.c_uint64, c_int, _Hp]
+    sig["aesfhe_pack_periodic"] = [vp, c_int, _Hp, c_int, _Hp]
     for name in EXPORTED:
         fn = getattr(L, name)
         fn.restype = (ctypes.c_char_p if name == "aesfhe_last_error"
@@ -281,9 +283,10 @@ class Ciphertext(_Handle):
     """Device-resident RNS-CKKS ciphertext (opaque handle).  `layout`: the AES slot layout
     (state_encoder.SlotLayout) the state encoder tagged it with, unset for plain ciphertexts; `value_dtype`: the word
     type a value ciphertext's slots hold (state_encoder.tag_value_dtype); `seed_id`: the 56-bit id of a seeded fresh
-    ciphertext (Engine.encrypt_seeded, DESIGN.md §3.27: counter << 16 | nonce16), None for every other ciphertext"""
+    ciphertext (Engine.encrypt_seeded, DESIGN.md §3.27: counter << 16 | nonce16), None for every other ciphertext;
+    `pack`: (G, period) of a result pack (Engine.pack_periodic), unset for every other ciphertext"""
 
-    __slots__ = ("layout", "value_dtype", "_seed_id")
+    __slots__ = ("layout", "value_dtype", "_seed_id", "pack")
 
     @property
     def seed_id(self) -> Optional[int]:
@@ -1048,6 +1051,23 @@ class Engine:
 
     def debug_mono_pack(self, a, b, period: int):
         return self._new(self._lib.aesfhe_debug_mono_pack, a.handle, b.handle, int(period))
+
+    def pack_periodic(self, cts, period: int) -> Ciphertext:
+        """1..32 single `period`-periodic ciphertexts (None: an absent member) as ONE level-0 ciphertext
+        z = sum_j X^(j N / (2 period G)) ct_j, G the smallest power of two >= len(cts) (aesfhe_pack_periodic,
+        DESIGN.md §3.28): exact, no key, no level.  The result carries .pack = (G, period); whoever holds the secret
+        decrypts it once and splits the members in the clear (result_pack.split_slots)"""
+        cts = list(cts)
+        H = ctypes.c_uint64 * max(len(cts), 1)
+        out = ctypes.c_uint64()
+        self._ctx.check(self._lib.aesfhe_pack_periodic(self._ctx.ptr, len(cts), H(*[0 if c is None else c.handle for c in cts]), int(period),
+                                                       ctypes.byref(out)))
+        z = Ciphertext(self._ctx, out.value)
+        g = 1
+        while g < len(cts):
+            g *= 2
+        z.pack = (g, int(period))
+        return z
 
     def debug_mono_split(self, m, period: int):
         x, y = ctypes.c_uint64(), ctypes.c_uint64()

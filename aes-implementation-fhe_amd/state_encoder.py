@@ -138,6 +138,13 @@ def _layout_tag(ct):
                                          byte_order=str(getattr(lay, "byte_order", "plain")))
 
 
+def _layout_of_tag(layout) -> SlotLayout:
+    """the SlotLayout a _layout_tag dict describes"""
+    lay = SlotLayout(int(layout["sc"]), int(layout["states"]), bool(layout["periodic"]))
+    lay.byte_order = str(layout.get("byte_order", "plain"))
+    return lay
+
+
 def _layout_of(ctx, layout, who: str):
     if layout is None:
         return None
@@ -588,7 +595,67 @@ class StateEncoder:
             return tag_layout(self.layout, self.ctx.stack(cts))[0]
         return tag_layout(self.layout, self.ctx.encrypt(self._packed_slots(self._as_batch(self._pair_states(state)[0]))))[0]
 
-    def decode_packed(self, ct) -> np.ndarray:
+    def decode_slots(self, hi_slots: np.ndarray, lo_slots: np.ndarray) -> np.ndarray:
+        """_decode1 on slot vectors: the (hi, lo) Zeta16 slot vectors of one pair (decrypted elsewhere, a result pack's
+        members above all) -> the (states, 16) bytes in the caller's byte order, (16,) for one state"""
+        if self.pairs > 1:
+            raise ValueError("decode_slots: multi-pair batches (pairs > 1) are not supported")
+        hs, ls = np.asarray(hi_slots), np.asarray(lo_slots)
+        if hs.shape != (self.sc,) or ls.shape != (self.sc,):
+            raise ValueError(f"expected two slot vectors of {self.sc} entries, got shapes {hs.shape} and {ls.shape}")
+        hi = ZetaEncoder.from_zeta(self._take(hs), 16)
+        lo = ZetaEncoder.from_zeta(self._take(ls), 16)
+        out = self._order(((hi << 4) | lo).astype(np.uint8))
+        return out[0] if self.states == 1 else out
+
+    def _check_pack_meta(self, meta) -> None:
+        """a result pack's meta against this encoder: one pair per ciphertext, the periodic layout, the same slot count,
+        and every member's layout tag this encoder's own"""
+        if self.pairs > 1:
+            raise ValueError("decode_packed: result packs of multi-pair batches (pairs > 1) are not supported")
+        if not self.layout.periodic:
+            raise ValueError("decode_packed: a result pack holds periodic results; this encoder uses the reference layout")
+        if int(meta["slots"]) != self.sc:
+            raise ValueError(f"decode_packed: the pack was made for {meta['slots']} slots, this encoder has {self.sc}")
+        if int(meta["period"]) % self.layout.period:
+            raise ValueError(f"decode_packed: the pack's period {meta['period']} is no multiple of this layout's {self.layout.period}")
+        for tag in meta["layouts"]:
+            if tag is not None and not self.layout.same(_layout_of_tag(tag)):
+                raise ValueError(f"decode_packed: a member holds states in the {_describe(_layout_of_tag(tag))} slot layout, "
+                                 f"this encoder uses the {_describe(self.layout)} one")
+
+    def _decode_members(self, slots, meta) -> list:
+        """decode_packed(array, meta) after the decryption: `slots` are the members' slot vectors in member order
+        (result_pack.unpack_results / split_slots)"""
+        tags = list(meta["value_dtypes"])
+        present = list(meta.get("present", [True] * len(tags)))
+        if len(slots) != len(tags):
+            raise ValueError(f"decode_packed: {len(slots)} slot vectors for {len(tags)} members")
+        if not all(present):
+            raise ValueError("decode_packed: the pack has an absent member; decode its members with decode_slots / values_from_slots")
+        out, j = [], 0
+        while j < len(tags):
+            if tags[j] is not None:
+                out.append(self.values_from_slots(slots[j], tags[j]))
+                j += 1
+                continue
+            if j + 1 >= len(tags) or tags[j + 1] is not None:
+                raise ValueError(f"decode_packed: an odd run of untagged members ends at member {j}: (hi, lo) pairs come two at a time")
+            out.append(self.decode_slots(slots[j], slots[j + 1]))
+            j += 2
+        return out
+
+    def decode_packed(self, ct, meta=None):
+        """decode_packed(ct): the packed hi | lo form of DESIGN.md §4c, as ever.  decode_packed(array, meta): a RESULT
+        PACK (result_pack.dump_results) -- the client's one decryption, then one entry per result in
+        member order: a member tagged as a value ciphertext is its float array (values_from_slots under its tag),
+        consecutive untagged members are taken two at a time as (hi, lo) and give the pair's bytes (one entry per
+        pair); an odd run of untagged members, an absent member, pairs > 1, the reference layout and a meta of
+        another slot count or layout raise ValueError"""
+        if meta is not None:
+            from result_pack import unpack_results
+            self._check_pack_meta(meta)
+            return self._decode_members(unpack_results(self.ctx, ct, meta), meta)
         check_layout(self.layout, ct)
         if self.pairs > 1:
             return np.stack([self._decode_packed1(c) for c in self.ctx.unstack(ct)])

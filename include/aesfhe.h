@@ -549,6 +549,20 @@ int aesfhe_debug_sparse_group_plain(aesfhe_ctx* ctx, int period, int which, int 
                                     double* out_re, double* out_im, int* info3);
 int aesfhe_debug_mono_pack(aesfhe_ctx* ctx, aesfhe_handle a, aesfhe_handle b, int period, aesfhe_handle* out);
 int aesfhe_debug_mono_split(aesfhe_ctx* ctx, aesfhe_handle m, int period, aesfhe_handle* out_hi, aesfhe_handle* out_lo);
+/* Result pack: 1 <= n_members <= 32 single ciphertexts (no stacks), at any levels and in any
+ * deferred state, as ONE ordinary level-0, two-polynomial, NTT-form ciphertext at scale delta_0:
+ *   z = sum_j X^(j k') ct_j,  k' = N / (2 period G),  G = the smallest power of two >= n_members,
+ * a G period-periodic message.  Each member must be `period`-periodic (slot j == slot j mod period): the caller's
+ * assertion, exactly as for aesfhe_renorm_periodic -- a member that is not is packed wrongly, without an error.  A
+ * handle of 0 is an absent member and contributes zero.  period: a power of two >= 1 with G period <= slot_count.
+ * Every member is brought to canonical form and dropped exactly to level 0; the pack is a sum of monomial products,
+ * so it takes no key switch and no level and adds only the members' own noise, and it runs on an evaluation-only
+ * context.  Convention: two members give aesfhe_debug_mono_pack's words; four members [a, c, b, d] give those of
+ * mono_pack(mono_pack(a, b, period), mono_pack(c, d, period), 2 period).  The holder of the secret decrypts once and
+ * separates the members in the clear (result_pack.split_slots).  Refused (status -1, aesfhe_last_error; nothing is
+ * kept, the context stays usable): n_members outside 1..32, every member absent, a stack as a member, a period that
+ * is no power of two, G period > slot_count. */
+int aesfhe_pack_periodic(aesfhe_ctx* ctx, int n_members, const aesfhe_handle* members, int period, aesfhe_handle* out);
 /* ephemeral sparse secret (NTT form, all limbs) */
 int aesfhe_export_sparse(aesfhe_ctx* ctx, uint32_t* out);
 int aesfhe_debug_lin_group(aesfhe_ctx* ctx, aesfhe_handle ct, int which, aesfhe_handle* out);
