@@ -617,33 +617,123 @@ public:
     int d2s_np() const { return std::min(kD2sP, hp_.n_p); }
     size_t ksk_words(u64 g) const {
         if (g == tag_d2s()) return (size_t)2 * (kD2sQ + d2s_np()) * hp_.n;
+        if (is_tag_ring(g)) return (size_t)kRingDigits * 2 * (kD2sQ + ring_key_np(ring_of(g))) * hp_.n;
         return (size_t)hp_.dnum * 2 * (hp_.n_ks + hp_.n_p) * hp_.n;
     }
-    double d2s_modulus_bits() const {
+    // log2 of Q0 * (the first np special primes)
+    double q0p_modulus_bits(int np) const {
         double b = 0;
         for (int t = 0; t < kD2sQ; ++t) b += std::log2((double)hp_.mod[t]);
-        for (int k = 0; k < d2s_np(); ++k) b += std::log2((double)hp_.mod[hp_.p_off() + k]);
+        for (int k = 0; k < np; ++k) b += std::log2((double)hp_.mod[hp_.p_off() + k]);
         return b;
+    }
+    double d2s_modulus_bits() const { return q0p_modulus_bits(d2s_np()); }
+    // a key over Q0 * P', P' = the first np special primes, [2][kD2sQ + np][N]: (-a t + e + (P' mod q_t) s, a) on the
+    // q0, q1 rows, switching the dense secret s to the target secret t ([primes][N], NTT form)
+    // nd digits of kD2sQ / nd limbs, [nd][2][kD2sQ + np][N]: digit j carries the gadget on its own rows (PRNG
+    // sub-stream j, as a full key's digits)
+    const u32* ksk_q0p(u64 g, int np, const u32* target, int nd = 1) {
+        const int n = hp_.n, ne = kD2sQ + np, da = kD2sQ / nd;
+        const u32* gad = q0p(np, nd).d + q0p(np, nd).gad;
+        void* raw = nullptr;
+        HIP_OK(hipMalloc(&raw, ksk_words(g) * sizeof(u32)));
+        u32* key = (u32*)raw;
+        const LimbMap em = extmap(kD2sQ);  // rows 0, 1: q0, q1; then the first special primes
+        u32* e = tmp(ne);
+        for (int j = 0; j < nd; ++j) {
+            u32* b = key + (size_t)j * 2 * ne * n;
+            u32* a = b + (size_t)ne * n;
+            launch_sample_uniform(S(), T_, a, ne, em, akey(), stream_id(4, g, j));
+            launch_sample_small(S(), T_, e, ne, em, pkey(), stream_id(5, g, j), 1);
+            ntt(e, ne, ne, em);
+            launch_keygen_combine(S(), T_, b, a, target, e, d_s_, gad, ne, em, j * da, j * da + da);
+        }
+        untmp(e, ne);
+        ksk_[g] = key;
+        HIP_OK(hipStreamSynchronize(S()));
+        return key;
     }
     const u32* ksk_d2s() {
         const u64 g = tag_d2s();
         if (eval_only_) key_missing(g, -1);
-        const int n = hp_.n, ne = kD2sQ + d2s_np();
+        return ksk_q0p(g, d2s_np(), sparse_secret());  // b = -a s_sp + e + (P' mod q_t) s
+    }
+    // ------------------------------------------------------------------ ring switch keys
+    // For a ring degree R = N / k the subring secret s_R is a uniform ternary polynomial of Z[X^k] (dense in the subring:
+    // R coefficients, not the bootstrap's sparse secret), drawn from the context key under PRNG stream 14 and cached per
+    // R; the ring key switches s to s_R over Q0 * P', built as the dense -> sparse key is (ksk_q0p) but with q0 and q1 a
+    // digit each, so that a P' of ONE special prime carries the gadget noise.  That key is an RLWE
+    // sample of the big ring whose secret lies in Z[X^k]: it splits into k independent samples of dimension R, so the
+    // modulus bound that matters is R's (the HE standard's table, ternary secret, 128 bits classical)
+    static constexpr int kRingDigits = 2;  // q0 and q1 a digit each: the gadget term carries q_max / P', not Q0 / P'
+    u64 tag_ring(int ring) const { return 12ull * hp_.n + (u64)ring; }
+    bool is_tag_ring(u64 t) const {
+        const u64 lo = 12ull * hp_.n;
+        return t > lo && t < lo + (u64)hp_.n && ((t - lo) & (t - lo - 1)) == 0;
+    }
+    int ring_of(u64 t) const { return (int)(t - 12ull * hp_.n); }
+    static int ring_max_log_modulus(int ring) {
+        static const int tab[][2] = {{1024, 27}, {2048, 54}, {4096, 109}, {8192, 218}, {16384, 438}, {32768, 881}, {65536, 1772}};
+        for (const auto& r : tab)
+            if (r[0] == ring) return r[1];
+        return 0;  // below 1024 (or no power of two): no modulus is admitted
+    }
+    // the largest special-prime count, 1..d2s_np(), whose Q0 * P' the bound for R admits; 0: not even one fits
+    int ring_np(int ring) const {
+        for (int c = d2s_np(); c >= 1; --c)
+            if (q0p_modulus_bits(c) <= (double)ring_max_log_modulus(ring)) return c;
+        return 0;
+    }
+    // the key's count: ring_np, or -- a ring the gate rejects, reachable with insecure_ok only -- the dense -> sparse key's
+    int ring_key_np(int ring) const { return ring_np(ring) ? ring_np(ring) : d2s_np(); }
+    void ring_check(const char* who, int ring) const {
+        if (ring < 1 || (ring & (ring - 1))) throw std::runtime_error(std::string(who) + ": the ring degree must be a power of two, got " + std::to_string(ring));
+        if (ring >= hp_.n) throw std::runtime_error(std::string(who) + ": the ring degree must be below N = " + std::to_string(hp_.n) + ", got " + std::to_string(ring));
+    }
+    void ring_gate(const char* who, int ring, bool insecure_ok) const {
+        if (insecure_ok || ring_np(ring)) return;
+        throw std::runtime_error(std::string(who) + ": ring too small for this modulus (R = " + std::to_string(ring) + " admits log2(Q0 P') <= " +
+                                 std::to_string(ring_max_log_modulus(ring)) + " at 128 bits, one special prime gives " +
+                                 std::to_string(q0p_modulus_bits(1)) + "; insecure_ok lifts this for test rings)");
+    }
+    std::map<int, std::vector<int>> ring_secret_;
+    const std::vector<int>& ring_secret_coeffs(int ring) {
+        need_secret("ring_secret");
+        ring_check("ring_secret", ring);
+        auto it = ring_secret_.find(ring);
+        if (it != ring_secret_.end()) return it->second;
+        std::vector<int> s(ring);
+        for (int j = 0; j < ring; ++j) s[j] = (int)(chacha_u64(pkey(), stream_id(14, (u64)ring, 0), (u64)j) % 3) - 1;
+        return ring_secret_[ring] = s;
+    }
+    const u32* ksk_ring(int ring, bool insecure_ok) {
+        ring_check("ring key", ring);
+        ring_gate("ring key", ring, insecure_ok);
+        const u64 g = tag_ring(ring);
+        auto it = ksk_.find(g);
+        if (it != ksk_.end()) return it->second;
+        if (eval_only_) key_missing(g, -1);
+        if (!d_s_) throw std::runtime_error("keys not generated");
+        // s_R on every prime, NTT form: read once by k_keygen_combine, freed when the key is made
+        const int n = hp_.n, nt = hp_.n_tot(), k = n / ring;
+        const std::vector<int>& s = ring_secret_coeffs(ring);
+        std::vector<u32> h((size_t)nt * n, 0u);
+        for (int t = 0; t < nt; ++t)
+            for (int j = 0; j < ring; ++j) h[(size_t)t * n + (size_t)j * k] = s[j] >= 0 ? (u32)s[j] : hp_.mod[t] - 1;
         void* raw = nullptr;
-        HIP_OK(hipMalloc(&raw, ksk_words(g) * sizeof(u32)));
-        u32* b = (u32*)raw;
-        u32* a = b + (size_t)ne * n;
-        const LimbMap em = extmap(kD2sQ);  // rows 0, 1: q0, q1; then the first special primes
-        u32* e = tmp(ne);
-        launch_sample_uniform(S(), T_, a, ne, em, akey(), stream_id(4, g, 0));
-        launch_sample_small(S(), T_, e, ne, em, pkey(), stream_id(5, g, 0), 1);
-        ntt(e, ne, ne, em);
-        // b = -a s_sp + e + (P' mod q_t) s on the q0, q1 rows
-        launch_keygen_combine(S(), T_, b, a, sparse_secret(), e, d_s_, d_d2s_ + d2s_off_.gad, ne, em, 0, kD2sQ);
-        untmp(e, ne);
-        ksk_[g] = b;
-        HIP_OK(hipStreamSynchronize(S()));
-        return b;
+        HIP_OK(hipMalloc(&raw, h.size() * sizeof(u32)));
+        const u32* key = nullptr;
+        try {
+            HIP_OK(hipMemcpy(raw, h.data(), h.size() * sizeof(u32), hipMemcpyHostToDevice));
+            ntt((u32*)raw, nt, nt, qmap());
+            key = ksk_q0p(g, ring_key_np(ring), (const u32*)raw, kRingDigits);  // synchronises
+        } catch (...) {
+            (void)hipStreamSynchronize(S());
+            (void)hipFree(raw);
+            throw;
+        }
+        HIP_OK(hipFree(raw));
+        return key;
     }
     const u32* ksk(u64 g) {
         auto it = ksk_.find(g);
@@ -651,6 +741,7 @@ public:
         if (eval_only_) key_missing(g, -1);
         if (!d_s_) throw std::runtime_error("keys not generated");
         if (g == tag_d2s()) return ksk_d2s();
+        if (is_tag_ring(g)) return ksk_ring(ring_of(g), false);  // a ring the gate rejects: aesfhe_ensure_ring_key's insecure_ok
         const int n = hp_.n, nks = hp_.n_ks, np = hp_.n_p, nkey = nks + np;
         void* raw = nullptr;
         HIP_OK(hipMalloc(&raw, ksk_words(g) * sizeof(u32)));
@@ -2729,48 +2820,56 @@ public:
     // c0' = add0 + ...; nb members at d + m ms / add0 + m ms
     // d: c1 of nb members (NTT form, the two base limbs q0, q1, member stride ms words);
     // returns the key-switched (c0', c1') over (q0, q1) with add0 (c0) added to c0'
-    Ct keyswitch_d2s(const u32* d, const u32* add0, int nb, size_t ms) {
-        const int n = hp_.n, nq = kD2sQ, np = d2s_np(), ne = nq + np, npl = 2 * nb;
-        if (npl > kMaxConvGroups || nb > kMaxKsBatch) throw std::runtime_error("keyswitch_d2s: batch too large");
+    // key, np, nd: the key over Q0 * P', its special-prime count and its digits -- the bootstrap's (ksk(tag_d2s()),
+    // d2s_np(), one digit q0 q1) or a ring key's (ksk_ring(R), ring_key_np(R), kRingDigits = 2: q0 and q1 a digit each,
+    // so that ONE special prime suffices; the ring switch); the constants are q0p(np, nd)'s
+    Ct keyswitch_d2s(const u32* d, const u32* add0, int nb, size_t ms, const u32* key, int np, int nd = 1) {
+        const int n = hp_.n, nq = kD2sQ, ne = nq + np, npl = 2 * nb;
+        if (npl > kMaxConvGroups || nb * nd > kMaxConvGroups || nb > kMaxKsBatch) throw std::runtime_error("keyswitch_d2s: batch too large");
         const LimbMap em = extmap(nq);
-        const u32* key = ksk(tag_d2s());
-        // ModUp Q0 -> P' (the own limbs q0, q1 are read from d by the key inner product)
+        const Q0PBasis& B = q0p(np, nd);
+        // limbs per digit: the key inner product reads a digit's own limbs from d.  One digit: both (the chain's alpha,
+        // as before); a digit per limb: 1
+        const int da = nq / nd, alpha = nd == 1 ? hp_.alpha : da;
+        // ModUp of every digit to the other limbs of Q0 * P' (the own limbs are read from d by the key inner product)
         const bool fz = fused_conv(true);
         u32* coef = tmp((size_t)nb * nq);
-        intt(coef, d, nb * nq, RowMap{nq, (int)(ms / n), nq, 0, 0}, qmap(), fz || conv_pre_ ? d_d2s_ + d2s_off_.up_qhinv : nullptr);
-        u32* ext = tmp((size_t)nb * ne);
+        intt(coef, d, nb * nq, RowMap{nq, (int)(ms / n), nq, 0, 0}, qmap(), fz || conv_pre_ ? B.d + B.up_qhinv : nullptr);
+        u32* ext = tmp((size_t)nb * nd * ne);
         ConvBatch up;
-        up.n = nb;
+        up.n = nb * nd;
         up.pre = conv_pre_;
-        for (int m = 0; m < nb; ++m) {
-            up.h[m] = nq, up.d0[m] = 0, up.skip0[m] = 0;
-            up.src[m] = coef + (size_t)m * nq * n;
-            up.dst[m] = ext + (size_t)m * ne * n;
-            up.tab[m] = d_d2s_ + d2s_off_.up_tab;      // [nq][ne] pairs: (Q0 / q_i) mod target
-            up.qhinv[m] = d_d2s_ + d2s_off_.up_qhinv;  // [nq] pairs: (Q0 / q_i)^-1 mod q_i
-            up.negq[m] = d_d2s_ + d2s_off_.up_negq;    // [ne]: -Q0 mod target
-        }
+        for (int m = 0; m < nb; ++m)
+            for (int j = 0; j < nd; ++j) {
+                const int gi = m * nd + j, lo = j * da;
+                up.h[gi] = da, up.d0[gi] = lo, up.skip0[gi] = lo;
+                up.src[gi] = coef + ((size_t)m * nq + lo) * n;
+                up.dst[gi] = ext + (size_t)gi * ne * n;
+                up.tab[gi] = B.d + B.up_tab + (size_t)j * 2 * da * ne;  // [da][ne] pairs: (digit / q_i) mod target
+                up.qhinv[gi] = B.d + B.up_qhinv + 2 * lo;               // [da] pairs: (digit / q_i)^-1 mod q_i
+                up.negq[gi] = B.d + B.up_negq + (size_t)j * ne;         // [ne]: -digit mod target
+            }
         RowMap xr = rows_dense(ne);
-        xr.skip_alpha = hp_.alpha, xr.skip_nl = nq, xr.skip_groups = 1;
+        xr.skip_alpha = alpha, xr.skip_nl = nq, xr.skip_groups = nd;
         if (fz) {
-            launch_ntt_fwd_conv(S(), T_, ext, up, nb * ne, xr, em);
-            cnt_[C_NTT_ROWS] += nb * ne;
+            launch_ntt_fwd_conv(S(), T_, ext, up, nb * nd * ne, xr, em);
+            cnt_[C_NTT_ROWS] += nb * nd * ne;
         } else {
             launch_base_convert(S(), T_, up, ne, em);
-            ntt(ext, ext, nb * ne, xr, em);
+            ntt(ext, ext, nb * nd * ne, xr, em);
         }
         untmp(coef, (size_t)nb * nq);
         u32* acc = tmp((size_t)npl * ne);
-        launch_key_inner(S(), T_, acc, ext, d, key, 1, ne, nq, hp_.alpha, ne, nq, em, 0, nb, (size_t)ne * n, ms, (size_t)2 * ne * n);
-        untmp(ext, (size_t)nb * ne);
+        launch_key_inner(S(), T_, acc, ext, d, key, nd, ne, nq, alpha, ne, nq, em, 0, nb, (size_t)nd * ne * n, ms, (size_t)2 * ne * n);
+        untmp(ext, (size_t)nb * nd * ne);
         // ModDown by P' onto (q0, q1), + add0 (its own tables; no k_bx_cols form)
         MdSpec s;
         s.who = "keyswitch_d2s", s.ne = ne, s.h = np, s.r0 = nq, s.lm = LimbMap{np, hp_.p_off(), 0};
         s.nt = nq, s.out_level = 0;
-        s.tab = d_d2s_ + d2s_off_.dn_tab;      // [np][nq] pairs: (P' / p_k) mod q_t
-        s.qhinv = d_d2s_ + d2s_off_.dn_qhinv;  // [np] pairs: (P' / p_k)^-1 mod p_k
-        s.negq = d_d2s_ + d2s_off_.dn_negq;    // [nq]: -P' mod q_t
-        s.pinv = d_d2s_ + d2s_off_.pinv, s.d0 = hp_.p_off();
+        s.tab = B.d + B.dn_tab;      // [np][nq] pairs: (P' / p_k) mod q_t
+        s.qhinv = B.d + B.dn_qhinv;  // [np] pairs: (P' / p_k)^-1 mod p_k
+        s.negq = B.d + B.dn_negq;    // [nq]: -P' mod q_t
+        s.pinv = B.d + B.pinv, s.d0 = hp_.p_off();
         s.add0 = add0, s.add_ms = ms;
         Ct o = run_moddown(s, acc, nb);
         untmp(acc, (size_t)npl * ne);
@@ -5431,6 +5530,70 @@ public:
             throw;
         }
     }
+    // Ring switch: one single ciphertext whose message lies in the subring Z[X^k], k = N / ring (the
+    // caller's assertion, as periodicity is pack_periodic's -- a result pack with 2 G period <= ring is such a message),
+    // brought to canonical two-polynomial form and to level 0 exactly as pack_periodic brings its members, switched to
+    // the subring secret s_R with the ring key over Q0 * P' (keyswitch_d2s), taken to coefficients and decimated:
+    // out[p][l][j] = the residue mod q_l of coefficient j k of c_p', [2][2][ring].  s_R has no coefficient off the
+    // multiples of k, so (c1' s_R)[j k] depends on c1'[i k] alone and the decimated pair decrypts under s_R in
+    // Z[X] / (X^ring + 1).  Every argument is checked before the first launch; the key comes next (an evaluation-only
+    // context without it: "evaluation key missing"); a failure further down releases what was made.
+    // The ModDown's finish is fused with the forward transform (run_moddown), so the coefficients are taken by one
+    // inverse transform of the four result rows, not from a coefficient-form ModDown
+    void ring_switch(aesfhe_handle h, int ring, bool insecure_ok, u32* out, u64 words) {
+        ring_check("ring_switch", ring);
+        if (!out) throw std::runtime_error("ring_switch: no output");
+        const int n = hp_.n, nq = kD2sQ;
+        if (words < (u64)2 * nq * ring)
+            throw std::runtime_error("ring_switch: output buffer too small (" + std::to_string(words) + " words, [2][2][ring] has " +
+                                     std::to_string((u64)2 * nq * ring) + ")");
+        if (hp_.nl(0) != nq) throw std::runtime_error("ring_switch: level 0 must hold the two base limbs");
+        ring_gate("ring_switch", ring, insecure_ok);
+        {
+            const Ct& c = ct(h);
+            if (c.nb != 1) throw std::runtime_error("ring_switch: a single ciphertext expected (the input is a stack)");
+            if (vis_npoly(c) != 2) throw std::runtime_error("ring_switch: 2-polynomial ciphertext expected");
+        }
+        const u32* key = ksk_ring(ring, insecure_ok);
+        const int np = ring_key_np(ring);
+        (void)q0p(np, kRingDigits);
+        std::vector<Ct> owned;
+        u32* dec = nullptr;
+        try {
+            const Ct& c = canon(h);
+            Ct z = normalize(c);
+            if (z.data != c.data) owned.push_back(z);
+            if (z.level != 0) {
+                Ct d = level_down(z, 0);
+                owned.push_back(d);
+                z = d;
+            }
+            Ct zn = ensure_ntt(z);
+            if (zn.data != z.data) owned.push_back(zn);
+            Ct sw = keyswitch_d2s(zn.data + (size_t)nq * n, zn.data, 1, (size_t)2 * nq * n, key, np, kRingDigits);
+            owned.push_back(sw);
+            intt(sw.data, 2 * nq, nq, qmap());
+            dec = tmp(2);  // 2 nq ring <= 2 N words
+            launch_ring_decimate(S(), T_, dec, sw.data, 2 * nq, ring);
+            HIP_OK(hipMemcpyAsync(out, dec, (size_t)2 * nq * ring * sizeof(u32), hipMemcpyDeviceToHost, S()));
+            HIP_OK(hipStreamSynchronize(S()));
+            untmp(dec, 2);
+            dec = nullptr;
+            for (const Ct& o : owned) release(o);
+        } catch (...) {
+            if (dec) untmp(dec, 2);
+            for (const Ct& o : owned) release(o);
+            throw;
+        }
+    }
+    // the key alone: generated on a keyed context (the client's warm-up before export_evaluation_keys), looked up on an
+    // evaluation-only one
+    void ensure_ring_key(int ring, bool insecure_ok) { (void)ksk_ring(ring, insecure_ok); }
+    void export_ring_secret(int ring, int32_t* out) {
+        if (!out) throw std::runtime_error("export_ring_secret: no output");
+        const std::vector<int>& s = ring_secret_coeffs(ring);
+        for (int j = 0; j < ring; ++j) out[j] = s[j];
+    }
     // the Shoup companions floor(M 2^32 / q_l) of monomial(e) on the level-0 limbs, [nl(0)][N]
     std::map<int, u32*> mono_shoup_;
     const u32* monomial_shoup(int e) {
@@ -5475,7 +5638,7 @@ public:
         launch_mul_const_half(S(), T_, z.data, z.data, const_half(r, r), z.npoly * nq, nq, qmap());
         if (stop_after == 1) return z;
         // 2. sparse-secret encapsulation: dense s -> sparse s_sp at modulus Q0
-        Ct sp = keyswitch_d2s(z.data + (size_t)nq * n, z.data, nb, (size_t)2 * nq * n);
+        Ct sp = keyswitch_d2s(z.data + (size_t)nq * n, z.data, nb, (size_t)2 * nq * n, ksk(tag_d2s()), d2s_np());
         release(z);
         if (stop_after == 2) return sp;
         // 3. ModRaise: centred CRT lift of both polynomials to every limb of the top level
@@ -5724,10 +5887,12 @@ public:
         if (level >= 0) {
             if (!reduced_level(level)) throw std::runtime_error("switching key: level " + std::to_string(level) + " is not a reduced level (low-P off, or the level has a full digit)");
             if (g == tag_d2s()) throw std::runtime_error("switching key: the dense -> sparse key has its own basis and no reduced-level form");
+            if (is_tag_ring(g)) throw std::runtime_error("switching key: a ring key has its own basis and no reduced-level form");
             em = extmap(hp_.nl(level));
             return 2 * hp_.nl(level) + 1;  // nl + np, np = nl + 1 (build_low_basis)
         }
         if (g == tag_d2s()) return em = extmap(kD2sQ), kD2sQ + d2s_np();
+        if (is_tag_ring(g)) return em = extmap(kD2sQ), kD2sQ + ring_key_np(ring_of(g));
         return em = extmap(hp_.n_ks), hp_.n_ks + hp_.n_p;
     }
     u64 ksk_words_at(u64 g, int level) const {
@@ -5763,7 +5928,7 @@ public:
         LimbMap em;
         const int rows = key_rows(g, level, em);
         if (level >= 0) return HalfGeom{1, rows, em, stream_id(10, g, level)};
-        return HalfGeom{g == tag_d2s() ? 1 : hp_.dnum, rows, em, stream_id(4, g, 0)};
+        return HalfGeom{g == tag_d2s() ? 1 : is_tag_ring(g) ? kRingDigits : hp_.dnum, rows, em, stream_id(4, g, 0)};
     }
     // the b rows of `key` to the host: one copy per digit (a digit's b rows are contiguous, digits 2 nkey rows apart)
     void export_half(const char* who, const u32* key, const HalfGeom& G, u32* out, u64 words) {
@@ -6179,71 +6344,89 @@ private:
         }
         d_mdr_ = dev_upload(mdr);
 
-        // dense -> sparse key switch over q0 * P' (ksk_d2s): [P' mod q0 pair][np pairs P'/p_k mod q0]
-        // [np pairs (P'/p_k)^-1 mod p_k][-P' mod q0][P'^-1 mod q0 pair]
-        {  // dense -> sparse key switch over Q0 * P' (keyswitch_d2s): offsets in d2s_off_
-            const int nq = kD2sQ, npd = d2s_np(), ne = nq + npd;
-            auto tq = [&](int x) { return x < nq ? q[x] : q[hp_.p_off() + x - nq]; };
-            std::vector<u32> t;
-            auto pair_ = [&](u32 v, u32 m) { t.push_back(v), t.push_back(shoup_pre(v, m)); };
-            d2s_off_.gad = t.size();  // [nq] pairs: P' mod q_t (the key's gadget)
-            for (int x = 0; x < nq; ++x) {
-                u32 v = 1;
-                for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
-                pair_(v, q[x]);
-            }
-            d2s_off_.up_tab = t.size();  // [nq][ne] pairs: (Q0 / q_i) mod target x
-            for (int i = 0; i < nq; ++i)
-                for (int x = 0; x < ne; ++x) {
-                    u32 v = 1;
-                    for (int k = 0; k < nq; ++k)
-                        if (k != i) v = mulm(v, q[k], tq(x));
-                    pair_(v, tq(x));
-                }
-            d2s_off_.up_qhinv = t.size();  // [nq] pairs: (Q0 / q_i)^-1 mod q_i
-            for (int i = 0; i < nq; ++i) {
-                u32 v = 1;
-                for (int k = 0; k < nq; ++k)
-                    if (k != i) v = mulm(v, q[k], q[i]);
-                pair_(hinvm(v, q[i]), q[i]);
-            }
-            d2s_off_.up_negq = t.size();  // [ne]: -Q0 mod target x
+        q0p(d2s_np());  // the dense -> sparse key switch's constants (keyswitch_d2s)
+    }
+
+    // Constants of a level-0 key switch over Q0 * P' (keyswitch_d2s), Q0 = q0 q1 and P' = the first npd special primes: the
+    // bootstrap's dense -> sparse switch (npd = d2s_np(), built with the tables) and the ring switch (npd = ring_np(R),
+    // DESIGN.md §3.29; built on first use).  One device array per npd, the offsets into it in words
+    struct Q0PBasis {
+        const u32* d = nullptr;
+        size_t gad = 0, up_tab = 0, up_qhinv = 0, up_negq = 0, dn_tab = 0, dn_qhinv = 0, dn_negq = 0, pinv = 0;
+    };
+    std::map<std::pair<int, int>, Q0PBasis> q0p_;
+    // nd digits of kD2sQ / nd limbs each: 1 (q0 q1 one digit) or 2 (a digit per limb); digit j's ModUp tables lie at
+    // up_tab + j 2 da ne, up_qhinv + 2 j da, up_negq + j ne (da limbs per digit)
+    const Q0PBasis& q0p(int npd, int nd = 1) {
+        auto it = q0p_.find({npd, nd});
+        if (it != q0p_.end()) return it->second;
+        if (npd < 1 || npd > d2s_np()) throw std::runtime_error("q0p: special-prime count out of range");
+        if (nd < 1 || kD2sQ % nd) throw std::runtime_error("q0p: the digits must divide the base limbs");
+        const auto& q = hp_.mod;
+        auto mulm = [](u64 a, u64 b, u32 m) { return (u32)(a % m * (b % m) % m); };
+        Q0PBasis B;
+        const int nq = kD2sQ, ne = nq + npd, da = nq / nd;
+        auto tq = [&](int x) { return x < nq ? q[x] : q[hp_.p_off() + x - nq]; };
+        std::vector<u32> t;
+        auto pair_ = [&](u32 v, u32 m) { t.push_back(v), t.push_back(shoup_pre(v, m)); };
+        B.gad = t.size();  // [nq] pairs: P' mod q_t (the key's gadget)
+        for (int x = 0; x < nq; ++x) {
+            u32 v = 1;
+            for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
+            pair_(v, q[x]);
+        }
+        B.up_tab = t.size();  // [nd][da][ne] pairs: (digit / q_i) mod target x
+        for (int i = 0; i < nq; ++i)
             for (int x = 0; x < ne; ++x) {
                 u32 v = 1;
-                for (int k = 0; k < nq; ++k) v = mulm(v, q[k], tq(x));
+                for (int k = i / da * da; k < i / da * da + da; ++k)
+                    if (k != i) v = mulm(v, q[k], tq(x));
+                pair_(v, tq(x));
+            }
+        B.up_qhinv = t.size();  // [nq] pairs: (digit / q_i)^-1 mod q_i
+        for (int i = 0; i < nq; ++i) {
+            u32 v = 1;
+            for (int k = i / da * da; k < i / da * da + da; ++k)
+                if (k != i) v = mulm(v, q[k], q[i]);
+            pair_(hinvm(v, q[i]), q[i]);
+        }
+        B.up_negq = t.size();  // [nd][ne]: -digit mod target x
+        for (int j = 0; j < nd; ++j)
+            for (int x = 0; x < ne; ++x) {
+                u32 v = 1;
+                for (int k = j * da; k < j * da + da; ++k) v = mulm(v, q[k], tq(x));
                 t.push_back(v ? tq(x) - v : 0);
             }
-            d2s_off_.dn_tab = t.size();  // [np][nq] pairs: (P' / p_k) mod q_t
-            for (int k = 0; k < npd; ++k)
-                for (int x = 0; x < nq; ++x) {
-                    u32 v = 1;
-                    for (int m2 = 0; m2 < npd; ++m2)
-                        if (m2 != k) v = mulm(v, q[hp_.p_off() + m2], q[x]);
-                    pair_(v, q[x]);
-                }
-            d2s_off_.dn_qhinv = t.size();  // [np] pairs: (P' / p_k)^-1 mod p_k
-            for (int k = 0; k < npd; ++k) {
-                const u32 pk = q[hp_.p_off() + k];
+        B.dn_tab = t.size();  // [np][nq] pairs: (P' / p_k) mod q_t
+        for (int k = 0; k < npd; ++k)
+            for (int x = 0; x < nq; ++x) {
                 u32 v = 1;
                 for (int m2 = 0; m2 < npd; ++m2)
-                    if (m2 != k) v = mulm(v, q[hp_.p_off() + m2], pk);
-                pair_(hinvm(v, pk), pk);
+                    if (m2 != k) v = mulm(v, q[hp_.p_off() + m2], q[x]);
+                pair_(v, q[x]);
             }
-            d2s_off_.dn_negq = t.size();  // [nq]: -P' mod q_t
-            for (int x = 0; x < nq; ++x) {
-                u32 v = 1;
-                for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
-                t.push_back(v ? q[x] - v : 0);
-            }
-            d2s_off_.pinv = t.size();  // [nq] pairs: P'^-1 mod q_t
-            for (int x = 0; x < nq; ++x) {
-                u32 v = 1;
-                for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
-                pair_(hinvm(v, q[x]), q[x]);
-            }
-            d_d2s_ = dev_upload(t);
+        B.dn_qhinv = t.size();  // [np] pairs: (P' / p_k)^-1 mod p_k
+        for (int k = 0; k < npd; ++k) {
+            const u32 pk = q[hp_.p_off() + k];
+            u32 v = 1;
+            for (int m2 = 0; m2 < npd; ++m2)
+                if (m2 != k) v = mulm(v, q[hp_.p_off() + m2], pk);
+            pair_(hinvm(v, pk), pk);
         }
-
+        B.dn_negq = t.size();  // [nq]: -P' mod q_t
+        for (int x = 0; x < nq; ++x) {
+            u32 v = 1;
+            for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
+            t.push_back(v ? q[x] - v : 0);
+        }
+        B.pinv = t.size();  // [nq] pairs: P'^-1 mod q_t
+        for (int x = 0; x < nq; ++x) {
+            u32 v = 1;
+            for (int k = 0; k < npd; ++k) v = mulm(v, q[hp_.p_off() + k], q[x]);
+            pair_(hinvm(v, q[x]), q[x]);
+        }
+        B.d = dev_upload(t);
+        return q0p_[{npd, nd}] = B;
     }
 
     HostParams hp_;
@@ -6283,8 +6466,6 @@ private:
     u32* d_moddown_phinv_ = nullptr;
     std::vector<size_t> moddown_off_;
     u32* d_mdr_ = nullptr;       // ModDown fused with the rescale, per level (see build_tables)
-    u32* d_d2s_ = nullptr;       // dense -> sparse key switch constants over Q0 * P' (see build_tables)
-    struct { size_t gad, up_tab, up_qhinv, up_negq, dn_tab, dn_qhinv, dn_negq, pinv; } d2s_off_{};
     std::vector<size_t> mdr_off_;
     bool batch_ops_ = std::getenv("AESFHE_BATCH_OPS") == nullptr || std::getenv("AESFHE_BATCH_OPS")[0] != '0';
     bool stack_evalmod_ = std::getenv("AESFHE_STACK_EVALMOD") == nullptr || std::getenv("AESFHE_STACK_EVALMOD")[0] != '0';
@@ -6930,6 +7111,18 @@ int aesfhe_pack_periodic(aesfhe_ctx* ctx, int n_members, const aesfhe_handle* me
     API_BEGIN Engine& e = *ctx->eng;
     if (!out) throw std::runtime_error("pack_periodic: no output handle");
     *out = e.put_ct(e.pack_periodic(n_members, members, period));
+    API_END
+}
+int aesfhe_ring_switch(aesfhe_ctx* ctx, aesfhe_handle c, int ring, int insecure_ok, uint32_t* out, uint64_t words) {
+    API_BEGIN ctx->eng->ring_switch(c, ring, insecure_ok != 0, out, words);
+    API_END
+}
+int aesfhe_ensure_ring_key(aesfhe_ctx* ctx, int ring, int insecure_ok) {
+    API_BEGIN ctx->eng->ensure_ring_key(ring, insecure_ok != 0);
+    API_END
+}
+int aesfhe_export_ring_secret(aesfhe_ctx* ctx, int ring, int32_t* out) {
+    API_BEGIN ctx->eng->export_ring_secret(ring, out);
     API_END
 }
 int aesfhe_debug_lin_group(aesfhe_ctx* ctx, aesfhe_handle c, int which, aesfhe_handle* out) {

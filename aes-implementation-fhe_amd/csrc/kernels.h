@@ -487,6 +487,10 @@ struct PackPtrs {
 };
 void launch_pack_periodic(hipStream_t st, const DevTables& T, u32* out, const PackPtrs& pp, int g, const u32* mono, const u32* mono_p, int nl,
                           LimbMap map);
+// --- ring switch ---------------------------------------------------------
+// out[r][j] = coef[r][j (N / ring)] for r < rows, j < ring: coef [rows][N] in coefficient form and natural order (the
+// inverse transform's output), out [rows][ring]; ring a power of two below N.  Moves rows x ring words each way
+void launch_ring_decimate(hipStream_t st, const DevTables& T, u32* out, const u32* coef, int rows, int ring);
 // raw decryption of up to 2 channels on their first kd[c] limbs: x[c][t] = c0 + c1 s (+ c2 s^2),
 // x: [2][4][N]; channel c reads ct[c] (npoly[c] polys of nlc[c] limbs); s, s2: NTT rows of s, s^2
 struct DecRaw {

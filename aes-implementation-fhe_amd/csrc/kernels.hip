@@ -876,6 +876,16 @@ __global__ void __launch_bounds__(kBlock) k_pack_periodic(u32* out, PackPtrs pp,
     }
     out[idx] = acc;
 }
+// ring switch: out[row][j] = coef[row][j << logk] over the `rows` coefficient-form rows of a ciphertext
+// (natural coefficient order, as the inverse transform leaves them), j < ring = N >> logk.  Grid (ceil(ring / kBlock),
+// rows); the guard covers a ring below one block.  Strided 4-byte reads, coalesced stores: rows x ring words each way
+__global__ void __launch_bounds__(kBlock) k_ring_decimate(u32* out, const u32* coef, int logk, int logn) {
+    const u32 ring = 1u << (logn - logk);
+    const u32 j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= ring) return;
+    const size_t row = blockIdx.y;
+    out[row * ring + j] = coef[(row << logn) + ((size_t)j << logk)];
+}
 
 inline dim3 ew_grid(int logn, int rows) { return dim3((1u << logn) / kBlock, rows); }
 
@@ -2339,6 +2349,15 @@ void launch_pack_periodic(hipStream_t st, const DevTables& T, u32* out, const Pa
         PACK_G(1) PACK_G(2) PACK_G(4) PACK_G(8) PACK_G(16) PACK_G(32)
 #undef PACK_G
     }
+}
+void launch_ring_decimate(hipStream_t st, const DevTables& T, u32* out, const u32* coef, int rows, int ring) {
+    int logr = 0;
+    while ((1 << logr) < ring) ++logr;
+    if (ring < 1 || (1 << logr) != ring || logr >= T.logn || rows < 1 || rows > 65535)
+        throw std::runtime_error("launch_ring_decimate: the ring must be a power of two below N");
+    if (!out || !coef) throw std::runtime_error("launch_ring_decimate: missing buffer");
+    prof_launch(KID_ELEMENTWISE, words(2.0 * rows * ring), k_ring_decimate, dim3((ring + kBlock - 1) / kBlock, (unsigned)rows), dim3(kBlock), 0, st, out,
+                coef, T.logn - logr, T.logn);
 }
 
 void launch_decode16(hipStream_t st, const DevTables& T, const u32* x, const int kd[2], const CrtConsts cc[2], const Slot16& sl,

@@ -241,6 +241,21 @@ class EngineContext:
         (include/aesfhe.h aesfhe_pack_periodic); result_pack.pack_results picks the period"""
         return self.engine.pack_periodic(cts, period)
 
+    # ring-switched result packs (DESIGN.md §3.29)
+    def ring_switch(self, ct, ring: int, insecure_ok: bool = False) -> np.ndarray:
+        """a single ciphertext whose message lies in Z[X^(N / ring)] as the (2, 2, ring) uint32 array of its ring-switched,
+        decimated form (include/aesfhe.h aesfhe_ring_switch); runs on an evaluation-only context that holds the ring key"""
+        return self.engine.ring_switch(ct, ring, insecure_ok)
+
+    def ensure_ring_key(self, ring: int, insecure_ok: bool = False):
+        """the client's warm-up: generate the ring key so that the next export_evaluation_keys carries it.  insecure_ok
+        lifts the 128-bit gate ("ring too small for this modulus") and exists for small test rings only"""
+        self.engine.ensure_ring_key(ring, insecure_ok)
+
+    def ring_secret(self, ring: int) -> np.ndarray:
+        """s_R: the `ring` ternary coefficients of the subring secret; "no secret key" on an evaluation-only context"""
+        return self.engine.ring_secret(ring)
+
     def rotate_multi(self, items):
         """[rotate(ct, s) for ct, s in items] -- different ciphertexts, different steps -- as one
         heterogeneous batched key switch (include/aesfhe.h aesfhe_galois_multi)"""

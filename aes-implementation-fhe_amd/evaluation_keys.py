@@ -191,8 +191,9 @@ def validate_compressed_header(h: dict) -> None:
 
 
 class CompressedEvaluationKeys:
-    """EvaluationKeys' interface over the b halves: `pk` is [n_q][N], a key [dnum][nkey][N] (full) or [nkey][N] (the
-    dense -> sparse key, a reduced level's key), each half the words of its EvaluationKeys counterpart; the header
+    """EvaluationKeys' interface over the b halves: `pk` is [n_q][N], a key [dnum][nkey][N] (full), [nkey][N] (the
+    dense -> sparse key, a reduced level's key) or [2][nkey][N] (a ring key, tag 12 N + ring, DESIGN.md §3.29: the key
+    `EngineContext.ensure_ring_key` adds), each half the words of its EvaluationKeys counterpart; the header
     carries the public mask key the a halves are regenerated from.  Never the secret, nor the client's own key."""
 
     def __init__(self, header: dict, pk, keys):

@@ -62,6 +62,7 @@ EXPORTED = [
     "aesfhe_import_pk_half", "aesfhe_import_ksk_half",
     "aesfhe_encrypt_sym", "aesfhe_export_half", "aesfhe_import_half",
     "aesfhe_pack_periodic",
+    "aesfhe_ring_switch", "aesfhe_ensure_ring_key", "aesfhe_export_ring_secret",
 ]
 
 # largest log2(PQ) for 128-bit classical security with a ternary secret (HE standard)
@@ -215,6 +216,9 @@ def load_library(path: Optional[Path] = None):
     sig["aesfhe_export_half"] = [vp, _H, _up, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
     sig["aesfhe_import_half"] = [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, c_int, ctypes.c_uint64, c_int, _Hp]
     sig["aesfhe_pack_periodic"] = [vp, c_int, _Hp, c_int, _Hp]
+    sig["aesfhe_ring_switch"] = [vp, _H, c_int, c_int, _up, ctypes.c_uint64]
+    sig["aesfhe_ensure_ring_key"] = [vp, c_int, c_int]
+    sig["aesfhe_export_ring_secret"] = [vp, c_int, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")]
     for name in EXPORTED:
         fn = getattr(L, name)
         fn.restype = (ctypes.c_char_p if name == "aesfhe_last_error"
@@ -1068,6 +1072,35 @@ class Engine:
             g *= 2
         z.pack = (g, int(period))
         return z
+
+    # ring-switched result packs
+    def ring_key_tag(self, ring: int) -> int:
+        """the key tag of the ring key for ring degree `ring` (12 N + ring), as key_ids / export_key name it"""
+        return 12 * self.n + int(ring)
+
+    def ring_switch(self, ct: Ciphertext, ring: int, insecure_ok: bool = False) -> np.ndarray:
+        """one single ciphertext whose message lies in Z[X^(N / ring)] (a result pack with 2 G period <= ring), dropped
+        to level 0, key-switched to the subring secret and decimated (aesfhe_ring_switch): the (2, 2, ring) uint32
+        coefficient-form residues mod q0, q1 of (c0', c1'), which result_pack.ring_decrypt opens with ring_secret(ring).
+        A ring the 128-bit bound rejects raises "ring too small for this modulus" unless insecure_ok (test rings)"""
+        self._ensure_keys()
+        ring = int(ring)
+        out = np.zeros((2, 2, max(ring, 1)), np.uint32)
+        self._ctx.check(self._lib.aesfhe_ring_switch(self._ctx.ptr, ct.handle, ring, int(bool(insecure_ok)), out, out.size if ring >= 1 else 0))
+        return out
+
+    def ensure_ring_key(self, ring: int, insecure_ok: bool = False):
+        """make the ring key resident without running an operation (aesfhe_ensure_ring_key): generated on a keyed
+        engine -- the warm-up that puts it into the next export of the evaluation keys --, looked up otherwise"""
+        self._ensure_keys()
+        self._ctx.check(self._lib.aesfhe_ensure_ring_key(self._ctx.ptr, int(ring), int(bool(insecure_ok))))
+
+    def ring_secret(self, ring: int) -> np.ndarray:
+        """the `ring` ternary coefficients (int32) of the subring secret s_R (aesfhe_export_ring_secret); needs the secret"""
+        ring = int(ring)
+        out = np.zeros(max(ring, 1), np.int32)
+        self._ctx.check(self._lib.aesfhe_export_ring_secret(self._ctx.ptr, ring, out))
+        return out
 
     def debug_mono_split(self, m, period: int):
         x, y = ctypes.c_uint64(), ctypes.c_uint64()

@@ -651,7 +651,9 @@ class StateEncoder:
         member order: a member tagged as a value ciphertext is its float array (values_from_slots under its tag),
         consecutive untagged members are taken two at a time as (hi, lo) and give the pair's bytes (one entry per
         pair); an odd run of untagged members, an absent member, pairs > 1, the reference layout and a meta of
-        another slot count or layout raise ValueError"""
+        another slot count or layout raise ValueError.  A meta with "ring" (dump_results(..., ring=))
+        names a ring-switched pack: the (2, 2, ring) array is decrypted in the small ring, in numpy, under the subring
+        secret (unpack_results), and decoded the same way"""
         if meta is not None:
             from result_pack import unpack_results
             self._check_pack_meta(meta)

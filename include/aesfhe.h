@@ -563,6 +563,28 @@ int aesfhe_debug_mono_split(aesfhe_ctx* ctx, aesfhe_handle m, int period, aesfhe
  * kept, the context stays usable): n_members outside 1..32, every member absent, a stack as a member, a period that
  * is no power of two, G period > slot_count. */
 int aesfhe_pack_periodic(aesfhe_ctx* ctx, int n_members, const aesfhe_handle* members, int period, aesfhe_handle* out);
+/* Ring switch: ONE single ciphertext (no stack), at any level and in any deferred state, whose
+ * message lies in the subring Z[X^k], k = N / ring -- the caller's assertion, exactly as periodicity is for
+ * aesfhe_pack_periodic (a result pack with 2 G period <= ring is such a message); a message outside the subring is
+ * switched wrongly, without an error.  The ciphertext is brought to canonical two-polynomial form and to level 0 as
+ * aesfhe_pack_periodic brings its members, key-switched to the subring secret s_R (a uniform ternary polynomial of
+ * Z[X^k]) over Q0 P' and decimated: out is [2][2][ring] uint32, the COEFFICIENT-form residues mod q0 and q1, below
+ * their moduli, of (c0', c1') at coefficient indices 0, k, 2k, ..., which decrypt as c0' + c1' s_R in
+ * Z[X] / (X^ring + 1) at scale delta_0.  ring: a power of two below N.  Security gate: the ring key splits into k RLWE
+ * samples of dimension `ring` at modulus Q0 P' (the key has two digits, q0 and q1, so one special prime suffices;
+ * layout [2][2][2 + np][N], tag 12 N + ring), so P' is the largest prefix of the dense -> sparse key's special
+ * primes with log2(Q0 P') within the HE standard's bound for `ring` (ternary secret, 128 bits classical: 27 / 54 /
+ * 109 / 218 / 438 / 881 for 1024 .. 32768); a ring below 1024 or one that admits not even one special prime is
+ * refused with "ring too small for this modulus" unless insecure_ok != 0, which exists for small test rings only.
+ * Refused before the first launch (status -1, aesfhe_last_error; nothing is kept, the context stays usable): a ring
+ * that is no power of two or >= N, words < 4 ring, a stack as input, a ring the gate rejects.  A keyed context makes
+ * the ring key on first use; an evaluation-only context without it fails with "evaluation key missing".
+ * aesfhe_ensure_ring_key: the key alone, under the same gate (the client's warm-up before it exports its keys;
+ * aesfhe_ensure_key with the key's tag does the same without insecure_ok).  aesfhe_export_ring_secret: the `ring`
+ * ternary coefficients of s_R (its coefficients at 0, k, 2k, ...), keyed contexts only ("no secret key" otherwise). */
+int aesfhe_ring_switch(aesfhe_ctx* ctx, aesfhe_handle ct, int ring, int insecure_ok, uint32_t* out, uint64_t words);
+int aesfhe_ensure_ring_key(aesfhe_ctx* ctx, int ring, int insecure_ok);
+int aesfhe_export_ring_secret(aesfhe_ctx* ctx, int ring, int32_t* out);
 /* ephemeral sparse secret (NTT form, all limbs) */
 int aesfhe_export_sparse(aesfhe_ctx* ctx, uint32_t* out);
 int aesfhe_debug_lin_group(aesfhe_ctx* ctx, aesfhe_handle ct, int which, aesfhe_handle* out);
