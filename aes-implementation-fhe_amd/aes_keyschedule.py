@@ -2,7 +2,8 @@
 (REF/test/test_aes_pipeline_roundtrip.py:20-110).
 
 ``expand_aes128_key`` is the FIPS-197 AES-128 key schedule (11 round keys, 16 bytes each,
-column-first); ``load_all_coeffs`` returns the dict AESPipeline expects.
+column-first), ``expand_aes_key`` the same schedule for 16-, 24- and 32-byte keys (11 / 13 / 15 round keys);
+``load_all_coeffs`` returns the dict AESPipeline expects.
 """
 from __future__ import annotations
 
@@ -51,6 +52,26 @@ def expand_aes128_key(master: np.ndarray) -> List[np.ndarray]:
             t[0] ^= RCON[i // 4 - 1]
         words.append(words[i - 4] ^ t)
     return [np.concatenate(words[4 * r:4 * r + 4]).astype(np.uint8) for r in range(11)]
+
+
+def expand_aes_key(master: np.ndarray) -> List[np.ndarray]:
+    """FIPS-197 §5.2 for a 16-, 24- or 32-byte key (Nk = 4 / 6 / 8): the 11, 13 or 15 round keys, 16 bytes each,
+    column-first.  On 16 bytes it equals expand_aes128_key"""
+    master = np.asarray(master, dtype=np.uint8)
+    if master.ndim != 1 or master.shape[0] not in (16, 24, 32):
+        raise ValueError(f"an AES key is 16, 24 or 32 bytes, got shape {master.shape}")
+    nk = master.shape[0] // 4
+    nr = nk + 6
+    words = [master[4 * i:4 * i + 4].copy() for i in range(nk)]
+    for i in range(nk, 4 * (nr + 1)):
+        t = words[i - 1].copy()
+        if i % nk == 0:
+            t = SBOX[np.roll(t, -1)]
+            t[0] ^= RCON[i // nk - 1]
+        elif nk == 8 and i % nk == 4:
+            t = SBOX[t]
+        words.append(words[i - nk] ^ t)
+    return [np.concatenate(words[4 * r:4 * r + 4]).astype(np.uint8) for r in range(nr + 1)]
 
 
 def load_all_coeffs(coeff_dir: Path = COEFF_DIR) -> Dict[str, Any]:

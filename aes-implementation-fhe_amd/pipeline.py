@@ -1,4 +1,7 @@
-"""AESPipeline: AES-128 round orchestration on CKKS/Zeta16 (REF/pipeline.py:17-254).
+"""AESPipeline: AES round orchestration on CKKS/Zeta16 (REF/pipeline.py:17-254).
+
+The key size follows the round keys: 11 / 13 / 15 of them (AES-128 / 192 / 256), clear or encrypted, run 10 / 12 / 14
+rounds in every method that takes round keys; any other count is a ValueError.  The reference runs AES-128 only.
 
 Drop-in for the reference class: same constructor, same coefficient keys ('xor4',
 'sub_hi', 'sub_lo', 'inv_sub_hi', 'inv_sub_lo'), same step order, optional renorm
@@ -36,7 +39,7 @@ layout (state_encoder.py): ``encrypt`` / ``decrypt`` take and
 (B, 16) arrays through the same step sequence, and a (16,) round key is shared by all B
 states (a (B, 16) key array gives each state its own).
 
-``fips=True`` computes FIPS-197 AES-128 instead of the reference's cipher (whose MixColumns mixes along
+``fips=True`` computes FIPS-197 AES (128, 192 or 256 by the key count) instead of the reference's cipher (whose MixColumns mixes along
 rows).  With T the 4 x 4 byte transpose, fips_encrypt(p, rks) = T(E'(T p, [T rk_r])) where
 E' is this pipeline's round sequence with ShiftColumns = T . ShiftRows . T in place of ShiftRows
 (shift_columns.py) and MixColumns unchanged; decrypt likewise with the inverses.  So the mode is the two
@@ -56,9 +59,10 @@ one ct x ct level more; ``transcipher_lut_bank`` / ``to_lut_bank`` (DESIGN.md §
 per byte, and return several outputs of one keystream.
 
 Encrypted round keys (key_expansion.py): every method that takes ``round_keys`` takes either the list of
-11 clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- 11 ciphertext
-pairs the server never saw in clear: ``expand_key(*encrypt_key(master))`` derives them homomorphically from ONE
-encrypted 16-byte key, ``EncryptedRoundKeys.from_pairs`` wraps keys the client expanded itself.  Their packed forms are
+11 (13, 15) clear byte arrays (encrypted here, as the reference does) or a ``key_expansion.EncryptedRoundKeys`` -- as many
+ciphertext pairs the server never saw in clear: ``expand_key(*encrypt_key(master))`` derives them homomorphically from ONE
+encrypted 16-byte key, or from the two halves of an encrypted 32-byte key (DESIGN.md §3.30);
+``EncryptedRoundKeys.from_pairs`` wraps keys the client expanded itself (the route of AES-192).  Their packed forms are
 built homomorphically and cached on the object.  Refused (ValueError): keys of another layout or byte order,
 ``pairs`` > 1, ``fuse_sub_ark`` (its fused keys permute clear key bytes).
 """
@@ -89,6 +93,15 @@ _KEY_BASIS = os.environ.get("AESFHE_KEY_BASIS", "1") != "0"
 # AESFHE_FHE_SB_NIB=0: true-FHE mode keeps the reference's 8 -> 4 (Inv)SubBytes (depth 13, double snaps)
 # instead of the nibble-bivariate form (A/B runs)
 _FHE_NIB = os.environ.get("AESFHE_FHE_SB_NIB", "1") != "0"
+
+
+def round_count(round_keys) -> int:
+    """Nr = 10 / 12 / 14 for 11 / 13 / 15 round keys (AES-128 / 192 / 256), clear or EncryptedRoundKeys; any other
+    count is a ValueError, raised before any GPU work"""
+    n = len(round_keys)
+    if n not in EncryptedRoundKeys.COUNTS:
+        raise ValueError(f"AES takes 11 round keys (AES-128), 13 (AES-192) or 15 (AES-256), got {n}")
+    return n - 1
 
 
 class AESPipeline:
@@ -162,7 +175,7 @@ class AESPipeline:
             self.srmc = ShiftRowsMixColumnsFusedEnc(ctx, self.mix, states)
         self._fk_cache: Dict[Tuple[int, int], Tuple[Any, Any]] = {}
         self._fk_tag = b""
-        # packed XOR stage of encrypt rounds 1..9; AESFHE_PACKED_XOR=0 for A/B
+        # packed XOR stage of encrypt's middle rounds 1..nr - 1; AESFHE_PACKED_XOR=0 for A/B
         if packed_xor is None:
             packed_xor = os.environ.get("AESFHE_PACKED_XOR", "1") != "0"
         self.packed_xor = bool(packed_xor and use_hard_renorm_between_steps and not true_fhe and self.srmc is None
@@ -171,7 +184,7 @@ class AESPipeline:
         self._pk_tag = b""
         self._kb_cache: Dict[int, Dict[str, Any]] = {}  # round -> the packed key's dropped form and std basis
         self._kb_tag = b""
-        # the same for decrypt rounds 9..1: AddRoundKey + InvMixColumns (with_inv_mix_columns)
+        # the same for decrypt's middle rounds nr - 1..1: AddRoundKey + InvMixColumns (with_inv_mix_columns)
         self.packed_dec = bool(self.packed_xor and with_inv_mix_columns and not fuse_sub_ark
                                and hasattr(self.invmix, "packed_ok") and self.invmix.packed_ok())
         # the level encrypt's renorms hand SubBytes: one above its depth in renorm mode, so that it
@@ -238,19 +251,44 @@ class AESPipeline:
     def encrypt_key(self, master: np.ndarray, seeded: bool = False):
         """client side: the (hi, lo) encryption of a (16,) AES-128 key, or of a (states, 16) array with one key
         per state (a (16,) key is shared by all states, as _encode_key broadcasts it) -- expand_key's input.
-        seeded=True: one batched seeded symmetric encryption, the pair then crosses the wire as
-        halves (state_encoder.dump_ct_seeded / load_ct_seeded)"""
+        A (32,) or (states, 32) AES-256 key gives the 4-tuple (hi0, lo0, hi1, lo1): the pairs of key bytes 0..15 and
+        16..31, what expand_key takes as its four ciphertexts.  A 24-byte key is a ValueError: the AES-192 schedule is
+        not expanded homomorphically (EncryptedRoundKeys.from_pairs takes its 13 client-expanded keys).
+        seeded=True: one batched seeded symmetric encryption (of all four ciphertexts for a 32-byte
+        key), the ciphertexts then cross the wire as halves (state_encoder.dump_ct_seeded / load_ct_seeded)"""
         if seeded and self.pairs > 1:
             raise ValueError("encrypt_key: seeded encryption of multi-pair batches (pairs > 1) is not supported")
-        return self._encode_key(master, seeded)
+        n = np.shape(master)[-1] if np.ndim(master) else 0
+        if n == 24:
+            raise ValueError("encrypt_key: a 24-byte AES-192 key is not expanded homomorphically; expand it on the "
+                             "client and wrap its 13 encrypted round keys with EncryptedRoundKeys.from_pairs")
+        if n != 32:
+            return self._encode_key(master, seeded)
+        key = np.asarray(master, dtype=np.uint8)
+        if self.states > 1 and key.shape == (32,):
+            key = np.broadcast_to(key, (self.states, 32))
+        if key.shape != ((32,) if self.states == 1 else (self.states, 32)):
+            raise ValueError(f"encrypt_key: a (32,) AES-256 key or one per state, ({self.states}, 32); got {key.shape}")
+        halves = [key[..., :16], key[..., 16:]]
+        if seeded:
+            (hi0, lo0), (hi1, lo1) = self.encoder.encode_many(halves, seeded=True)
+        else:
+            (hi0, lo0), (hi1, lo1) = (self.encoder.encode(h) for h in halves)
+        return hi0, lo0, hi1, lo1
 
-    def expand_key(self, key_hi, key_lo, debug: Dict[str, Any] | None = None) -> EncryptedRoundKeys:
+    def expand_key(self, key_hi, key_lo, key_hi1=None, key_lo1=None, debug: Dict[str, Any] | None = None) -> EncryptedRoundKeys:
         """the 11 round keys of an encrypted AES-128 key, derived homomorphically (key_expansion.KeyExpansion,
         DESIGN.md §3.19): what encrypt / decrypt / encrypt_public / ctr_keystream / transcipher take as
-        round_keys in place of clear bytes.  A debug dict gets the stages ks.r{r}.{prefix,sub,rot,out}."""
+        round_keys in place of clear bytes.  With the second pair (key_hi1, key_lo1) -- expand_key(*encrypt_key(key32))
+        -- the 15 round keys of an encrypted AES-256 key: keys 0 and 1 are the inputs, renormalised.
+        A debug dict gets the stages ks.r{r}.{prefix,sub,rot,out} (r = 1..10, or 2..14 for AES-256)."""
+        if (key_hi1 is None) != (key_lo1 is None):
+            raise ValueError("expand_key: the second half of an AES-256 key is a (hi, lo) pair, both or neither")
         if getattr(self, "_key_expansion", None) is None:
             self._key_expansion = KeyExpansion(self)
-        return self._key_expansion.expand(key_hi, key_lo, debug)
+        if key_hi1 is None:
+            return self._key_expansion.expand(key_hi, key_lo, debug)
+        return self._key_expansion.expand256(key_hi, key_lo, key_hi1, key_lo1, debug)
 
     def _check_encrypted_keys(self, erk: EncryptedRoundKeys) -> None:
         if self.pairs > 1:
@@ -267,12 +305,16 @@ class AESPipeline:
         return self._rk_tag if isinstance(self._rk_tag, EncryptedRoundKeys) else None
 
     def _prepare_round_keys(self, round_keys):
+        """the encrypted (hi, lo) pair of every round key: 11, 13 or 15 of them, and the callers run len - 1 rounds.
+        The caches behind it (_rk_cache, _pk_cache, _kb_cache, _fk_cache) are keyed by the bytes of the whole schedule
+        and sized by its length, so schedules of different lengths never share an entry"""
+        round_count(round_keys)
         if isinstance(round_keys, EncryptedRoundKeys):  # already ciphertexts: cached by the object, nothing encoded
             self._check_encrypted_keys(round_keys)
             if self._rk_tag is not round_keys:
                 self._rk_cache, self._rk_raw, self._rk_tag = round_keys.pairs, None, round_keys
             return self._rk_cache
-        tag = b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
+        tag = bytes([len(round_keys)]) + b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
         if self._rk_cache is None or self._rk_tag != tag:  # encrypted round keys are reused across calls
             self._rk_cache = [self._encode_key(np.asarray(k, dtype=np.uint8)) for k in round_keys]
             self._rk_raw = [np.array(k, dtype=np.uint8) for k in round_keys]
@@ -392,7 +434,7 @@ class AESPipeline:
     def _fused_key(self, round_keys, r: int, direction: int):
         """round key r permuted by ShiftRows (direction -1) / InvShiftRows (+1), encrypted once:
         the key of a SubBytes-AddRoundKey fusion across a ShiftRows (sub_bytes_ark.py)"""
-        tag = b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
+        tag = bytes([len(round_keys)]) + b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
         if tag != self._fk_tag:
             self._fk_cache, self._fk_tag = {}, tag
         if (r, direction) not in self._fk_cache:
@@ -448,7 +490,7 @@ class AESPipeline:
 
     # ---------------------------------------------------------------- encrypt
     def encrypt_round(self, ct, key_pair, debug=None, r: int = 0, next_level: int | None = None):
-        """One middle round r = 1..9: SB, renorm, SR, MC, ARK, renorm (REF :142-151).  With a
+        """One middle round r = 1..nr - 1 (nr = 10 / 12 / 14): SB, renorm, SR, MC, ARK, renorm (REF :142-151).  With a
         debug dict every step is logged under enc.r{r}.<step> (the names of the reference's
         one-round debug block, REF :154-171)."""
         if next_level is None:
@@ -514,6 +556,8 @@ class AESPipeline:
         return ct
 
     def encrypt(self, state: np.ndarray, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
+        """AES-128 / 192 / 256 by the number of round keys: 11 / 13 / 15 keys run 10 / 12 / 14 rounds"""
+        round_count(round_keys)  # before the state is encrypted
         if debug is not None:
             debug.clear()
         ct = self.encoder.encode(state)
@@ -523,20 +567,21 @@ class AESPipeline:
         return self._encrypt_tail(ct, rk, round_keys, debug)
 
     def _encrypt_tail(self, ct, rk, round_keys, debug):
-        """encrypt after round 0's AddRoundKey: its renorm, rounds 1..9, the final round (shared by encrypt
-        and encrypt_public, whose round 0 differs)"""
+        """encrypt after round 0's AddRoundKey: its renorm, rounds 1..nr - 1, the final round nr = len(rk) - 1 (shared
+        by encrypt and encrypt_public, whose round 0 differs)"""
+        nr = len(rk) - 1
         self._log_pair(debug, "enc.r0.ark", *ct)
         ct = self._renorm_pair(*ct, level=self.need_sub)
         self._log_pair(debug, "enc.r0.renorm", *ct)
-        for r in range(1, 10):
-            nxt = NEED_SUB_ARK_SR if (self.fuse_sub_ark and r == 9) else self.need_sub
+        for r in range(1, nr):
+            nxt = NEED_SUB_ARK_SR if (self.fuse_sub_ark and r == nr - 1) else self.need_sub
             ct = self.encrypt_round(ct, rk[r], debug, r, next_level=nxt)
         if self.fuse_sub_ark:
-            # SR(SB(x)) ^ k10 = SR(SB(x) ^ InvShiftRows(k10)): one fused LUT, then ShiftRows
-            ct = self.sbark(*ct, *self._fused_key(round_keys, 10, +1))
+            # SR(SB(x)) ^ k_nr = SR(SB(x) ^ InvShiftRows(k_nr)): one fused LUT, then ShiftRows
+            ct = self.sbark(*ct, *self._fused_key(round_keys, nr, +1))
             self._log_pair(debug, "enc.final.sub_ark", *ct)
             ct = self.shift_rows(*ct)
-            self._log_pair(debug, "enc.final.ark10", *ct)
+            self._log_pair(debug, f"enc.final.ark{nr}", *ct)
             ct = self._renorm_pair(*ct)
             self._log_pair(debug, "enc.output", *ct)
             return tag_layout(self.layout, *ct)
@@ -550,8 +595,8 @@ class AESPipeline:
             self._log_pair(debug, "enc.final.sub.renorm", *ct)
             ct = self.shift_rows(*ct)
         self._log_pair(debug, "enc.final.sr", *ct)
-        ct = self.ark(*ct, *rk[10], out_level=self._floor())
-        self._log_pair(debug, "enc.final.ark10", *ct)
+        ct = self.ark(*ct, *rk[nr], out_level=self._floor())
+        self._log_pair(debug, f"enc.final.ark{nr}", *ct)
         ct = self._renorm_pair(*ct)
         self._log_pair(debug, "enc.output", *ct)
         return tag_layout(self.layout, *ct)
@@ -567,6 +612,7 @@ class AESPipeline:
         encrypt's own path.  Same bytes and the same layout-tagged pair as encrypt(state, round_keys); the
         debug stages keep encrypt's names (no "enc.input": there is no input ciphertext)."""
         self._no_pairs("encrypt_public")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         if debug is not None:
             debug.clear()
         rk = self._prepare_round_keys(round_keys)
@@ -578,6 +624,7 @@ class AESPipeline:
         encrypted key: encrypt_public of ctr_mode.counter_blocks, one block per state"""
         from ctr_mode import counter_blocks
         self._no_pairs("ctr_keystream")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         blocks = counter_blocks(nonce12, counter0, self.states)
         return self.encrypt_public(blocks[0] if self.states == 1 else blocks, round_keys)
 
@@ -588,6 +635,7 @@ class AESPipeline:
         is evaluated under the encrypted key and XORed with the public ciphertext bytes (AddRoundKey.public),
         then renormalised by the pipeline's own renorm (secret-key, or bootstrap + snap with true_fhe)."""
         self._no_pairs("transcipher")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
         ct = self.ark.public(*ks, *nib, out_level=self._floor())
@@ -631,6 +679,7 @@ class AESPipeline:
         decode_values returns (states, 16 // w).  dtype "u1" with a scalar gain and no offset is the path above,
         unchanged; any other dtype (32-bit words would add no precision over 16) raises ValueError."""
         self._no_pairs("transcipher_values")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
         typed = self._typed_lut(dtype, gain, offset)
         lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
@@ -665,6 +714,7 @@ class AESPipeline:
         groups of the decode, rotated together in one batched key switch).  Slots that hold no state hold 0;
         encoder.decode_values returns (states, 16)."""
         self._no_pairs("transcipher_linear")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
         lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
@@ -697,6 +747,7 @@ class AESPipeline:
         left on the fresh-level-7 set); no XOR4, renorm or bootstrap comes after the keystream
         (xor_value_lut.ByteValueLUT).  Slots that hold no state hold 0; encoder.decode_values returns (states, 16)."""
         self._no_pairs("transcipher_lut")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
         lut = self._byte_lut(table, gain)
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
@@ -743,6 +794,7 @@ class AESPipeline:
         keystream, as transcipher_lut's.  Slots that hold no state hold 0; encoder.decode_values reads each output as
         (states, 16)."""
         self._no_pairs("transcipher_lut_bank")
+        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
         nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
         bank = self._byte_bank(tables, select, gain)
         ks = self.ctr_keystream(nonce12, counter0, round_keys)
@@ -758,6 +810,8 @@ class AESPipeline:
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
+        """the inverse of encrypt: 11 / 13 / 15 round keys undo 10 / 12 / 14 rounds"""
+        nr = round_count(round_keys)
         check_layout(self.layout, ct_hi, ct_lo)  # a pair from another layout would decrypt to wrong bytes
         if debug is not None:
             debug.clear()
@@ -765,8 +819,8 @@ class AESPipeline:
         self._log_pair(debug, "dec.input", ct_hi, ct_lo)
         if self.true_fhe and not self.fuse_sub_ark:
             return self._decrypt_fhe(ct_hi, ct_lo, rk, debug)
-        ct = self.ark(ct_hi, ct_lo, *rk[10], out_level=self._floor())
-        self._log_pair(debug, "dec.init.ark10", *ct)
+        ct = self.ark(ct_hi, ct_lo, *rk[nr], out_level=self._floor())
+        self._log_pair(debug, f"dec.init.ark{nr}", *ct)
         fuse = self.fuse_sub_ark
         if fuse and self.isub is None:
             raise KeyError("inv_sub_hi")
@@ -777,8 +831,8 @@ class AESPipeline:
             ct, isr_done = self.encoder.renorm_perm(*ct, isr, level=self.need_isr_isb - SHIFTROWS_DEPTH), True
         else:
             ct, isr_done = self._renorm_pair(*ct, level=NEED_SUB_ARK_SR if fuse else self.need_isr_isb), False
-        self._log_pair(debug, "dec.init.ark10.renorm", *ct)
-        for r in range(9, 0, -1):
+        self._log_pair(debug, f"dec.init.ark{nr}.renorm", *ct)
+        for r in range(nr - 1, 0, -1):
             if fuse:
                 # ISB(ISR(x)) ^ k_r = ISR(ISB(x) ^ ShiftRows(k_r)): one fused LUT, then InvShiftRows
                 ct = self.isbark(*ct, *self._fused_key(round_keys, r, -1))
@@ -852,11 +906,12 @@ class AESPipeline:
         if self.isub is None:
             raise KeyError("inv_sub_hi")
         fl = self._floor()
-        ct = self.ark(ct_hi, ct_lo, *rk[10], out_level=fl)
-        self._log_pair(debug, "dec.init.ark10", *ct)
+        nr = len(rk) - 1
+        ct = self.ark(ct_hi, ct_lo, *rk[nr], out_level=fl)
+        self._log_pair(debug, f"dec.init.ark{nr}", *ct)
         ct = self._renorm_pair(*self.inv_shift_rows(*ct), level=NEED_SUBBYTES)
-        self._log_pair(debug, "dec.r9.isr", *ct)
-        for r in range(9, -1, -1):
+        self._log_pair(debug, f"dec.r{nr - 1}.isr", *ct)
+        for r in range(nr - 1, -1, -1):
             # InvSubBytes' output error is ~3e-2: its renorm snaps twice before AddRoundKey's XOR4
             ct = self._renorm_pair(*self.isub.apply(*ct, out_level=fl), level=NEED_XOR)
             self._log_pair(debug, f"dec.r{r}.isb" if r else "dec.final.isb.renorm", *ct)
