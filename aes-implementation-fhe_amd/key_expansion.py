@@ -251,6 +251,7 @@ class EncryptedRoundKeys:
             check_layout(layout, *p)
             tag_layout(layout, *p)
         self.pairs, self.layout = pairs, layout
+        self.raw = None  # no key byte in clear (ClearRoundKeys has them)
         self.packed: List[Any] = [None] * len(pairs)
         self.key_basis: Dict[int, Dict[str, Any]] = {}
 
@@ -282,6 +283,28 @@ class EncryptedRoundKeys:
 
     def __getitem__(self, r: int):
         return self.pairs[r]
+
+
+class ClearRoundKeys:
+    """the key schedule an AESPipeline keeps for CLEAR round keys, in EncryptedRoundKeys' shape: `pairs` (the keys
+    encrypted by the pipeline, as the reference does), `packed` and `key_basis` as there, and what only clear keys can
+    have: `raw` (the uint8 key arrays) and `fused` ((round, direction) -> the encrypted pair of the key permuted by
+    (Inv)ShiftRows, AESPipeline._fused_key).  A pipeline keeps the most recent one and reuses it while `matches`."""
+
+    def __init__(self, raw, pairs):
+        self.raw, self.pairs = raw, pairs
+        self.tag = self.tag_of(raw)
+        self.packed: List[Any] = [None] * len(pairs)
+        self.key_basis: Dict[int, Dict[str, Any]] = {}
+        self.fused: Dict[Tuple[int, int], Tuple[Any, Any]] = {}
+
+    @staticmethod
+    def tag_of(raw) -> bytes:
+        """the round-key count, then the bytes of all keys: schedules of different lengths never match"""
+        return bytes([len(raw)]) + b"".join(k.tobytes() for k in raw)
+
+    def matches(self, raw) -> bool:
+        return self.tag == self.tag_of(raw)
 
 
 class KeyExpansion:

@@ -31,8 +31,8 @@ exactly SubBytes' 13 levels).  No secret key is used between encryption and decr
 after it on packed states -- hi and lo side by side in ONE ciphertext, the XOR4 LUT being the
 same for both halves (MixColFinal.mix_packed): single XOR4s instead of pairs,
 single-ciphertext renorms, one sparse bootstrap; the renorm after AddRoundKey unpacks into the
-(hi, lo) pair SubBytes reads.  A debug dict logs the packed path's own stages (``packed_xor=False``
-runs the reference's pair steps).
+(hi, lo) pair SubBytes reads (``packed_xor=False`` runs the reference's pair steps).  On either path a
+debug dict logs the stages of the very run an unlogged call makes: same levels, folds and hand-overs.
 
 ``states`` = B > 1 runs B independent AES states per ciphertext pair in the slot-packed
 layout (state_encoder.py): ``encrypt`` / ``decrypt`` take and return
@@ -69,13 +69,13 @@ built homomorphically and cached on the object.  Refused (ValueError): keys of a
 from __future__ import annotations
 
 import os
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 
 from add_round_key import AddRoundKey
 from invmixcolumns_fhe import InvMixColumnsFHE
-from key_expansion import EncryptedRoundKeys, KeyExpansion
+from key_expansion import ClearRoundKeys, EncryptedRoundKeys, KeyExpansion
 from inv_shiftrows import InvShiftRows
 from mixcol_final import MixColFinal
 from shift_rows import ShiftRows
@@ -102,6 +102,30 @@ def round_count(round_keys) -> int:
     if n not in EncryptedRoundKeys.COUNTS:
         raise ValueError(f"AES takes 11 round keys (AES-128), 13 (AES-192) or 15 (AES-256), got {n}")
     return n - 1
+
+
+# The shared bodies of AESPipeline's transcipher_* and to_* methods.  Module functions, so that they serve any object
+# with the pipeline's attributes (the CPU tests bind single methods to stand-ins).  `build` makes the LUT object and
+# raises the ValueErrors of its own arguments; every refusal comes before any GPU work, in the order written here.
+def _transcipher_with(pipe, name: str, aes_ct, nonce12, counter0: int, round_keys, build):
+    pipe._no_pairs(name)
+    round_count(round_keys)  # 11 / 13 / 15 keys
+    nib = pipe.encoder.nibble_slots(aes_ct)  # checks the shape
+    lut = build()
+    ks = pipe.ctr_keystream(nonce12, counter0, round_keys)
+    return lut.apply_public(*ks, *nib)
+
+
+def _convert_with(pipe, name: str, ct_hi, ct_lo, build):
+    pipe._no_pairs(name)
+    check_layout(pipe.layout, ct_hi, ct_lo)
+    return build().apply(ct_hi, ct_lo)
+
+
+def _values_lut(pipe, dtype, gain, offset):
+    """the LUT of transcipher_values / to_values: the typed one, or XorValueLUT for plain unsigned bytes"""
+    typed = pipe._typed_lut(dtype, gain, offset)
+    return typed if typed is not None else pipe._value_lut(1.0 / 256.0 if gain is None else gain)
 
 
 class AESPipeline:
@@ -162,8 +186,9 @@ class AESPipeline:
         self.snapper = None
         self.use_hard_renorm_between_steps = use_hard_renorm_between_steps
         self.with_inv_mix_columns = with_inv_mix_columns
-        self._rk_cache: List[Tuple[Any, Any]] | None = None
-        self._rk_tag = b""
+        # the key schedule of the last call (_prepare_round_keys): a ClearRoundKeys or the caller's EncryptedRoundKeys
+        self._schedule: ClearRoundKeys | EncryptedRoundKeys | None = None
+        self._fold_perms: Dict[Any, Any] = {}  # shift module -> its slot_perm() (_fold_perm)
         self.fuse_sub_ark = fuse_sub_ark
         if fuse_sub_ark:
             self.sbark = SubBytesARK(self.sub, coeffs["xor4"])
@@ -173,17 +198,11 @@ class AESPipeline:
             if not hasattr(self.mix, "mix_rotated"):
                 raise TypeError("fuse_sr_mc needs a MixColFinal (mix_rotated) as mixcolumns")
             self.srmc = ShiftRowsMixColumnsFusedEnc(ctx, self.mix, states)
-        self._fk_cache: Dict[Tuple[int, int], Tuple[Any, Any]] = {}
-        self._fk_tag = b""
         # packed XOR stage of encrypt's middle rounds 1..nr - 1; AESFHE_PACKED_XOR=0 for A/B
         if packed_xor is None:
             packed_xor = os.environ.get("AESFHE_PACKED_XOR", "1") != "0"
         self.packed_xor = bool(packed_xor and use_hard_renorm_between_steps and not true_fhe and self.srmc is None
                                and hasattr(self.mix, "packed_ok") and self.mix.packed_ok())
-        self._pk_cache: List[Any] | None = None
-        self._pk_tag = b""
-        self._kb_cache: Dict[int, Dict[str, Any]] = {}  # round -> the packed key's dropped form and std basis
-        self._kb_tag = b""
         # the same for decrypt's middle rounds nr - 1..1: AddRoundKey + InvMixColumns (with_inv_mix_columns)
         self.packed_dec = bool(self.packed_xor and with_inv_mix_columns and not fuse_sub_ark
                                and hasattr(self.invmix, "packed_ok") and self.invmix.packed_ok())
@@ -232,14 +251,16 @@ class AESPipeline:
         """AddRoundKey then renorm: the XOR4s run on inputs dropped just above the floor"""
         return self._renorm_pair(*self.ark(*ct, *key_pair, out_level=self._floor()), level=level)
 
+    def _sub_level(self, level):
+        """the level the renorm after (Inv)SubBytes hands out, `level` but in true-FHE mode: SubBytes' ~3e-2 output
+        errors get two snaps (ShiftRows + the GF multipliers need 6 levels, MixColumns renormalises after them)"""
+        return NEED_SR_ARK if self.true_fhe else level
+
     def _sub_renorm(self, ct, inverse: bool = False, level=None):
         lut = self.isub if inverse else self.sub
         if lut is None:
             raise KeyError("inv_sub_hi")
-        if self.true_fhe:
-            level = NEED_SR_ARK  # true-FHE: SubBytes' ~3e-2 output errors get two snaps (ShiftRows +
-            #                      the GF multipliers need 6 levels, MixColumns renormalises after them)
-        return self._renorm_pair(*self._sub_apply(ct, defer_conj=True, lut=lut), level=level)
+        return self._renorm_pair(*self._sub_apply(ct, defer_conj=True, lut=lut), level=self._sub_level(level))
 
     def _encode_key(self, key_bytes: np.ndarray, seeded: bool = False):
         key_bytes = np.asarray(key_bytes, dtype=np.uint8)
@@ -300,26 +321,20 @@ class AESPipeline:
         if not self.layout.same(erk.layout):  # ciphertexts that carry no tag (the CPU oracle's)
             raise ValueError("encrypted round keys were made for another slot layout or byte order")
 
-    def _encrypted_keys(self) -> EncryptedRoundKeys | None:
-        """the EncryptedRoundKeys of the last _prepare_round_keys, None after clear round keys"""
-        return self._rk_tag if isinstance(self._rk_tag, EncryptedRoundKeys) else None
-
     def _prepare_round_keys(self, round_keys):
         """the encrypted (hi, lo) pair of every round key: 11, 13 or 15 of them, and the callers run len - 1 rounds.
-        The caches behind it (_rk_cache, _pk_cache, _kb_cache, _fk_cache) are keyed by the bytes of the whole schedule
-        and sized by its length, so schedules of different lengths never share an entry"""
+        Everything cached per key schedule (the pairs, the packed keys, their XOR4 bases, the fused keys) lives on ONE
+        object, self._schedule: the caller's EncryptedRoundKeys, kept by identity with nothing encoded, or the most
+        recent ClearRoundKeys, reused while the key count and the bytes of all keys match"""
         round_count(round_keys)
-        if isinstance(round_keys, EncryptedRoundKeys):  # already ciphertexts: cached by the object, nothing encoded
+        if isinstance(round_keys, EncryptedRoundKeys):
             self._check_encrypted_keys(round_keys)
-            if self._rk_tag is not round_keys:
-                self._rk_cache, self._rk_raw, self._rk_tag = round_keys.pairs, None, round_keys
-            return self._rk_cache
-        tag = bytes([len(round_keys)]) + b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
-        if self._rk_cache is None or self._rk_tag != tag:  # encrypted round keys are reused across calls
-            self._rk_cache = [self._encode_key(np.asarray(k, dtype=np.uint8)) for k in round_keys]
-            self._rk_raw = [np.array(k, dtype=np.uint8) for k in round_keys]
-            self._rk_tag = tag
-        return self._rk_cache
+            self._schedule = round_keys
+            return round_keys.pairs
+        raw = [np.array(k, dtype=np.uint8) for k in round_keys]
+        if not (isinstance(self._schedule, ClearRoundKeys) and self._schedule.matches(raw)):
+            self._schedule = ClearRoundKeys(raw, [self._encode_key(k) for k in raw])
+        return self._schedule.pairs
 
     def _ark_packed(self, x, r: int, defer_conj: bool = False):
         """AddRoundKey on a packed state: XOR4(x, packed round key r).  The key's level drop and
@@ -330,43 +345,23 @@ class AESPipeline:
         key = self._packed_round_key(r)
         if not _KEY_BASIS:
             return self.xor4.apply(x, key, out_level=self._floor())
-        erk = self._encrypted_keys()
-        if erk is None and self._kb_tag != self._rk_tag:
-            self._kb_cache, self._kb_tag = {}, self._rk_tag
-        if not self._xor4_keep_b():  # an XOR4 without basis sharing (a caller-supplied LUT object)
-            return self.xor4.apply(x, key, out_level=self._floor())
-        kb = (self._kb_cache if erk is None else erk.key_basis).setdefault(r, {})
-        if defer_conj and FOLDS.conj and self._xor4_defer_ok():
-            return self.xor4.apply(x, key, out_level=self._floor(), keep_b=kb, defer_conj=True)
-        return self.xor4.apply(x, key, out_level=self._floor(), keep_b=kb)
+        kb = self._schedule.key_basis.setdefault(r, {})
+        return self.xor4.apply(x, key, out_level=self._floor(), keep_b=kb, defer_conj=bool(defer_conj and FOLDS.conj))
 
-    def _isr_perm(self, ct, debug):
-        """InvShiftRows' byte permutation when the renorm before it can fold it (as _sr_perm)"""
+    def _fold_perm(self, shift, ct):
+        """the byte permutation of `shift` (self.shift or self.invshift) when the renorm before it can fold it
+        (utils.FOLDS.sr: off in the strict default; secret-key renorm mode, one period-16 state pair on the device),
+        else None.  A debug run keeps the fold and logs what it can (no separate log of the renorm's own output)"""
         if not FOLDS.sr or self.true_fhe or not self.use_hard_renorm_between_steps:
             return None
-        if not hasattr(self, "_isr_perm_v"):
-            sp = getattr(self.invshift, "slot_perm", None)
-            self._isr_perm_v = sp() if sp is not None else None
-        if self._isr_perm_v is None:
-            return None
+        if shift not in self._fold_perms:
+            sp = getattr(shift, "slot_perm", None)
+            self._fold_perms[shift] = sp() if sp is not None else None
+        perm = self._fold_perms[shift]
         ok = getattr(self.encoder, "renorm_perm_ok", None)
-        c0 = ct[0].s1 if hasattr(ct[0], "s1") else ct[0]
-        return self._isr_perm_v if ok is not None and ok(c0) else None
-
-    def _sr_perm(self, ct, debug):
-        """ShiftRows' byte permutation when the renorm before it can fold it (utils.FOLDS.sr: off in the
-        strict default; secret-key renorm mode, one period-16 state pair on the device), else None.  A
-        debug run keeps the fold and logs what it can (no separate log of the renorm's own output)"""
-        if not FOLDS.sr or self.true_fhe or not self.use_hard_renorm_between_steps:
+        if perm is None or ok is None:
             return None
-        if not hasattr(self, "_sr_perm_v"):
-            sp = getattr(self.shift, "slot_perm", None)
-            self._sr_perm_v = sp() if sp is not None else None
-        if self._sr_perm_v is None:
-            return None
-        ok = getattr(self.encoder, "renorm_perm_ok", None)
-        c0 = ct[0].s1 if hasattr(ct[0], "s1") else ct[0]
-        return self._sr_perm_v if ok is not None and ok(c0) else None
+        return perm if ok(ct[0].s1 if hasattr(ct[0], "s1") else ct[0]) else None
 
     def _sr_entry_ok(self) -> bool:
         """ShiftRows runs inside MixColumns' packed entry (MixColFinal.sr_entry): the rot form with its
@@ -380,66 +375,34 @@ class AESPipeline:
         output goes straight into _renorm_pair): the nibble form may hand over utils.ConjSum halves
         for the folded renorm"""
         lut = self.sub if lut is None else lut
-        if defer_conj and FOLDS.conj and self.use_hard_renorm_between_steps and not self.true_fhe:
-            import inspect
-            try:
-                ok = "defer_conj" in inspect.signature(lut.apply).parameters
-            except (TypeError, ValueError):
-                ok = False
-            if ok:
-                return lut.apply(*ct, out_level=self._floor(), defer_conj=True)
-        return lut.apply(*ct, out_level=self._floor())
-
-    def _xor4_defer_ok(self) -> bool:
-        """whether this pipeline's XOR4 takes defer_conj (checked once)"""
-        if not hasattr(self, "_defer_ok"):
-            import inspect
-            try:
-                self._defer_ok = "defer_conj" in inspect.signature(self.xor4.apply).parameters
-            except (TypeError, ValueError):
-                self._defer_ok = False
-        return self._defer_ok
-
-    def _xor4_keep_b(self) -> bool:
-        """whether this pipeline's XOR4 takes keep_b (checked once; a TypeError raised INSIDE the
-        evaluation must surface, not be taken for a missing keyword)"""
-        if not hasattr(self, "_keep_b_ok"):
-            import inspect
-            try:
-                self._keep_b_ok = "keep_b" in inspect.signature(self.xor4.apply).parameters
-            except (TypeError, ValueError):
-                self._keep_b_ok = False
-        return self._keep_b_ok
+        defer = bool(defer_conj and FOLDS.conj and self.use_hard_renorm_between_steps and not self.true_fhe)
+        return lut.apply(*ct, out_level=self._floor(), defer_conj=defer)
 
     def _packed_round_key(self, r: int):
-        """round key r encrypted in the packed form (after _prepare_round_keys of the same keys); an encrypted
-        key schedule is packed homomorphically, once, and the packed form kept on the EncryptedRoundKeys"""
-        erk = self._encrypted_keys()
-        if erk is not None:
-            if erk.packed[r] is None:
-                if self.use_hard_renorm_between_steps and not self.true_fhe:
-                    erk.packed[r] = self.encoder.renorm_pack(*erk.pairs[r])  # the packing renorm where it applies
-                else:
-                    erk.packed[r] = self.encoder.pack(*erk.pairs[r])
-            return erk.packed[r]
-        if self._pk_cache is None or self._pk_tag != self._rk_tag:
-            self._pk_cache, self._pk_tag = [None] * len(self._rk_cache), self._rk_tag
-        if self._pk_cache[r] is None:
-            key = self._rk_raw[r]
-            if self.states > 1 and key.shape == (16,):
-                key = np.broadcast_to(key, (self.states, 16))
-            self._pk_cache[r] = self.encoder.encode_packed(key)
-        return self._pk_cache[r]
+        """round key r of the current schedule (after _prepare_round_keys) encrypted in the packed form, made once and
+        kept on the schedule: clear key bytes are encoded packed, an encrypted key is packed homomorphically"""
+        ks = self._schedule
+        if ks.packed[r] is None:
+            if ks.raw is not None:
+                key = ks.raw[r]
+                if self.states > 1 and key.shape == (16,):
+                    key = np.broadcast_to(key, (self.states, 16))
+                ks.packed[r] = self.encoder.encode_packed(key)
+            elif self.use_hard_renorm_between_steps and not self.true_fhe:
+                ks.packed[r] = self.encoder.renorm_pack(*ks.pairs[r])  # the packing renorm where it applies
+            else:
+                ks.packed[r] = self.encoder.pack(*ks.pairs[r])
+        return ks.packed[r]
 
-    def _fused_key(self, round_keys, r: int, direction: int):
-        """round key r permuted by ShiftRows (direction -1) / InvShiftRows (+1), encrypted once:
-        the key of a SubBytes-AddRoundKey fusion across a ShiftRows (sub_bytes_ark.py)"""
-        tag = bytes([len(round_keys)]) + b"".join(np.ascontiguousarray(k, dtype=np.uint8).tobytes() for k in round_keys)
-        if tag != self._fk_tag:
-            self._fk_cache, self._fk_tag = {}, tag
-        if (r, direction) not in self._fk_cache:
-            self._fk_cache[(r, direction)] = self._encode_key(shift_rows_bytes(np.asarray(round_keys[r], np.uint8), direction))
-        return self._fk_cache[(r, direction)]
+    def _fused_key(self, r: int, direction: int):
+        """round key r of the current (clear) schedule permuted by ShiftRows (direction -1) / InvShiftRows (+1),
+        encrypted once: the key of a SubBytes-AddRoundKey fusion across a ShiftRows (sub_bytes_ark.py)"""
+        # only fuse_sub_ark calls this, and _check_encrypted_keys refuses an EncryptedRoundKeys (no raw, no fused) with
+        # it, so the schedule here is always a ClearRoundKeys
+        fused = self._schedule.fused
+        if (r, direction) not in fused:
+            fused[(r, direction)] = self._encode_key(shift_rows_bytes(self._schedule.raw[r], direction))
+        return fused[(r, direction)]
 
     def _log_packed(self, dbg, tag: str, ct, **meta) -> None:
         """debug snapshot of a packed (hi | lo) state, decoded to bytes"""
@@ -495,55 +458,48 @@ class AESPipeline:
         one-round debug block, REF :154-171)."""
         if next_level is None:
             next_level = self.need_sub
+        # a debug dict logs the stages of the path every call takes, under the reference's names: the levels, the
+        # folds and the deferred conjugate (a utils.ConjSum is logged as it is, decoded if the encoder can) are
+        # production's own
+        ct = self._sub_apply(ct, defer_conj=True)
+        self._log_pair(debug, f"enc.r{r}.sub", *ct)
         if self.packed_xor and r > 0:
             # packed XOR stage (DESIGN.md §4c): MixColumns returns the packed state, AddRoundKey
-            # XORs it with the packed round key, its renorm unpacks into the (hi, lo) pair.  A debug
-            # dict logs THIS path's stages under the reference's names (the packed ones decoded from
-            # the hi | lo halves), so the golden stage test observes the headline path itself.
-            ct = self._sub_apply(ct, defer_conj=True)
-            self._log_pair(debug, f"enc.r{r}.sub", *ct)
+            # XORs it with the packed round key, its renorm unpacks into the (hi, lo) pair (the packed
+            # stages are logged decoded from the hi | lo halves)
             need = getattr(self.mix, "packed_input_need", None)
             lv = need() if need else NEED_SR_MIX - SHIFTROWS_DEPTH + self.encoder.PACK_DEPTH
-            perm = self._sr_perm(ct, debug)
+            perm = self._fold_perm(self.shift, ct)
+            entry = {}  # mix_packed's keywords when ShiftRows runs (and is logged) inside its entry
             if perm is not None:  # ShiftRows folded into the renorm (a byte permutation of the snap)
                 ct = self.encoder.renorm_perm(*ct, perm, level=lv)
+                self._log_pair(debug, f"enc.r{r}.sr", *ct)
             elif self._sr_entry_ok():
                 # ShiftRows homomorphic inside MixColumns' entry (MixColFinal.sr_entry: masked rotations
                 # fused with the first column shift and the packs, one level): the renorm hands out lv
                 ct = self._renorm_pair(*ct, level=lv)
                 self._log_pair(debug, f"enc.r{r}.sub.renorm", *ct)
                 log_sr = (lambda p0: self._log_packed(debug, f"enc.r{r}.sr", p0)) if debug is not None else None
-                acc = self.mix.mix_packed(*ct, sr=self.shift, on_sr=log_sr)
-                self._log_packed(debug, f"enc.r{r}.mc", acc)
-                x = self._ark_packed(acc, r, defer_conj=True)
-                self._log_packed(debug, f"enc.r{r}.ark", x)
-                ct = self.encoder.renorm_unpack(x, level=next_level)
-                self._log_pair(debug, f"enc.r{r}.ark.renorm", *ct)
-                return ct
+                entry = {"sr": self.shift, "on_sr": log_sr}
             else:
                 ct = self._renorm_pair(*ct, level=lv + SHIFTROWS_DEPTH)
                 self._log_pair(debug, f"enc.r{r}.sub.renorm", *ct)
                 ct = self.shift_rows(*ct)
-            self._log_pair(debug, f"enc.r{r}.sr", *ct)
-            acc = self.mix.mix_packed(*ct)
+                self._log_pair(debug, f"enc.r{r}.sr", *ct)
+            acc = self.mix.mix_packed(*ct, **entry)
             self._log_packed(debug, f"enc.r{r}.mc", acc)
             x = self._ark_packed(acc, r, defer_conj=True)
             self._log_packed(debug, f"enc.r{r}.ark", x)
             ct = self.encoder.renorm_unpack(x, level=next_level)
             self._log_pair(debug, f"enc.r{r}.ark.renorm", *ct)
             return ct
-        if debug is None:
-            ct = self._sub_renorm(ct, level=NEED_SR_MIX)
-            ct = self.srmc(*ct) if self.srmc is not None else self.mix_columns(*self.shift_rows(*ct))
-            return self._ark_renorm(ct, key_pair, level=next_level)
-        ct = self.sub.apply(*ct, out_level=self._floor())
-        self._log_pair(debug, f"enc.r{r}.sub", *ct)
-        ct = self._renorm_pair(*ct, level=NEED_SR_MIX)
+        ct = self._renorm_pair(*ct, level=self._sub_level(NEED_SR_MIX))
         self._log_pair(debug, f"enc.r{r}.sub.renorm", *ct)
         if self.srmc is not None:  # ShiftRows and MixColumns merged (shiftrows_mixcolumns.py)
-            inner = {}
+            inner = {} if debug is not None else None  # the merged step's own ShiftRows output, only when logging
             ct = self.srmc(*ct, debug=inner)
-            self._log_pair(debug, f"enc.r{r}.sr", *inner["sr"])
+            if inner is not None:
+                self._log_pair(debug, f"enc.r{r}.sr", *inner["sr"])
         else:
             ct = self.shift_rows(*ct)
             self._log_pair(debug, f"enc.r{r}.sr", *ct)
@@ -564,9 +520,9 @@ class AESPipeline:
         self._log_pair(debug, "enc.input", *ct)
         rk = self._prepare_round_keys(round_keys)
         ct = self.ark(*ct, *rk[0], out_level=self._floor())
-        return self._encrypt_tail(ct, rk, round_keys, debug)
+        return self._encrypt_tail(ct, rk, debug)
 
-    def _encrypt_tail(self, ct, rk, round_keys, debug):
+    def _encrypt_tail(self, ct, rk, debug):
         """encrypt after round 0's AddRoundKey: its renorm, rounds 1..nr - 1, the final round nr = len(rk) - 1 (shared
         by encrypt and encrypt_public, whose round 0 differs)"""
         nr = len(rk) - 1
@@ -578,24 +534,21 @@ class AESPipeline:
             ct = self.encrypt_round(ct, rk[r], debug, r, next_level=nxt)
         if self.fuse_sub_ark:
             # SR(SB(x)) ^ k_nr = SR(SB(x) ^ InvShiftRows(k_nr)): one fused LUT, then ShiftRows
-            ct = self.sbark(*ct, *self._fused_key(round_keys, nr, +1))
+            ct = self.sbark(*ct, *self._fused_key(nr, +1))
             self._log_pair(debug, "enc.final.sub_ark", *ct)
             ct = self.shift_rows(*ct)
-            self._log_pair(debug, f"enc.final.ark{nr}", *ct)
-            ct = self._renorm_pair(*ct)
-            self._log_pair(debug, "enc.output", *ct)
-            return tag_layout(self.layout, *ct)
-        ct = self._sub_apply(ct, defer_conj=True)
-        self._log_pair(debug, "enc.final.sub", *ct)
-        perm = self._sr_perm(ct, debug)
-        if perm is not None:  # ShiftRows folded into the renorm
-            ct = self.encoder.renorm_perm(*ct, perm, level=NEED_SR_ARK - SHIFTROWS_DEPTH)
         else:
-            ct = self._renorm_pair(*ct, level=NEED_SR_ARK)
-            self._log_pair(debug, "enc.final.sub.renorm", *ct)
-            ct = self.shift_rows(*ct)
-        self._log_pair(debug, "enc.final.sr", *ct)
-        ct = self.ark(*ct, *rk[nr], out_level=self._floor())
+            ct = self._sub_apply(ct, defer_conj=True)
+            self._log_pair(debug, "enc.final.sub", *ct)
+            perm = self._fold_perm(self.shift, ct)
+            if perm is not None:  # ShiftRows folded into the renorm
+                ct = self.encoder.renorm_perm(*ct, perm, level=NEED_SR_ARK - SHIFTROWS_DEPTH)
+            else:
+                ct = self._renorm_pair(*ct, level=NEED_SR_ARK)
+                self._log_pair(debug, "enc.final.sub.renorm", *ct)
+                ct = self.shift_rows(*ct)
+            self._log_pair(debug, "enc.final.sr", *ct)
+            ct = self.ark(*ct, *rk[nr], out_level=self._floor())
         self._log_pair(debug, f"enc.final.ark{nr}", *ct)
         ct = self._renorm_pair(*ct)
         self._log_pair(debug, "enc.output", *ct)
@@ -617,7 +570,7 @@ class AESPipeline:
             debug.clear()
         rk = self._prepare_round_keys(round_keys)
         ct = self.ark.public(*rk[0], *self.encoder.nibble_slots(state), out_level=self._floor())
-        return self._encrypt_tail(ct, rk, round_keys, debug)
+        return self._encrypt_tail(ct, rk, debug)
 
     def ctr_keystream(self, nonce12, counter0: int, round_keys: List[np.ndarray] | EncryptedRoundKeys):
         """the encrypted keystream blocks of counters counter0 .. counter0 + states - 1 (mod 2^32) under the
@@ -678,23 +631,16 @@ class AESPipeline:
         gain * q + offset, q the integer the message bytes spell in `dtype`; every other slot holds 0.
         decode_values returns (states, 16 // w).  dtype "u1" with a scalar gain and no offset is the path above,
         unchanged; any other dtype (32-bit words would add no precision over 16) raises ValueError."""
-        self._no_pairs("transcipher_values")
-        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
-        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
-        typed = self._typed_lut(dtype, gain, offset)
-        lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
-        ks = self.ctr_keystream(nonce12, counter0, round_keys)
-        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
+        out = _transcipher_with(self, "transcipher_values", aes_ct, nonce12, counter0, round_keys,
+                                lambda: _values_lut(self, dtype, gain, offset))
+        return tag_value_dtype(dtype, tag_layout(self.layout, out)[0])
 
     def to_values(self, ct_hi, ct_lo, gain=None, dtype: str = "u1", offset=0.0):
         """a clean layout-tagged (hi, lo) pair -- the output of encrypt, decrypt or transcipher -- as ONE ciphertext of
         gain * byte per state slot (XorValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair); dtype, gain and
         offset as transcipher_values'"""
-        self._no_pairs("to_values")
-        check_layout(self.layout, ct_hi, ct_lo)
-        typed = self._typed_lut(dtype, gain, offset)
-        lut = typed if typed is not None else self._value_lut(1.0 / 256.0 if gain is None else gain)
-        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+        out = _convert_with(self, "to_values", ct_hi, ct_lo, lambda: _values_lut(self, dtype, gain, offset))
+        return tag_value_dtype(dtype, tag_layout(self.layout, out)[0])
 
     # ---------------------------------------------------------------- a linear map fused with the value decode (DESIGN.md §3.22)
     def _linear_lut(self, weight, bias, dtype, in_scale, zero_point):
@@ -713,20 +659,15 @@ class AESPipeline:
         transcipher_values' does (xor_value_lut.LinearValueLUT: the matrix's non-zero cyclic diagonals are weight
         groups of the decode, rotated together in one batched key switch).  Slots that hold no state hold 0;
         encoder.decode_values returns (states, 16)."""
-        self._no_pairs("transcipher_linear")
-        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
-        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
-        lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
-        ks = self.ctr_keystream(nonce12, counter0, round_keys)
-        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
+        out = _transcipher_with(self, "transcipher_linear", aes_ct, nonce12, counter0, round_keys,
+                                lambda: self._linear_lut(weight, bias, dtype, in_scale, zero_point))
+        return tag_value_dtype(dtype, tag_layout(self.layout, out)[0])
 
     def to_linear(self, ct_hi, ct_lo, weight, bias=0.0, dtype: str = "i1", in_scale=None, zero_point=0):
         """a clean layout-tagged (hi, lo) pair as ONE ciphertext of weight (bytes - zero_point) * in_scale + bias per
         state (LinearValueLUT.apply; utils.XOR_VALUE_DEPTH levels below the pair); arguments as transcipher_linear's"""
-        self._no_pairs("to_linear")
-        check_layout(self.layout, ct_hi, ct_lo)
-        lut = self._linear_lut(weight, bias, dtype, in_scale, zero_point)
-        return tag_value_dtype(dtype, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+        out = _convert_with(self, "to_linear", ct_hi, ct_lo, lambda: self._linear_lut(weight, bias, dtype, in_scale, zero_point))
+        return tag_value_dtype(dtype, tag_layout(self.layout, out)[0])
 
     # ---------------------------------------------------------------- a 256-entry byte table fused with the value decode (DESIGN.md §3.23)
     def _byte_lut(self, table, gain):
@@ -746,20 +687,14 @@ class AESPipeline:
         utils.BYTE_LUT_DEPTH = 5 levels below the keystream (one ct x ct level more than transcipher_values; 2 levels
         left on the fresh-level-7 set); no XOR4, renorm or bootstrap comes after the keystream
         (xor_value_lut.ByteValueLUT).  Slots that hold no state hold 0; encoder.decode_values returns (states, 16)."""
-        self._no_pairs("transcipher_lut")
-        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
-        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
-        lut = self._byte_lut(table, gain)
-        ks = self.ctr_keystream(nonce12, counter0, round_keys)
-        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, lut.apply_public(*ks, *nib))[0])
+        out = _transcipher_with(self, "transcipher_lut", aes_ct, nonce12, counter0, round_keys, lambda: self._byte_lut(table, gain))
+        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, out)[0])
 
     def to_lut(self, ct_hi, ct_lo, table, gain=1.0):
         """a clean layout-tagged (hi, lo) pair as ONE ciphertext of gain * table[byte] per state slot
         (ByteValueLUT.apply; utils.BYTE_LUT_DEPTH levels below the pair); table and gain as transcipher_lut's"""
-        self._no_pairs("to_lut")
-        check_layout(self.layout, ct_hi, ct_lo)
-        lut = self._byte_lut(table, gain)
-        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, lut.apply(ct_hi, ct_lo))[0])
+        out = _convert_with(self, "to_lut", ct_hi, ct_lo, lambda: self._byte_lut(table, gain))
+        return tag_value_dtype(LUT_VALUE_TAG, tag_layout(self.layout, out)[0])
 
     # ---------------------------------------------------------------- a bank of byte tables: a table per slot, several outputs (DESIGN.md §3.26)
     def _byte_bank(self, tables, select, gain):
@@ -793,20 +728,14 @@ class AESPipeline:
         once for all outputs (xor_value_lut.ByteValueBank); every output sits utils.BYTE_LUT_DEPTH = 5 levels below the
         keystream, as transcipher_lut's.  Slots that hold no state hold 0; encoder.decode_values reads each output as
         (states, 16)."""
-        self._no_pairs("transcipher_lut_bank")
-        round_count(round_keys)  # 11 / 13 / 15 keys, checked before any GPU work
-        nib = self.encoder.nibble_slots(aes_ct)  # checks the shape before any GPU work
-        bank = self._byte_bank(tables, select, gain)
-        ks = self.ctr_keystream(nonce12, counter0, round_keys)
-        return self._tag_bank(bank.apply_public(*ks, *nib))
+        return self._tag_bank(_transcipher_with(self, "transcipher_lut_bank", aes_ct, nonce12, counter0, round_keys,
+                                                lambda: self._byte_bank(tables, select, gain)))
 
     def to_lut_bank(self, ct_hi, ct_lo, tables, select, gain=1.0):
         """a clean layout-tagged (hi, lo) pair as K ciphertexts of gain_k * tables[select[k]][byte] per state slot
         (ByteValueBank.apply; utils.BYTE_LUT_DEPTH levels below the pair); tables, select and gain as
         transcipher_lut_bank's"""
-        self._no_pairs("to_lut_bank")
-        check_layout(self.layout, ct_hi, ct_lo)
-        return self._tag_bank(self._byte_bank(tables, select, gain).apply(ct_hi, ct_lo))
+        return self._tag_bank(_convert_with(self, "to_lut_bank", ct_hi, ct_lo, lambda: self._byte_bank(tables, select, gain)))
 
     # ---------------------------------------------------------------- decrypt
     def decrypt(self, ct_hi, ct_lo, round_keys: List[np.ndarray] | EncryptedRoundKeys, debug: Dict[str, Any] | None = None):
@@ -825,8 +754,8 @@ class AESPipeline:
         if fuse and self.isub is None:
             raise KeyError("inv_sub_hi")
         # InvShiftRows folded into the renorm before it (the packed decrypt: this renorm and every
-        # InvMixColumns renorm), as ShiftRows in encrypt (pipeline._sr_perm)
-        isr = self._isr_perm(ct, debug) if self.packed_dec and not fuse else None
+        # InvMixColumns renorm), as ShiftRows in encrypt
+        isr = self._fold_perm(self.invshift, ct) if self.packed_dec and not fuse else None
         if isr is not None:
             ct, isr_done = self.encoder.renorm_perm(*ct, isr, level=self.need_isr_isb - SHIFTROWS_DEPTH), True
         else:
@@ -835,7 +764,7 @@ class AESPipeline:
         for r in range(nr - 1, 0, -1):
             if fuse:
                 # ISB(ISR(x)) ^ k_r = ISR(ISB(x) ^ ShiftRows(k_r)): one fused LUT, then InvShiftRows
-                ct = self.isbark(*ct, *self._fused_key(round_keys, r, -1))
+                ct = self.isbark(*ct, *self._fused_key(r, -1))
                 self._log_pair(debug, f"dec.r{r}.isb_ark", *ct)
                 ct = self.inv_shift_rows(*ct)
                 ct = self._renorm_pair(*ct, level=NEED_GF if self.with_inv_mix_columns else NEED_SUB_ARK_SR)
@@ -876,23 +805,20 @@ class AESPipeline:
                 ct = self._renorm_pair(*self.inv_mix_columns(*ct), level=self.need_isr_isb)
                 self._log_pair(debug, f"dec.r{r}.imc", *ct)
         if fuse:
-            ct = self.isbark(*ct, *self._fused_key(round_keys, 0, -1))
+            ct = self.isbark(*ct, *self._fused_key(0, -1))
             self._log_pair(debug, "dec.final.isb_ark", *ct)
             ct = self.inv_shift_rows(*ct)
-            self._log_pair(debug, "dec.final.ark0", *ct)
-            ct = self._renorm_pair(*ct)
-            self._log_pair(debug, "dec.output", *ct)
-            return ct
-        if not isr_done:
-            ct = self.inv_shift_rows(*ct)
-        self._log_pair(debug, "dec.final.isr", *ct)
-        if self.isub is None:
-            raise KeyError("inv_sub_hi")
-        ct = self.isub.apply(*ct, out_level=self._floor())
-        self._log_pair(debug, "dec.final.isb", *ct)
-        ct = self._renorm_pair(*ct, level=NEED_XOR)
-        self._log_pair(debug, "dec.final.isb.renorm", *ct)
-        ct = self.ark(*ct, *rk[0], out_level=self._floor())
+        else:
+            if not isr_done:
+                ct = self.inv_shift_rows(*ct)
+            self._log_pair(debug, "dec.final.isr", *ct)
+            if self.isub is None:
+                raise KeyError("inv_sub_hi")
+            ct = self.isub.apply(*ct, out_level=self._floor())
+            self._log_pair(debug, "dec.final.isb", *ct)
+            ct = self._renorm_pair(*ct, level=NEED_XOR)
+            self._log_pair(debug, "dec.final.isb.renorm", *ct)
+            ct = self.ark(*ct, *rk[0], out_level=self._floor())
         self._log_pair(debug, "dec.final.ark0", *ct)
         ct = self._renorm_pair(*ct)
         self._log_pair(debug, "dec.output", *ct)

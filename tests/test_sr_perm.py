@@ -1,5 +1,5 @@
 """ShiftRows / InvShiftRows as byte permutations (shift_rows.ShiftRows.slot_perm, folded into the
-periodic renorm by pipeline._sr_perm / aesfhe_renorm_periodic_perm): output byte i <- input byte
+periodic renorm by pipeline._fold_perm / aesfhe_renorm_periodic_perm): output byte i <- input byte
 perm[i] must be the FIPS-197 ShiftRows of oracle/aes_plain.py for the one-state periodic layout,
 and None for layouts where a byte is not one slot."""
 import numpy as np

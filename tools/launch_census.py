@@ -50,7 +50,7 @@ def main():
     for _ in range(reps):
         lv = pipe.mix.packed_input_need() + SHIFTROWS_DEPTH if packed else NEED_SR_MIX  # the pipeline's own level
 
-        perm = pipe._sr_perm(ct0, None) if packed else None  # the pipeline folds ShiftRows into this renorm
+        perm = pipe._fold_perm(pipe.shift, ct0) if packed else None  # the pipeline folds ShiftRows into this renorm
 
         def sub_step():
             if perm is not None:
