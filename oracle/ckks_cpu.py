@@ -58,6 +58,11 @@ def lib():
         "orc_embed_inverse": (None, [vp, f64p, f64p, f64p]),
         "orc_embed": (None, [vp, f64p, f64p, f64p]),
         "orc_encode": (None, [vp, f64p, f64p, c_dbl, c_int, u32p]),
+        "orc_encode_ext": (None, [vp, f64p, f64p, c_dbl, c_int, c_int, u32p]),
+        "orc_ks_digits": (c_int, [vp, c_int, c_int]),
+        "orc_modup": (c_int, [vp, c_int, c_int, u32p, u32p]),
+        "orc_key_inner": (c_int, [vp, c_int, c_int, c_u64, u32p, u32p, u32p, u32p]),
+        "orc_moddown": (c_int, [vp, c_int, c_int, u32p, ctypes.c_void_p, ctypes.c_void_p, u32p]),
         "orc_secret": (None, [vp, i32p]),
         "orc_secret_ntt": (None, [vp, u32p]),
         "orc_gen_pk": (None, [vp, u32p]),
@@ -147,6 +152,13 @@ class OracleParams:
         self._L.orc_encode(self.h, np.ascontiguousarray(z.real), np.ascontiguousarray(z.imag), float(scale), nl, out)
         return out
 
+    def encode_ext(self, z: np.ndarray, scale: float, nl: int, np_: int) -> np.ndarray:
+        """encode onto limbs 0..nl-1 AND the first np_ special primes: [nl + np_][N], the masks of a sum over Q P"""
+        z = np.broadcast_to(np.asarray(z, np.complex128), (self.slot_count,))
+        out = np.zeros((nl + np_, self.n), np.uint32)
+        self._L.orc_encode_ext(self.h, np.ascontiguousarray(z.real), np.ascontiguousarray(z.imag), float(scale), nl, int(np_), out)
+        return out
+
     # -- keys ------------------------------------------------------------------------------
     def secret(self) -> np.ndarray:
         s = np.zeros(self.n, np.int32)
@@ -201,6 +213,64 @@ class OracleParams:
     def keyswitch(self, level: int, d: np.ndarray, ksk: np.ndarray) -> np.ndarray:
         out = np.zeros((2, self.nl(level), self.n), np.uint32)
         self._L.orc_keyswitch(self.h, level, np.ascontiguousarray(d, np.uint32), np.ascontiguousarray(ksk, np.uint32), out)
+        return out
+
+    # -- the three steps of the key switch on their own.  np_: the special primes of the basis;
+    #    None or n_p is the full basis (digits of alpha limbs, gen_ksk's keys), any other count one digit of all nl
+    #    limbs with a [2][nl + np_][N] key -- the reduced per-level basis at np_ = nl + 1 (gen_ksk_low's keys).  The
+    #    count alone tells them apart: n_p = alpha + 1, and a reduced level has nl < alpha, so nl + 1 is never n_p
+    def _np(self, np_):
+        return self.n_p if np_ is None else int(np_)
+
+    def ext_moduli(self, level: int, np_=None) -> np.ndarray:
+        """the moduli of the extended rows: Q limbs 0..nl-1, then the first np_ special primes"""
+        return np.concatenate([self.moduli[: self.nl(level)], self.moduli[self.n_q: self.n_q + self._np(np_)]])
+
+    def ks_digits(self, level: int, np_=None) -> int:
+        nd = self._L.orc_ks_digits(self.h, int(level), self._np(np_))
+        if nd < 0:
+            raise ValueError(f"no key-switching basis of {np_} special primes at level {level}")
+        return nd
+
+    def modup(self, level: int, d: np.ndarray, np_=None) -> np.ndarray:
+        """d [nl][N] -> the extended digits [nd][nl + np_][N]"""
+        np_ = self._np(np_)
+        d = np.ascontiguousarray(d, np.uint32)
+        if d.shape != (self.nl(level), self.n):
+            raise ValueError(f"modup: shape {d.shape} at level {level}")
+        out = np.zeros((self.ks_digits(level, np_), self.nl(level) + np_, self.n), np.uint32)
+        if self._L.orc_modup(self.h, int(level), np_, d, out):
+            raise ValueError("modup: bad basis")
+        return out
+
+    def key_inner(self, level: int, ext: np.ndarray, d: np.ndarray, key: np.ndarray, g: int = 1, np_=None) -> np.ndarray:
+        """the accumulator [2][nl + np_][N] = sum over digits of (extended rows, the own digit's from d) (.) key,
+        every source word read through X -> X^g (g = 1: the plain read)"""
+        np_ = self._np(np_)
+        nl, nd = self.nl(level), self.ks_digits(level, np_)
+        ext, d, key = (np.ascontiguousarray(x, np.uint32) for x in (ext, d, key))
+        rows = self.n_ks + self.n_p if np_ == self.n_p else nl + np_
+        if ext.shape != (nd, nl + np_, self.n) or d.shape != (nl, self.n) or key.size < nd * 2 * rows * self.n or key.shape[-2:] != (rows, self.n):
+            raise ValueError(f"key_inner: shapes {ext.shape} / {d.shape} / {key.shape} at level {level}, {np_} special primes")
+        out = np.zeros((2, nl + np_, self.n), np.uint32)
+        if self._L.orc_key_inner(self.h, int(level), np_, int(g), ext, d, key, out):
+            raise ValueError("key_inner: bad basis or Galois element (odd, below 2N)")
+        return out
+
+    def moddown(self, level: int, acc: np.ndarray, add0=None, add1=None, np_=None) -> np.ndarray:
+        """the accumulator [2][nl + np_][N] divided by P (centred), plus the Q-side addends add0 (c0) / add1 (c1)"""
+        np_ = self._np(np_)
+        nl = self.nl(level)
+        acc = np.ascontiguousarray(acc, np.uint32)
+        if acc.shape != (2, nl + np_, self.n):
+            raise ValueError(f"moddown: shape {acc.shape} at level {level}, {np_} special primes")
+        adds = [None if a is None else np.ascontiguousarray(a, np.uint32) for a in (add0, add1)]
+        if any(a is not None and a.shape != (nl, self.n) for a in adds):
+            raise ValueError("moddown: addends are [nl][N]")
+        ptr = [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in adds]
+        out = np.zeros((2, nl, self.n), np.uint32)
+        if self._L.orc_moddown(self.h, int(level), np_, acc, ptr[0], ptr[1], out):
+            raise ValueError("moddown: bad basis")
         return out
 
     def tensor(self, level: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:

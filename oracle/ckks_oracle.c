@@ -456,22 +456,28 @@ static i128 round_i128(double x) {
     return (i128)x;
 }
 
-/* encode z at `scale` onto limbs 0..nl-1 (NTT form) */
-void orc_encode(void *h, const double *zre, const double *zim, double scale, int nl, u32 *out) {
+/* encode z at `scale` onto limbs 0..nl-1 and the first np special primes (NTT form, [nl + np][N]) */
+void orc_encode_ext(void *h, const double *zre, const double *zim, double scale, int nl, int np, u32 *out) {
     orc_t *o = (orc_t *)h;
-    int n = o->n;
+    int n = o->n, ne = nl + np;
     double *m = (double *)malloc(sizeof(double) * n);
     orc_embed_inverse(h, zre, zim, m);
     for (int k = 0; k < n; k++) {
         i128 v = round_i128(m[k] * scale);
-        for (int i = 0; i < nl; i++) {
-            i128 r = v % (i128)o->mod[i];
-            if (r < 0) r += o->mod[i];
+        for (int i = 0; i < ne; i++) {
+            u32 q = o->mod[i < nl ? i : o->n_q + (i - nl)];
+            i128 r = v % (i128)q;
+            if (r < 0) r += q;
             out[(size_t)i * n + k] = (u32)r;
         }
     }
     free(m);
-    for (int i = 0; i < nl; i++) ntt_limb(o, i, out + (size_t)i * n);
+    for (int i = 0; i < ne; i++) ntt_limb(o, i < nl ? i : o->n_q + (i - nl), out + (size_t)i * n);
+}
+
+/* encode z at `scale` onto limbs 0..nl-1 (NTT form) */
+void orc_encode(void *h, const double *zre, const double *zim, double scale, int nl, u32 *out) {
+    orc_encode_ext(h, zre, zim, scale, nl, 0, out);
 }
 
 /* ------------------------------------------------------------------ */
@@ -857,6 +863,112 @@ int orc_keyswitch_low(void *h, int level, int nsrc, const u32 *d, const u32 *ksk
     orc_t *o = (orc_t *)h;
     if (level < 0 || level > o->L || NL(o, level) >= o->alpha || nsrc < 1 || nsrc > 2) return -1;
     keyswitch_one_digit(o, NL(o, level), NL(o, level) + 1, nsrc, d, ksk, out);
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* the three steps on their own: the doubly-hoisted sums */
+/* multiply and add in Q P between the inner product and the ModDown,   */
+/* so they are no composition of whole key switches.  np = the special  */
+/* primes of the basis: n_p is the full basis (digits of alpha limbs,   */
+/* orc_gen_ksk's key layout [dnum][2][n_ks + n_p][N]); any other count  */
+/* is keyswitch_one_digit's shape (one digit of all nl limbs, key       */
+/* [2][nl + np][N]), the reduced per-level basis at np = nl + 1.  The   */
+/* count alone tells the two apart: n_p = alpha + 1 in both builders,   */
+/* and a level has a reduced basis only below alpha limbs, so its       */
+/* nl + 1 <= alpha never equals n_p.                                    */
+/* Thin wrappers over the static steps above: no arithmetic of their    */
+/* own but the final addm of the ModDown's addends.                     */
+/* ------------------------------------------------------------------ */
+typedef struct { int nl, np, ne, nd, alpha, nkey; int *gid, *kid; } ksb_t;
+static int ksb_open(const orc_t *o, int level, int np, ksb_t *b) {
+    if (level < 0 || level > o->L || np < 1 || np > o->n_p) return -1;
+    int full = np == o->n_p;
+    b->nl = NL(o, level); b->np = np; b->ne = b->nl + np;
+    b->alpha = full ? o->alpha : b->nl;
+    b->nd = (b->nl + b->alpha - 1) / b->alpha;
+    b->nkey = full ? o->n_ks + o->n_p : b->ne;
+    b->gid = (int *)malloc(sizeof(int) * b->ne);
+    b->kid = (int *)malloc(sizeof(int) * b->ne);
+    for (int x = 0; x < b->ne; x++) {
+        b->gid[x] = x < b->nl ? x : o->n_q + (x - b->nl);
+        b->kid[x] = x < b->nl || !full ? x : o->n_ks + (x - b->nl);
+    }
+    return 0;
+}
+static void ksb_close(ksb_t *b) { free(b->gid); free(b->kid); }
+
+/* digits of the basis (level, np), or -1: the first dimension of orc_modup's output */
+int orc_ks_digits(void *h, int level, int np) {
+    ksb_t b;
+    if (ksb_open((const orc_t *)h, level, np, &b)) return -1;
+    ksb_close(&b);
+    return b.nd;
+}
+
+/* ModUp: d [nl][N] (NTT form) -> ext [nd][nl + np][N], digit j's own rows copied from d */
+int orc_modup(void *h, int level, int np, const u32 *d, u32 *ext) {
+    orc_t *o = (orc_t *)h;
+    ksb_t b;
+    if (ksb_open(o, level, np, &b)) return -1;
+    int n = o->n;
+    u32 *coef = (u32 *)malloc(sizeof(u32) * (size_t)b.nl * n);
+    memcpy(coef, d, sizeof(u32) * (size_t)b.nl * n);
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < b.nl; i++) intt_limb(o, i, coef + (size_t)i * n);
+    for (int j = 0; j < b.nd; j++) {
+        int lo = j * b.alpha, hi = lo + b.alpha < b.nl ? lo + b.alpha : b.nl;
+        modup_digit(o, d, coef, lo, hi, b.gid, b.ne, ext + (size_t)j * b.ne * n);
+    }
+    free(coef);
+    ksb_close(&b);
+    return 0;
+}
+
+/* inner product: acc [2][nl + np][N] = sum_j src_j (.) key_j, src_j = digit j's extended rows with its own rows
+ * taken from d (as the kernels take them), every row read through X -> X^g (g = 1: the plain read) */
+int orc_key_inner(void *h, int level, int np, u64 g, const u32 *ext, const u32 *d, const u32 *key, u32 *acc) {
+    orc_t *o = (orc_t *)h;
+    ksb_t b;
+    if (ksb_open(o, level, np, &b)) return -1;
+    if (!(g & 1) || g >= 2ull * o->n) { ksb_close(&b); return -1; }
+    int n = o->n;
+    memset(acc, 0, sizeof(u32) * (size_t)2 * b.ne * n);
+    u32 *src = (u32 *)malloc(sizeof(u32) * (size_t)b.ne * n);
+    for (int j = 0; j < b.nd; j++) {
+        int lo = j * b.alpha, hi = lo + b.alpha < b.nl ? lo + b.alpha : b.nl;
+#pragma omp parallel for schedule(static)
+        for (int x = 0; x < b.ne; x++) {
+            const u32 *row = x >= lo && x < hi ? d + (size_t)x * n : ext + ((size_t)j * b.ne + x) * n;
+            if (g == 1) memcpy(src + (size_t)x * n, row, sizeof(u32) * n);
+            else automorph_limb(o, b.gid[x], g, row, src + (size_t)x * n);
+        }
+        const u32 *kb = key + (size_t)j * 2 * b.nkey * n, *ka = kb + (size_t)b.nkey * n;
+        key_inner_acc(o, src, b.gid, b.kid, b.ne, kb, ka, acc);
+    }
+    free(src);
+    ksb_close(&b);
+    return 0;
+}
+
+/* ModDown: acc [2][nl + np][N] -> out [2][nl][N], plus the Q-side addends add0 (to c0) and add1 (to c1), each
+ * [nl][N] or NULL */
+int orc_moddown(void *h, int level, int np, const u32 *acc, const u32 *add0, const u32 *add1, u32 *out) {
+    orc_t *o = (orc_t *)h;
+    ksb_t b;
+    if (ksb_open(o, level, np, &b)) return -1;
+    int n = o->n;
+    moddown(o, acc, b.nl, np, out);
+    for (int p = 0; p < 2; p++) {
+        const u32 *add = p ? add1 : add0;
+        if (!add) continue;
+        for (int t = 0; t < b.nl; t++)
+            for (int k = 0; k < n; k++) {
+                size_t x = (size_t)t * n + k;
+                out[(size_t)p * b.nl * n + x] = addm(out[(size_t)p * b.nl * n + x], add[x], o->mod[t]);
+            }
+    }
+    ksb_close(&b);
     return 0;
 }
 

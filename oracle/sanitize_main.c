@@ -25,6 +25,11 @@ void orc_intt(void *h, const int *limbs, int nl, u32 *data);
 void orc_embed_inverse(void *h, const double *zre, const double *zim, double *m_out);
 void orc_embed(void *h, const double *m, double *zre, double *zim);
 void orc_encode(void *h, const double *zre, const double *zim, double scale, int nl, u32 *out);
+void orc_encode_ext(void *h, const double *zre, const double *zim, double scale, int nl, int np, u32 *out);
+int orc_ks_digits(void *h, int level, int np);
+int orc_modup(void *h, int level, int np, const u32 *d, u32 *ext);
+int orc_key_inner(void *h, int level, int np, u64 g, const u32 *ext, const u32 *d, const u32 *key, u32 *acc);
+int orc_moddown(void *h, int level, int np, const u32 *acc, const u32 *add0, const u32 *add1, u32 *out);
 void orc_secret(void *h, int *s_out);
 void orc_secret_ntt(void *h, u32 *out);
 void orc_gen_pk(void *h, u32 *out);
@@ -75,6 +80,19 @@ static u32 *rand_poly(const chain_t *c, int npoly, int nl) {
     return p;
 }
 
+/* the three steps of the key switch on the basis of np special primes at level l: ModUp, the inner product read
+ * plainly and through X -> X^5, ModDown with and without addends; key: the basis's own layout */
+static void three_steps(const chain_t *c, int l, int np, const u32 *d, const u32 *key) {
+    const int n = c->n, nl = nl_of(c, l), ne = nl + np, nd = orc_ks_digits(c->h, l, np);
+    if (nd < 1) exit(4);
+    u32 *ext = xalloc((size_t)nd * ne * n), *acc = xalloc((size_t)2 * ne * n), *out = xalloc((size_t)2 * nl * n);
+    if (orc_modup(c->h, l, np, d, ext)) exit(4);
+    if (orc_key_inner(c->h, l, np, 1, ext, d, key, acc) || orc_key_inner(c->h, l, np, 5, ext, d, key, acc)) exit(4);
+    if (orc_key_inner(c->h, l, np, 4, ext, d, key, acc) != -1) exit(4);  /* an even element is refused */
+    if (orc_moddown(c->h, l, np, acc, NULL, NULL, out) || orc_moddown(c->h, l, np, acc, d, d, out)) exit(4);
+    free(ext); free(acc); free(out);
+}
+
 static void open_chain(chain_t *c, void *h, int L1) {
     int info[8];
     c->h = h;
@@ -104,6 +122,10 @@ static void exercise(chain_t *c) {
     const int f = c->L1 < L ? c->L1 - 2 : L;  /* the engine's fresh level on a bootstrappable chain */
     u32 *pt = xalloc((size_t)nl_of(c, f + 1) * n);
     orc_encode(c->h, zr, zi, delta[f] * (double)c->mod[nl_of(c, f)], nl_of(c, f + 1), pt);
+    u32 *ptx = xalloc((size_t)(nl_of(c, f) + c->n_p) * n);  /* a mask over Q P: the Q limbs and every special prime */
+    orc_encode_ext(c->h, zr, zi, delta[f], nl_of(c, f), c->n_p, ptx);
+    free(ptx);
+    if (orc_ks_digits(c->h, L + 1, c->n_p) != -1 || orc_ks_digits(c->h, 0, c->n_p + 1) != -1) exit(4);
     /* keys */
     int *s = (int *)calloc(n, sizeof(int));
     orc_secret(c->h, s);
@@ -123,10 +145,12 @@ static void exercise(chain_t *c) {
         u32 *a = rand_poly(c, 2, nl), *b = rand_poly(c, 2, nl);
         u32 *o3 = xalloc((size_t)3 * nl * n), *o2 = xalloc((size_t)2 * nl * n);
         orc_keyswitch(c->h, l, a + (size_t)nl * n, ksk, o2);
+        three_steps(c, l, c->n_p, a, ksk);
         if (nl < c->alpha) {  /* a reduced level: its own key, one source, then two summed before the ModDown */
             u32 *klow = xalloc((size_t)2 * 2 * (2 * nl + 1) * n);
             if (orc_gen_ksk_low(c->h, 0, l, klow) || orc_gen_ksk_low(c->h, 5, l, klow + (size_t)2 * (2 * nl + 1) * n)) exit(3);
             if (orc_keyswitch_low(c->h, l, 1, a, klow, o2) || orc_keyswitch_low(c->h, l, 2, a, klow, o2)) exit(3);
+            three_steps(c, l, nl + 1, a, klow);
             free(klow);
         } else if (orc_gen_ksk_low(c->h, 0, l, o2) != -1 || orc_keyswitch_low(c->h, l, 1, a, ksk, o2) != -1) {
             exit(3);  /* an unreduced level is refused, nothing written */

@@ -107,3 +107,61 @@ def conv_top_digits(O, nl, alpha):
     """conv_top of every key-switching digit of a polynomial of nl limbs (digits of alpha limbs, the last one
     partial): the d operand that saturates every ModUp conversion at once"""
     return np.concatenate([conv_top(O, range(lo, min(lo + alpha, nl))) for lo in range(0, nl, alpha)])
+
+
+# ----------------------------------------------------------------------------- plaintexts with known residues
+# A slot vector z = embed(m) / scale encodes, at `scale`, to the small integer polynomial m exactly: the inverse
+# embedding returns m / scale to a relative 1e-13 or so, the product with the scale is m to far better than 1/2,
+# and the encoder's rounding lands on m.  The plaintext residues on every Q and P row are then NTT(m mod q) -- known
+# without trusting either float encoder (tests/test_oracle_hoisted.py asserts it of the oracle's, the GPU parity
+# tests of the engine's).  Each builder returns (z, m): the slots to hand to encode, and the int64 polynomial.
+def pt_scale(scales, moduli, level, nl=lambda l: l + 2):
+    """the engine's plaintext scale of `level` (csrc/params.cpp ptscale[l]), the same expression in the same order:
+    scales = E.scales() / O.deltas, moduli = E.moduli() / O.moduli"""
+    qd = 1.0
+    for t in range(nl(level - 1), nl(level)):
+        qd *= float(moduli[t])
+    return float(scales[level - 1]) * qd / float(scales[level])
+
+
+def pt_from_poly(O, m, scale):
+    """(z, m) for any integer polynomial m with |m_k| well below 2^40; z is never constant across the slots (the
+    engines take a constant plaintext as a scalar by exact equality): a constant one has slot 1 nudged by a
+    relative 1e-12, which moves no coefficient by more than 1e-12 |m_0|"""
+    m = np.asarray(m, np.int64).reshape(-1)
+    if m.shape != (O.n,) or np.abs(m).max() >= 1 << 40:
+        raise ValueError("pt_from_poly: N small integer coefficients")
+    z = O.embed(m.astype(np.float64)) / float(scale)
+    if np.all(z == z[0]):
+        z = z.copy()
+        z[1] = z[1] * (1.0 + 1e-12)
+    assert not np.all(z == z[0])
+    return z, m
+
+
+def pt_top(O, scale):
+    """m = -1: every residue of the NTT form is q - 1, on every row, special primes included"""
+    m = np.zeros(O.n, np.int64)
+    m[0] = -1
+    return pt_from_poly(O, m, scale)
+
+
+def pt_impulse(O, scale, k=None):
+    """m = -X^k (k = N / 2 + 1 unless given): the NTT form is minus a power of each row's 2N-th root per word,
+    residues over the whole of [0, q)"""
+    m = np.zeros(O.n, np.int64)
+    m[O.n // 2 + 1 if k is None else k] = -1
+    return pt_from_poly(O, m, scale)
+
+
+def pt_small(O, scale, seed):
+    """random coefficients in +-2^20: a mask of ordinary size, every residue different"""
+    m = np.random.default_rng(seed).integers(-(1 << 20), (1 << 20) + 1, O.n)
+    return pt_from_poly(O, m, scale)
+
+
+def poly_ntt(O, m, limbs):
+    """NTT form of the integer polynomial m on the oracle's primes `limbs`: [len(limbs)][N]"""
+    limbs = list(limbs)
+    q = O.moduli[limbs].astype(np.int64)[:, None]
+    return O.ntt((np.asarray(m, np.int64)[None, :] % q).astype(np.uint32), limbs)

@@ -74,3 +74,31 @@ def test_conv_top_digits_layout(O):
     assert d.shape == (nl, O.n)
     assert np.array_equal(d[8:11], ep.conv_top(O, range(8, 11)))
     assert np.array_equal(d[4:8], ep.conv_top(O, range(4, 8)))
+
+
+def test_plaintext_builders(O):
+    """pt_top / pt_impulse / pt_small: slot vectors that are non-constant by exact equality and encode, at the scale
+    they were built for, to the polynomial they return (tests/test_oracle_hoisted.py runs every row and level)"""
+    level = 5
+    sc = ep.pt_scale(O.deltas, O.moduli, level)
+    assert sc == O.deltas[level - 1] * float(O.moduli[level + 1]) / O.deltas[level]  # csrc/params.cpp ptscale[l]
+    nl = O.nl(level)
+    limbs = list(range(nl)) + list(range(O.n_q, O.n_q + O.n_p))
+    built = {"top": ep.pt_top(O, sc), "impulse": ep.pt_impulse(O, sc), "small": ep.pt_small(O, sc, 3)}
+    for name, (z, m) in built.items():
+        assert z.dtype == np.complex128 and z.shape == (O.slot_count,) and m.dtype == np.int64 and m.shape == (O.n,), name
+        assert not (z == z[0]).all(), name
+        assert np.array_equal(O.encode_ext(z, sc, nl, O.n_p), ep.poly_ntt(O, m, limbs)), name
+    z, m = built["top"]
+    assert m[0] == -1 and not m[1:].any()
+    assert np.allclose(z * sc, -1.0, rtol=1e-11, atol=0) and np.count_nonzero(z != z[0]) == 1  # one nudged slot
+    assert np.array_equal(ep.poly_ntt(O, m, limbs), ep.top(O.moduli[limbs], O.n))
+    z, m = built["impulse"]
+    assert np.count_nonzero(m) == 1 and m[O.n // 2 + 1] == -1
+    enc = ep.poly_ntt(O, m, limbs)
+    assert all(len(np.unique(r)) == O.n for r in enc)  # N distinct residues per row: minus the odd powers of psi
+    z, m = built["small"]
+    assert np.abs(m).max() <= 1 << 20 and len(np.unique(m)) > O.n // 2
+    assert np.array_equal(ep.pt_small(O, sc, 3)[1], m) and not np.array_equal(ep.pt_small(O, sc, 4)[1], m)
+    with pytest.raises(ValueError):
+        ep.pt_from_poly(O, np.zeros(O.n - 1, np.int64), sc)
